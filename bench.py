@@ -1,6 +1,6 @@
 """Headline benchmark: stitched image-pairs/s at 512x512 (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload 512|1024]
+    python bench.py --gpus N --steps K --warmup W [--workload 512|1024] [--dump-outputs DIR]
 
 N > 1: if the process was not started by ``torch.distributed.run`` it starts
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`` itself (as a child: this parent
@@ -39,6 +39,7 @@ sys.path.insert(0, ROOT)
 FP32_MFMA_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 = vector fp32 peak
 HBM_PEAK_GBS = 8000.0
 BF16_MFMA_PEAK_TFLOPS = 2500.0    # MI355X_MICROARCH.md: dense bf16 MFMA (v_mfma_f32_32x32x16_bf16: 32 cycles per SIMD), no sparsity
+DUMP_LIMIT_BYTES = 60 << 20       # --dump-outputs: array data of all files together (below 64 MB with the .npy headers)
 
 
 def parse_args(argv=None):
@@ -63,7 +64,13 @@ def parse_args(argv=None):
                     help="the harness is timed twice: one pair per forward (like `value`) and batches of this size (the reference's loader "
                          "batches 12, evaluate.py:34) -> harness_batched_pairs_per_s; 0 or 1 = skip the batched pass")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal on a 1-GPU box: every rank computes on cuda:0 (use with --backend gloo; RCCL needs one GPU per rank)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES >> 20} MiB in all (a fixed seeded sample of each array when the whole would exceed it)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------- launcher (no GPU use)
@@ -72,6 +79,8 @@ def launcher_command(args, port):
     fwd = ["--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--workload", args.workload,
            "--streams", str(args.streams), "--batch", str(args.batch), "--backend", args.backend, "--harness", args.harness,
            "--harness-pairs", str(args.harness_pairs), "--harness-batch", str(args.harness_batch)]
+    if args.dump_outputs:
+        fwd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     for flag, on in (("--no-cpu-baseline", args.no_cpu_baseline), ("--no-corr-roofline", args.no_corr_roofline),
                      ("--eager", args.eager), ("--dry-run", args.dry_run), ("--share-gpu", args.share_gpu)):
         if on:
@@ -165,6 +174,44 @@ def provenance(path):
     raw = open(path, "rb").read()
     return {"file": os.path.relpath(path, ROOT), "mtime_utc": datetime.datetime.utcfromtimestamp(os.path.getmtime(path)).strftime("%Y-%m-%dT%H:%M:%SZ"),
             "sha16": hashlib.sha256(raw).hexdigest()[:16], "head": raw[:96].decode("utf-8", "replace").replace("\n", " ")}
+
+
+def dump_outputs(path, outputs, limit=DUMP_LIMIT_BYTES):
+    """``--dump-outputs``: write the dict a caller of the timed path receives as ``path/<name>.npy`` (list entries as
+    ``<name>_<i>``).  fp64 results stay float64 (as do integers, exactly), everything else is written as float32.  When the
+    arrays together exceed ``limit`` bytes, every array of more than 65536 elements keeps the same fraction of them: a sorted
+    sample of flat indices drawn with a seed fixed by the array's name, so two builds write the same elements.  Returns {name: [shape, sampled]}."""
+    import zlib
+    import numpy as np
+    import torch
+    arrays = {}
+
+    def add(name, v):
+        if isinstance(v, (list, tuple)):
+            for j, x in enumerate(v):
+                add(f"{name}_{j}", x)
+            return
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        wide = a.dtype == np.float64 or a.dtype.kind in "iu" and a.dtype.itemsize > 1
+        arrays[name] = a.astype(np.float64 if wide else np.float32)
+
+    for k, v in outputs.items():
+        add(k, v)
+    small = sum(a.nbytes for a in arrays.values() if a.size <= 65536)          # scalars, matrices, metrics: always whole
+    large = sum(a.nbytes for a in arrays.values()) - small
+    frac = min(1.0, (limit - small) / large) if large else 1.0
+    os.makedirs(path, exist_ok=True)
+    manifest = {}
+    for name, a in sorted(arrays.items()):
+        flat = a.reshape(-1)
+        k = flat.size if a.size <= 65536 else int(flat.size * frac)
+        sampled = k < flat.size
+        if sampled:
+            rs = np.random.RandomState(zlib.crc32(name.encode()))
+            flat = flat[np.sort(rs.choice(flat.size, k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), flat if sampled else a)
+        manifest[name] = [list(a.shape), sampled]
+    return manifest
 
 
 def corr_roofline(ops, B=8, N=4096, C=256, iters=10):
@@ -376,6 +423,7 @@ def worker(args):
             print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
     big = args.workload == "1024"
+    last = [None]          # (output dict, metric name, metric) of the most recent step: --dump-outputs writes the last timed one
     if big:
         # configs[3]: 1024x1024 pairs, 4 per GPU, each its own test_out call (batch 1: the canvas is per pair)
         pairs = [tuple(t.cuda() for t in structured_pair(1024, 1024, seed=900 + 8 * rank + i, shift=(11 - 3 * i, 5 * i - 9)))
@@ -393,7 +441,9 @@ def worker(args):
             g, h, st = pending.pop(0)
             with torch.cuda.stream(st):
                 o = g.finish(h) if g is not None else h
-                return o["blend_image"].float().mean().double().reshape(1)     # a per-pair scalar for the final gather
+                v = o["blend_image"].float().mean().double().reshape(1)     # a per-pair scalar for the final gather
+                last[0] = (o, "blend_image_mean", v)
+                return v
 
         def step(i=0, n_in_flight=None, drain=False):
             """software pipeline over the pairs in flight: enqueue pair i's network graph, then finish (bounds read-back +
@@ -421,7 +471,9 @@ def worker(args):
             k = i % (n_in_flight or nstreams)
             with torch.cuda.stream(streams[k]):
                 o = fwds[k](a, b)
-                return ops.masked_psnr_ssim(a, o["final_warp_output"])[0]      # evaluate.py:53-59 metric, HIP kernel, fp64 (psnr, ssim)
+                m = ops.masked_psnr_ssim(a, o["final_warp_output"])[0]      # evaluate.py:53-59 metric, HIP kernel, fp64 (psnr, ssim)
+                last[0] = (o, "psnr_ssim", m)
+                return m
 
     t_local_done, rank_times = [0.0], []
 
@@ -473,6 +525,12 @@ def worker(args):
         finish_one()
     log("timed region")
     dt = timed(args.steps)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs: a graph replay of the same slot would overwrite the static output buffers)
+        o, mname, m = last[0]
+        dumped = {"dir": os.path.abspath(args.dump_outputs), "arrays": dump_outputs(args.dump_outputs, dict(o, **{mname: m}))}
+        log(f"wrote the last timed step's outputs to {dumped['dir']}")
     per_rank_pairs_s = [args.steps * nb / t for t in rank_times]
     dt1 = None
     if nstreams > 1:
@@ -572,6 +630,7 @@ def worker(args):
                          "stale_profile_warning": None if (tsrc is None or tsrc.get("launches_per_step_in_file") in (None, launches)) else
                          f"the committed PMC pass saw {tsrc['launches_per_step_in_file']} launches per step, this run {launches}: `traffic` is from an older build"},
             "corr_volume": None if args.no_corr_roofline else corr_roofline(ops),
+            "dump_outputs": dumped,
         }
         if world == 1 and not args.no_cpu_baseline:
             log("cpu baseline + parity")
