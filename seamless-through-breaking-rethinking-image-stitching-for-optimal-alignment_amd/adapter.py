@@ -11,8 +11,6 @@ reference's other branches raise ``NotImplementedError`` here exactly where they
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn as nn
 
@@ -195,9 +193,6 @@ class FlowHomoAdpater(nn.Module):
         B, _, img_h, img_w = input1_tensor.shape
         if B != 1:
             raise NotImplementedError("test_out shares one data-dependent canvas: batch must be 1 (as in out.py:37)")
-        pre_out = None
-        if os.environ.get("ST_EXP_PREALLOC") == "1":           # experiment: the two flow outputs do not reuse blocks the networks freed
-            pre_out = (torch.empty((B, 2, img_h, img_w), device=dev), torch.empty((B, 2, img_h, img_w), device=dev))
         a512 = ops.resize_bilinear(input1_tensor, 512, 512, False)                                     # :204-205
         b512 = ops.resize_bilinear(input2_tensor, 512, 512, False)
         motion = self.predict_homo(a512, b512).contiguous()
@@ -210,14 +205,12 @@ class FlowHomoAdpater(nn.Module):
         warp2_512 = out_H[:, 0:3].contiguous()
         warp_mask_512 = ops.mean_threshold(out_H[:, 3:6].contiguous(), 0.5)                            # :233-234
         flow512, back512 = self.predict_flow_pair(a512, warp2_512)                                     # :236 and :326, one batch
-        residual = ops.resize_bilinear(flow512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)), out=pre_out[0] if pre_out else None)  # :241
-        back = ops.resize_bilinear(back512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)), out=pre_out[1] if pre_out else None)
+        residual = ops.resize_bilinear(flow512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))  # :241
+        back = ops.resize_bilinear(back512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))
         H = torch.empty((B, 3, 3), device=dev)
         ops.dlt4(self._corners(dev, float(img_w), float(img_h)), motion, H, B, img_w / 512.0, img_h / 512.0, 1.0)  # :244-253
         bounds = torch.empty((4,), device=dev)
         ops.mesh_bounds(H, bounds, img_w, img_h)                                                       # :254-266
-        if os.environ.get("ST_EXP_KEEP") == "1":                  # diagnostics (tools/graph_race_stress.py): the 512 x 512 flows as extra static outputs
-            return dict(residual=residual, back=back, H=H, bounds=bounds, warp2_512=warp2_512, warp_mask_512=warp_mask_512, flow512=flow512, back512=back512)
         return dict(residual=residual, back=back, H=H, bounds=bounds, warp2_512=warp2_512, warp_mask_512=warp_mask_512)
 
     def _test_out_canvas(self, input1_tensor, input2_tensor, nets):

@@ -1597,24 +1597,6 @@ extern "C" int st_mlp128_split3(const st_mlp_desc* desc, const void* image, int6
     int G = (nblk + MS3_NWAVES - 1) / MS3_NWAVES;
     if (G > 256) G = 256;                                       // 147 KB of LDS: one workgroup per CU
     const size_t lds = (size_t)3 * MS3_STAGE_B;
-    // timing experiment (tools/mlp_split3_probe.py --diag): ST_MLP3_DIAG=1 runs the instrumented instance, waits for it and prints per-phase cycle sums of wave 0
-    static const int diag = [] { const char* e = getenv("ST_MLP3_DIAG"); return e ? atoi(e) : 0; }();
-    if (diag) {
-        static unsigned long long* dbuf = nullptr;
-        if (!dbuf && hipHostMalloc((void**)&dbuf, 256 * 8 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return ST_EINVAL;      // pinned: the kernel writes it, the host reads it after the sync
-        auto kd = d.wp ? rowmlp128_split3_kernel<true, true> : rowmlp128_split3_kernel<false, true>;
-        (void)hipFuncSetAttribute((const void*)kd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kd, dim3(G), dim3(64 * MS3_NWAVES), lds, (hipStream_t)stream, d, (const unsigned char*)image, (unsigned)need, dbuf);
-        ST_CHECK_LAUNCH();
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return ST_EINVAL;
-        const unsigned long long* h = dbuf;
-        double s8[8] = {0}, sum = 0;
-        for (int b = 0; b < G; ++b) for (int i = 0; i < 8; ++i) s8[i] += (double)h[8 * b + i] / G;
-        for (int i = 0; i < 8; ++i) sum += s8[i];
-        fprintf(stderr, "mlp_split3 diag (mean s_memtime cycles of wave 0 over %d workgroups): syncs %.0f  load+split %.0f  projection %.0f  LN+split %.0f  first fc1 %.0f  phase1 %.0f  phase2 %.0f  last+epilogue %.0f  sum %.0f\n",
-                G, s8[0], s8[1], s8[2], s8[3], s8[4], s8[5], s8[6], s8[7], sum);
-        return ST_OK;
-    }
     auto kern = d.wp ? rowmlp128_split3_kernel<true> : rowmlp128_split3_kernel<false>;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     st_gemm_observer_fn obs = g_observer;
@@ -1627,7 +1609,7 @@ extern "C" int st_mlp128_split3(const st_mlp_desc* desc, const void* image, int6
         obs(&od, stream, 0, g_observer_user);
     }
     g_last_plan[0] = 9; g_last_plan[1] = 38; g_last_plan[2] = 1; g_last_plan[3] = 1;
-    hipLaunchKernelGGL(kern, dim3(G), dim3(64 * MS3_NWAVES), lds, (hipStream_t)stream, d, (const unsigned char*)image, (unsigned)need, (unsigned long long*)nullptr);
+    hipLaunchKernelGGL(kern, dim3(G), dim3(64 * MS3_NWAVES), lds, (hipStream_t)stream, d, (const unsigned char*)image, (unsigned)need);
     if (obs) obs(&od, stream, 1, g_observer_user);
     ST_CHECK_LAUNCH();
     return ST_OK;
@@ -1919,15 +1901,10 @@ static int launch_dma(const st_gemm_desc& d, hipStream_t s) {
     // otherwise be many short workgroups (two resident per CU with this LDS footprint)
     const bool plain = d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0 && d.H * d.W == d.M &&
                        d.Ho * d.Wo == d.M;
-    // Round-5 experiment, measured and NOT adopted (both switches default to the round-4 behaviour): ST_PERSIST_SLOTS=256 gives a launch ONE
-    // workgroup slot per CU (a CU holds two of this LDS footprint; a workgroup then walks >= 2 M tiles with one continuous DMA ring) so that the
-    // second slot is left to the kernel of another stream (ST_PERSIST_CONV=1 also let convolutions walk that way; removed in round 6).  On uniform GEMMs the idea pays (tools/persist_probe.py, 5 decoder shapes, one hipGraph
-    // per stream: 3 streams 120.9 -> 127.8 TFLOP/s, 2 streams 119.2 -> 124.1, 1 stream 104.2 -> 102.4); in the product it does not (bench.py,
-    // 3 pairs in flight, same box, A/B/A: slots 512 conv 0: 82.66 / 82.58 pairs/s; 256 / 1: 81.09 / 80.67; 256 / 0: 82.60; 512 / 1: 82.22;
-    // one pair in flight 72.4 -> 69.0): between the GEMMs of a forward run ~150 short kernels of other kinds, and a GEMM that holds one slot
-    // runs at one wave per SIMD whenever the neighbouring stream is not in a GEMM itself.
-    static const int slots_env = [] { const char* e = getenv("ST_PERSIST_SLOTS"); return e ? atoi(e) : 512; }();
-    const int slots = slots_env / batch;
+    // 512 workgroup slots = both of a CU's slots for this LDS footprint.  One slot per CU (a workgroup walking >= 2 M tiles, the second slot
+    // left to another stream's kernel) was measured in round 5 and not adopted: faster on uniform GEMMs alone, slower in the product (bench.py,
+    // 3 pairs in flight, same box A/B/A: 82.66 / 82.58 -> 81.09 / 80.67 pairs/s; one pair in flight 72.4 -> 69.0).
+    const int slots = 512 / batch;
     if (STAGES == 4 && plain && !d.a2 && d.split_k <= 1 && (d.K / 32) % STAGES == 0 && (long)ntm * ntn > slots && ntn <= slots && slots > 0) {
         int G = slots / ntn;
         if (G > ntm) G = ntm;
@@ -2171,14 +2148,14 @@ static int conv_gemm_launch(const st_gemm_desc* desc, void* stream) {
 }
 
 // ---- split3 (csrc/gemm_split3.h): a / w are three blocked bf16 planes -------------------------------------------------------
-template <int WM, int WN, int TM, int TN, int STAGES, int DIAG = 0>
+template <int WM, int WN, int TM, int TN, int STAGES>
 static int launch_split3(const st_gemm_desc& d, hipStream_t s) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
     const int batch = d.batch > 0 ? d.batch : 1;
     const size_t lds = (size_t)STAGES * 3 * (BM + BN) * 64;
-    void (*k)(const st_gemm_desc) = conv_gemm_split3_kernel<WM, WN, TM, TN, STAGES, DIAG>;
-    if constexpr (TM * TN == 1 && WM == 2 && WN == 2 && STAGES == 3) k = conv_gemm_split3_kernel64<STAGES, DIAG>;
+    void (*k)(const st_gemm_desc) = conv_gemm_split3_kernel<WM, WN, TM, TN, STAGES>;
+    if constexpr (TM * TN == 1 && WM == 2 && WN == 2 && STAGES == 3) k = conv_gemm_split3_kernel64<STAGES>;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k, dim3(ntm * ntn, 1, d.split_k > 1 ? d.split_k : batch), dim3(512), lds, s, d);
     if (d.split_k > 1)
@@ -2252,21 +2229,14 @@ static int conv_gemm_split3_launch(const st_gemm_desc* desc, void* stream) {
     if (cfg == 0) cfg = (long)((d.M + 127) / 128) * ((d.N + 63) / 64) * batch >= 256 ? 32 : 34;
     // many short tiles (>= 4 per workgroup slot, K <= 2 048): the persistent 64x64 walk (tile_cfg 37) -- the all-pairs volume, PatchEmbed's third conv
     const long ntl64 = (long)((d.M + 63) / 64) * ((d.N + 63) / 64);
-    static const int persist_env = [] { const char* e = getenv("ST_SPLIT3_PERSIST"); return e ? atoi(e) : 1; }();      // ST_SPLIT3_PERSIST=0: A/B switch
-    if (persist_env && d.tile_cfg == 0 && !d.a2 && d.split_k <= 1 && d.K <= 2048 && ntl64 * batch >= 2048) cfg = 37;
+    if (d.tile_cfg == 0 && !d.a2 && d.split_k <= 1 && d.K <= 2048 && ntl64 * batch >= 2048) cfg = 37;
     if (d.c_t) cfg = 37;
-    static const int tile_env = [] { const char* e = getenv("ST_SPLIT3_TILE"); return e ? atoi(e) : 0; }();      // experiments: force one tile configuration
-    if (tile_env && d.tile_cfg == 0 && !d.c_t) cfg = tile_env;
     // two consumer groups per workgroup (csrc/gemm_split3.h KPAR; tile_cfg 39: 64x64 tiles, 38: 128x64) for a launch of exactly one 64x64 tile per CU and
     // a long K -- the N = 128 shapes at M = 8 192 (SepConvGRU's q convolutions, the motion encoder's 126-channel conv).  Measured (tools/split3_probe.py,
     // 8192 x 128 x 1920): 23.9 us against 29.1 for the four-consumer tile and 33.9 + a 7.4 us reducer launch for the split-K-2 form it replaces.  The
-    // 128x64 form (bit 1 of ST_SPLIT3_KPAR) is SLOWER than its four-consumer twin on the N = 256 shapes (47.7 against 42.7 us): three waves per SIMD and
-    // twelve waves per barrier cost more than the second MFMA issuer returns there.  ST_SPLIT3_KPAR=0: off.
-    static const int kpar_env = [] { const char* e = getenv("ST_SPLIT3_KPAR"); return e ? atoi(e) : 2; }();
-    if (kpar_env && d.tile_cfg == 0 && !tile_env && batch == 1 && d.split_k <= 1 && d.K >= 1024) {
-        if ((kpar_env & 1) && cfg == 32 && (long)((d.M + 127) / 128) * ((d.N + 63) / 64) <= 512) cfg = 38;
-        else if ((kpar_env & 2) && cfg == 34 && ntl64 == 256) cfg = 39;
-    }
+    // 128x64 form (tile_cfg 38, never chosen here) is SLOWER than its four-consumer twin on the N = 256 shapes (47.7 against 42.7 us): three waves per
+    // SIMD and twelve waves per barrier cost more than the second MFMA issuer returns there.
+    if (d.tile_cfg == 0 && cfg == 34 && ntl64 == 256 && batch == 1 && d.split_k <= 1 && d.K >= 1024) cfg = 39;
     static const int bms[10] = {0, 128, 128, 64, 64, 128, 64, 64, 128, 64}, bns[10] = {0, 128, 64, 128, 64, 64, 64, 64, 64, 64};
     if (cfg < 31 || cfg > 39) return ST_EINVAL;
     if (cfg >= 38 && (d.split_k > 1 || batch != 1)) return ST_EINVAL;
@@ -2278,8 +2248,8 @@ static int conv_gemm_split3_launch(const st_gemm_desc* desc, void* stream) {
         split = 1;
         if (batch == 1 && d.workspace && d.K >= 512 && tiles < 256) split = (int)((256 + tiles - 1) / tiles);
         // exactly one workgroup per CU (N = 128 at M = 8 192) leaves every SIMD with ONE consumer wave -- two K halves give it two
-        static const int sk2 = [] { const char* e = getenv("ST_SPLIT3_SK2"); return e ? atoi(e) : 1; }();      // measured: decoder chain 5.36 -> 5.23 ms (tools/decoder_bench.py); ST_SPLIT3_SK2=0 = off
-        if (sk2 && batch == 1 && d.workspace && d.K >= 1024 && tiles == 256 && cfg == 34) split = 2;
+        // (measured: decoder chain 5.36 -> 5.23 ms, tools/decoder_bench.py)
+        if (batch == 1 && d.workspace && d.K >= 1024 && tiles == 256 && cfg == 34) split = 2;
         if (split > d.K / 256) split = d.K / 256;
         if (split > 16) split = 16;
         if (split < 1) split = 1;
@@ -2293,12 +2263,6 @@ static int conv_gemm_split3_launch(const st_gemm_desc* desc, void* stream) {
     d.split_k = split;
     g_last_plan[0] = 8; g_last_plan[1] = cfg; g_last_plan[2] = split; g_last_plan[3] = 0;
     hipStream_t s = (hipStream_t)stream;
-    // timing experiments (tools/split3_probe.py --diag): ST_SPLIT3_DIAG=1 consumers skip the MFMAs, 2 loaders skip the DMA; results are garbage
-    static const int diag = [] { const char* e = getenv("ST_SPLIT3_DIAG"); return e ? atoi(e) : 0; }();
-    if (diag == 1) return cfg == 34 ? launch_split3<2, 2, 1, 1, 3, 1>(d, s) : cfg == 32 ? launch_split3<2, 2, 2, 1, 4, 1>(d, s) : launch_split3<2, 2, 2, 2, 3, 1>(d, s);
-    if (diag == 3) return launch_split3<2, 2, 1, 1, 3, 3>(d, s);
-    if (diag == 4) return launch_split3<2, 2, 1, 1, 3, 4>(d, s);      // in-kernel clock stamps -> workspace (tools/split3_clock.py)
-    if (diag == 2) return cfg == 34 ? launch_split3<2, 2, 1, 1, 3, 2>(d, s) : cfg == 32 ? launch_split3<2, 2, 2, 1, 4, 2>(d, s) : launch_split3<2, 2, 2, 2, 3, 2>(d, s);
     if (cfg == 37) {
         int G = 512 / batch;
         if (G < 1) G = 1;

@@ -49,13 +49,12 @@ __global__ __launch_bounds__(256) void split3_pack_kernel(const float* __restric
     *reinterpret_cast<bf16x8*>(planes + 2 * plane_stride + o) = l;
 }
 
-// DIAG (timing experiments only, results are garbage): 1 = consumers skip the MFMAs (ingest alone), 2 = loaders skip the DMA (reads + MFMAs alone)
 // KPAR = 2: EIGHT consumer waves (768-thread workgroups, three waves per SIMD): waves 0-3 take the first 16-k half of every 32-k step, waves 4-7 the
 // second half, on the same 32 x 32 (x TM x TN) sub-tiles; the second group's accumulators cross LDS once, behind the K loop, and the first group
 // runs the epilogue.  A single consumer wave per SIMD issues one v_mfma_f32_32x32x16_bf16 per 32 cycles at best (tools/probes/mfma_bf16_chain.hip)
 // and, with 128 x 64 tiles at one workgroup per CU, that is what bounds the loop (MFMA-only 35 us against DMA-only 29 us on the 1x5 conv); the
 // decoder's M = 8 192 shapes have no second tile to give the CU, so the K dimension is what two waves of a SIMD can share.
-template <int WM, int WN, int TM, int TN, int STAGES, int DIAG = 0, int KPAR = 1>
+template <int WM, int WN, int TM, int TN, int STAGES, int KPAR = 1>
 __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, const int block_id) {
     static_assert(WM * WN == 4, "4 consumer waves per K half (+ 4 loader waves)");
     static_assert(KPAR == 1 || KPAR == 2, "one or two consumer groups");
@@ -89,8 +88,6 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
     const int kt0 = kz * per;
     const int ntiles = min(nkt_all, kt0 + per) - kt0;       // K steps of this workgroup (> 0: the host never over-splits)
 
-    unsigned long long sr_entry = 0;
-    if (DIAG == 4) sr_entry = __builtin_amdgcn_s_memrealtime();
     if (wave >= 4 * KPAR) {
         // ------------------------------------------------------------------ loader waves
         const int lw = wave - 4 * KPAR;
@@ -147,9 +144,9 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
             const unsigned so = (unsigned)(stage * STAGE_B);
             const bool second = i_c0 < a2c;
 #pragma unroll
-            for (int i = 0; i < PA; ++i) if (DIAG != 2 && DIAG != 3) lds_dma16(second ? rsrcA2 : rsrcA, ldsA[i] + so, voffA[i], soffA);
+            for (int i = 0; i < PA; ++i) lds_dma16(second ? rsrcA2 : rsrcA, ldsA[i] + so, voffA[i], soffA);
 #pragma unroll
-            for (int i = 0; i < PB; ++i) if (DIAG != 2 && DIAG != 3) lds_dma16(rsrcW, ldsB[i] + so, voffB[i], soffB);
+            for (int i = 0; i < PB; ++i) lds_dma16(rsrcW, ldsB[i] + so, voffB[i], soffB);
             soffB += w_chunk_b; soffA += a_chunk_b;
             i_c0 += 32;
             if (i_c0 >= d.Cin) {
@@ -166,11 +163,11 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
         };
         for (int t = 0; t < STAGES && t < ntiles; ++t) issue_tile(t);
         wait_tiles(min(STAGES - 1, ntiles - 1));    // tile 0 has landed (this wave's pieces) ...
-        if (DIAG != 3) asm volatile("s_barrier" ::: "memory");     // ... and everybody else's
+        asm volatile("s_barrier" ::: "memory");     // ... and everybody else's
         int stage = 0;
         for (int t = 0; t + 1 < ntiles; ++t) {
             wait_tiles(min(STAGES - 2, ntiles - 2 - t));   // tile t+1 landed; tiles t+2 .. t+STAGES-1 may still fly
-            if (DIAG != 3) asm volatile("s_barrier" ::: "memory"); // consumers have every fragment of tile t in registers: its stage is free
+            asm volatile("s_barrier" ::: "memory"); // consumers have every fragment of tile t in registers: its stage is free
             if (t + STAGES < ntiles) issue_tile(stage);
             stage = stage == STAGES - 1 ? 0 : stage + 1;
         }
@@ -308,11 +305,11 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
     }
     // (Measured and dropped, round 6, 1x5 conv 8192 x 256 x 1920 on 64x64 tiles: a third fragment buffer so that both 16-k steps of the next
     // tile are requested right behind the barrier -- 44.5 us either way; two alternating accumulators per sub-tile -- 33.1 vs 33.6 us MFMA-only;
-    // no barriers at all, MFMA-only -- 33.6 us: the consumer side is MFMA-bound at ~90 % while its workgroup runs, tools/split3_clock.py.)
+    // no barriers at all, MFMA-only -- 33.6 us: the consumer side is MFMA-bound at ~90 % while its workgroup runs, profiles/r6_split3_clock.txt.)
     bf16x8 fa[2][3][TM], fb[2][3][TN];
     // One product = TM x TN MFMAs on one (A plane, B plane) pair.  The fragment reads of the NEXT 16-k step ride in the gaps between the
     // MFMAs of the first three products, one or two ds_read_b128 per gap (a burst of 12 reads between two MFMAs drains the matrix pipe:
-    // MFMA-only runs of the first version, tools/split3_probe.py ST_SPLIT3_DIAG=2, took 34 us where the MFMAs need 21), in the order the
+    // MFMA-only runs of the first version, loaders skipping the DMA, took 34 us where the MFMAs need 21), in the order the
     // next step's products need them: set 0 = (A lo, B hi), set 1 = (A hi, B lo), set 2 = (A mid, B mid).  Each set is thus requested one
     // whole 16-k step (6 TM TN MFMAs) before its first use.
     auto prod = [&](int buf, int p, int q, int nbuf, int nstage, int nj, int set) {
@@ -323,8 +320,7 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int jn = 0; jn < TN; ++jn) {
-                if (DIAG == 1) asm volatile("" ::"v"(fa[buf][p][i]), "v"(fb[buf][q][jn]));       // keep the fragment reads alive
-                else acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[buf][p][i], fb[buf][q][jn], acc[i][jn], 0, 0, 0);
+                acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[buf][p][i], fb[buf][q][jn], acc[i][jn], 0, 0, 0);
                 if (set >= 0) {
                     const int upto = ((i * TN + jn + 1) * NR + NM - 1) / NM;           // reads due after this MFMA
 #pragma unroll
@@ -357,7 +353,7 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
         __builtin_amdgcn_sched_barrier(0);
     }
 
-    if (DIAG != 3) asm volatile("s_barrier" ::: "memory");         // tile 0 is in LDS
+    asm volatile("s_barrier" ::: "memory");         // tile 0 is in LDS
     read_set(0, 0, 0, 0); read_set(0, 0, 0, 1); read_set(0, 0, 0, 2);
     __builtin_amdgcn_sched_barrier(0);
     // MORE (a literal in the steady state): tile t+1 exists.  Kept out of a run-time branch there: behind a branch that only sometimes
@@ -371,7 +367,7 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
         // 16-k step 1 (buffer 1)
         if (MORE || more_rt) {
             // every read of stage s has returned (lgkmcnt(0)); tile t+1 has landed everywhere; the loaders may now refill stage s
-            if (DIAG != 3) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             prod(1, 2, 0, 0, (s + 1) % STAGES, 0, 0); prod(1, 0, 2, 0, (s + 1) % STAGES, 0, 1); prod(1, 1, 1, 0, (s + 1) % STAGES, 0, 2);
         } else {
             prod(1, 2, 0, 0, 0, 0, -1); prod(1, 0, 2, 0, 0, 0, -1); prod(1, 1, 1, 0, 0, 0, -1);
@@ -389,8 +385,6 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    unsigned long long st0 = 0, sr0 = 0;
-    if (DIAG == 4) { st0 = __builtin_amdgcn_s_memtime(); sr0 = __builtin_amdgcn_s_memrealtime(); }
     int tb = 0;
     for (; tb + STAGES < ntiles; tb += STAGES) {     // every tile of the turn has a successor
 #pragma unroll
@@ -399,11 +393,6 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
 #pragma unroll
     for (int s = 0; s < STAGES; ++s)
         if (tb + s < ntiles) tile_body(st_false{}, s, tb + s, tb + s + 1 < ntiles);
-    if (DIAG == 4 && wave == 0 && lane == 0 && d.workspace) {      // in-kernel clock of the K loop: shader cycles per 100 MHz tick (diagnostic build only)
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(d.workspace) + (size_t)(blockIdx.x + gridDim.x * blockIdx.z) * 8;
-        const unsigned long long sr1 = __builtin_amdgcn_s_memrealtime();
-        o[0] = __builtin_amdgcn_s_memtime() - st0; o[1] = sr1 - sr0; o[2] = sr_entry; o[3] = sr0; o[4] = sr1;
-    }
     if (ntiles > KBLK) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -412,10 +401,6 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
     }
     if (EPI_AHEAD) gemm_epilogue_store<TM, TN, false, false>(d, C, acc, eop, m0, n0, wm, wn, li, lh, split, kz);
     else gemm_tile_epilogue<TM, TN>(d, C, acc, m0, n0, wm, wn, li, lh, split, kz);
-    if (DIAG == 4 && wave == 0 && lane == 0 && d.workspace) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        reinterpret_cast<unsigned long long*>(d.workspace)[(size_t)(blockIdx.x + gridDim.x * blockIdx.z) * 8 + 5] = __builtin_amdgcn_s_memrealtime();
-    }
 }
 
 // PERSISTENT walk (64x64 tiles, 3-stage ring): a workgroup walks output tiles w, w + G, w + 2G, ... of its batch with ONE continuous DMA ring,
@@ -604,24 +589,24 @@ __global__ __launch_bounds__(512, 4) void conv_gemm_split3_persist_kernel(const 
     conv_gemm_split3_persist_body<CT>(d);
 }
 
-template <int WM, int WN, int TM, int TN, int STAGES, int DIAG = 0>
+template <int WM, int WN, int TM, int TN, int STAGES>
 __global__ __launch_bounds__(512) void conv_gemm_split3_kernel(const st_gemm_desc d) {
-    conv_gemm_split3_body<WM, WN, TM, TN, STAGES, DIAG>(d, (int)blockIdx.x);
+    conv_gemm_split3_body<WM, WN, TM, TN, STAGES>(d, (int)blockIdx.x);
 }
 // the 64x64 configuration lives on TWO workgroups per CU (72 KB of LDS each): 4 waves per SIMD, so at most 128 registers per wave
 template <int WM, int WN, int TM, int TN, int STAGES>
 __global__ __launch_bounds__(768, 1) void conv_gemm_split3_kpar_kernel(const st_gemm_desc d) {
-    conv_gemm_split3_body<WM, WN, TM, TN, STAGES, 0, 2>(d, (int)blockIdx.x);
+    conv_gemm_split3_body<WM, WN, TM, TN, STAGES, 2>(d, (int)blockIdx.x);
 }
 
-template <int STAGES, int DIAG = 0>
+template <int STAGES>
 __global__ __launch_bounds__(512, 4) void conv_gemm_split3_kernel64(const st_gemm_desc d) {
-    conv_gemm_split3_body<2, 2, 1, 1, STAGES, DIAG>(d, (int)blockIdx.x);
+    conv_gemm_split3_body<2, 2, 1, 1, STAGES>(d, (int)blockIdx.x);
 }
 
 // two independent split3 contractions in one launch (st_conv_gemm_pair with split3 descriptors): workgroups [0, tiles0) run d[0], the rest d[1]
 template <int WM, int WN, int TM, int TN, int STAGES>
 __global__ __launch_bounds__(512, 4) void conv_gemm_split3_pair_kernel(const st_gemm_pair_args g) {
     const bool second = (int)blockIdx.x >= g.tiles0;             // workgroup-uniform
-    conv_gemm_split3_body<WM, WN, TM, TN, STAGES, 0>(second ? g.d[1] : g.d[0], second ? (int)blockIdx.x - g.tiles0 : (int)blockIdx.x);
+    conv_gemm_split3_body<WM, WN, TM, TN, STAGES>(second ? g.d[1] : g.d[0], second ? (int)blockIdx.x - g.tiles0 : (int)blockIdx.x);
 }

@@ -16,7 +16,7 @@
 //     hidden walk is SOFTWARE-PIPELINED inside the wave: while chunk c's 16 hidden values per lane go through bias + GELU + split on
 //     the VALU, the matrix pipe runs chunk c + 1's fc1 product (48 MFMAs); then chunk c's fc2 products (48 MFMAs) run with the
 //     fragment reads of the next group between them.  One barrier per step, the DMA of step q + 2 issued right behind it.
-//   * what bounds it (tools/probes/mfma_bf16_chain.hip, in-kernel stamps ST_MLP3_DIAG=1, profiles/r6_mlp_split3_*): a wave issues one
+//   * what bounds it (tools/probes/mfma_bf16_chain.hip, in-kernel s_memtime stamps, profiles/r6_mlp_split3_*): a wave issues one
 //     v_mfma_f32_32x32x16_bf16 per 32 cycles whatever it accumulates into, and each one keeps the SIMD's VALU issue busy for ~23 of
 //     them -- also for the OTHER wave of the SIMD: an eight-wave variant (two per SIMD, the two halves of the workgroup half a step
 //     apart so that one's GELU phase meets the other's MFMA phase) measured 4 500 cycles per block and chunk against 4 700 here, with
@@ -116,14 +116,8 @@ __device__ __forceinline__ float ms3_gelu(float x) {
     return fmaf(-fabsf(x), y, fmaxf(x, 0.f));
 }
 
-// DIAG: s_memtime sums per phase of wave 0 -> diag[8 * blockIdx.x ..]: 0 syncs (wait + barrier), 1 row load + split, 2 projection steps,
-// 3 LayerNorm + split, 4 first fc1 product, 5 phase 1, 6 phase 2, 7 last chunk + epilogue (ST_MLP3_DIAG=1, tools/mlp_split3_diag.py)
-template <bool PROJ, bool DIAG = false>
-__global__ __launch_bounds__(256, 1) void rowmlp128_split3_kernel(const st_mlp_desc d, const unsigned char* __restrict__ image, const unsigned image_bytes,
-                                                                  unsigned long long* __restrict__ diag) {
-    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tmark = 0;
-#define MS3_T0() if (DIAG) tmark = __builtin_amdgcn_s_memtime();
-#define MS3_T1(i) if (DIAG) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tsum[i] += t_ - tmark; tmark = t_; }
+template <bool PROJ>
+__global__ __launch_bounds__(256, 1) void rowmlp128_split3_kernel(const st_mlp_desc d, const unsigned char* __restrict__ image, const unsigned image_bytes) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char sm3[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
@@ -180,11 +174,9 @@ __global__ __launch_bounds__(256, 1) void rowmlp128_split3_kernel(const st_mlp_d
     if (total > 1) dma_step();
     // sync of step q: the pieces of steps <= q + 1 have landed in every wave's view, everyone is past step q - 1, whose stage takes step q + 2
     auto step_sync = [&]() {
-        MS3_T0()
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (q_dma < total) dma_step();
-        MS3_T1(0)
     };
 
     // fragment offsets: W1 part, row li (256 B), 16-B slot (2 ks + lh) ^ (li & 15); W2 part, row 32 t + li (64 B), slot (2 ks + lh) ^ ((li >> 2) & 3)
@@ -269,7 +261,6 @@ __global__ __launch_bounds__(256, 1) void rowmlp128_split3_kernel(const st_mlp_d
         float4 xf[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) xf[j] = *reinterpret_cast<const float4*>(d.a + rowc * d.lda + 8 * j + 4 * lh);
-        MS3_T0()
         if (PROJ) {
             // x = a . wp^T + bp + res0, 32 features per step; x stays in registers (xf), a's planes make way for x's; the residual rows are requested up front
             float4 ev[16];
@@ -281,7 +272,6 @@ __global__ __launch_bounds__(256, 1) void rowmlp128_split3_kernel(const st_mlp_d
                 for (int j = 0; j < 16; ++j) ev[j] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
             split_rows(xf);
-            MS3_T1(1)
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 step_sync();
@@ -296,7 +286,6 @@ __global__ __launch_bounds__(256, 1) void rowmlp128_split3_kernel(const st_mlp_d
                     xf[4 * c + jj] = make_float4((acc[4 * jj] + bv.x) + e.x, (acc[4 * jj + 1] + bv.y) + e.y, (acc[4 * jj + 2] + bv.z) + e.z, (acc[4 * jj + 3] + bv.w) + e.w);
                 }
                 g = next_stage(g);
-                MS3_T1(2)
             }
         }
         {
@@ -322,7 +311,6 @@ __global__ __launch_bounds__(256, 1) void rowmlp128_split3_kernel(const st_mlp_d
             }
             split_rows(xn);
         }
-        MS3_T1(3)
         __builtin_amdgcn_sched_barrier(0);
         f32x16 o[4];
 #pragma unroll
@@ -333,7 +321,6 @@ __global__ __launch_bounds__(256, 1) void rowmlp128_split3_kernel(const st_mlp_d
         step_sync();
         f32x16 acc;
         MS3_CHUNK128(acc, g, false)
-        MS3_T1(4)
         u32x4 hp[3][2];                                         // a chunk's hidden values as planes: two 16-k MFMA steps of fc2
 #pragma unroll 1
         for (int hc = 0; hc + 1 < nhc; ++hc) {
@@ -363,9 +350,7 @@ __global__ __launch_bounds__(256, 1) void rowmlp128_split3_kernel(const st_mlp_d
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            MS3_T1(5)
             MS3_PHASE2(wc)
-            MS3_T1(6)
             acc = an;
             g = gn;
         }
@@ -408,10 +393,7 @@ __global__ __launch_bounds__(256, 1) void rowmlp128_split3_kernel(const st_mlp_d
                 }
             }
         }
-        MS3_T1(7)
     }
-    if (DIAG && tid == 0)
-        for (int i = 0; i < 8; ++i) diag[8 * blockIdx.x + i] = tsum[i];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -810,8 +792,6 @@ __global__ __launch_bounds__(256, 1) void pe_tail_split3_kernel(const float* __r
 #undef PT3_BF
 }
 
-#undef MS3_T0
-#undef MS3_T1
 #undef MS3_PHASE2
 #undef MS3_GELU_PAIR
 #undef MS3_CHUNK128

@@ -27,42 +27,22 @@ from .checkpoint import HP, ParamTree, flat_params, flow_spec
 from .homography import pack_conv
 
 
-# LayerNorm in front of a K = 128 Linear runs inside the row-streaming GEMM (ops.conv_gemm(ln_eps=...)): gamma / beta are
-# folded into the weights at pack time.  ST_FUSE_LN=0 keeps the separate LayerNorm kernel (A/B measurements).
-FUSE_LN = os.environ.get("ST_FUSE_LN", "1") != "0"
-PAIR_CONVS = os.environ.get("ST_PAIR_CONVS", "1") != "0"       # convc2 + convf2 of the motion encoder as one launch
-FUSE_MLP = os.environ.get("ST_FUSE_MLP", "1") != "0"            # the C = 128 Twins MLPs (LN -> fc1 + GELU -> fc2 + residual) as one st_mlp128 launch
-FUSE_PROJ = os.environ.get("ST_FUSE_PROJ", "1") != "0"          # ... with the Block's attention output projection + residual in front, same launch
-FUSE_CHAIN = os.environ.get("ST_FUSE_CHAIN", "1") != "0"        # the latent layers' 128-wide tails as one st_linear_chain128 launch
-# ST_FORK=1: the context branch of a pass (cnet Twins, then everything of the decoder that only needs the context: proj_net / proj_inp, the
-# SepConvGRU tables, the GMA attention matrix) on a second HIP stream beside the feature branch (fnet Twins, correlation volume, PatchEmbed,
-# latent layers); joined by an event before the first vertical layer (context) and by a stream join before the refinement loop.  Captured
-# into the forward's hipGraph as a parallel branch.  Same kernels, same operands: bit-identical.  Measured in round 5 (section 5 of DESIGN.md).
-FORK = os.environ.get("ST_FORK", "0") == "1"
-FORK_ENC = os.environ.get("ST_FORK_ENC", "0") == "1"           # experiment: flow_encode of an iteration on a side stream beside cost lookup + token chain (which fill half the CUs)
-# The decoder's long-K contractions (SepConvGRU, motion-encoder 3x3 convs, GMA aggregate, flow / mask head conv1: ~5.3 of the 12 ms of a pair)
-# on the bf16 matrix cores with EXACTLY split operands (csrc/gemm_split3.h: x = hi + mid + lo in three bf16, six products, fp32 accumulate --
-# error against fp64 0.83x the fp32 MFMA chain's, 1.5-1.76x its speed, profiles/r6_split3_probe.json).  Every operand travels as blocked
-# bf16 planes written by the epilogue of the kernel that produced it; ST_SPLIT3=0 = the fp32-MFMA kernels of rounds 1-5 (A/B).
+# One configuration ships; every fused path below won its same-box A/B (DESIGN.md sections 5 and 7) and the separate-launch paths it
+# replaced are gone.  Whatever a shape or weight condition rules out (Twins stage 2 with C = 256, cost maps that are not 64 x 64, N % 32 != 0)
+# keeps the general kernels.
+#   * LayerNorm in front of a K = 128 Linear runs inside the row-streaming GEMM (ops.conv_gemm(ln_eps=...)): gamma / beta are folded into
+#     the weights at pack time;
+#   * the C = 128 Twins MLPs (LN -> fc1 + GELU -> fc2 + residual), with the Block's attention output projection + residual in front, are
+#     one st_mlp128 launch; the latent layers' 128-wide tails are the same operator with hidden = 128;
+#   * convc2 + convf2 of the motion encoder are one launch (two workgroups per CU, no split-K slabs);
+#   * PatchEmbed c0 + c2 of a 64 x 64 cost map are one launch that keeps the first feature map on the CU (csrc/patchembed.hip).
+# The decoder's long-K contractions (SepConvGRU, motion-encoder 3x3 convs, GMA aggregate, flow / mask head conv1: ~5.3 of the 12 ms of a
+# pair) except the HBM-bound aggregate, PatchEmbed's third convolution and ffn_with_coord + LayerNorm, the q | k | v projections and the
+# block tails run on the bf16 matrix cores with EXACTLY split operands (csrc/gemm_split3.h, csrc/mlp_split3.h: x = hi + mid + lo in three
+# bf16, six products, fp32 accumulate -- error against fp64 0.83x the fp32 MFMA chain's, 1.5-1.76x its speed, profiles/r6_split3_probe.json).
+# Every operand travels as blocked bf16 planes written by the epilogue of the kernel that produced it.  ST_SPLIT3=0 = the fp32-MFMA kernels of rounds 1-5: the all-fp32 reference
+# that bench.py reports as value_exact_fp32.
 SPLIT3 = os.environ.get("ST_SPLIT3", "1") != "0"
-FUSE_PE = os.environ.get("ST_FUSE_PE", "1") != "0"              # PatchEmbed c0 + c2 per cost map in one launch (csrc/patchembed.hip; the library reads the same switch)
-assert not (SPLIT3 and FORK_ENC), "ST_FORK_ENC is an fp32-path experiment"
-S3_PAIR = os.environ.get("ST_S3_PAIR", "1") != "0"
-S3_PE = os.environ.get("ST_S3_PE", "1") != "0"                 # PatchEmbed's third convolution on planes
-S3_MLP = os.environ.get("ST_S3_MLP", "1") != "0"               # the C = 128 block tails (st_mlp128) on the split3 kernel (st_mlp128_split3, weights packed into its image once)
-S3_PE_TAIL = os.environ.get("ST_S3_PE_TAIL", "1") != "0"       # PatchEmbed's ffn_with_coord + LayerNorm (three HBM-bound launches over M P rows) as one split3 launch
-S3_LIN = os.environ.get("ST_S3_LIN", "1") != "0"               # LayerNorm -> q | k | v projection (K = 128, N = 384) on the split3 row kernel (st_rowlin128_split3)
-S3_CHAIN = os.environ.get("ST_S3_CHAIN", "1") != "0"           # the latent layers' 128-wide tails (st_linear_chain128) on the same split3 kernel, hidden = 128
-S3_AGG = os.environ.get("ST_S3_AGG", "0") == "1"               # GMA aggregate on planes (measured equal to the fp32 kernel in the chain: HBM-bound; default off)
-S3_OFF = int(os.environ.get("ST_S3_OFF", "0"))     # bisecting aid: bit 1 mask-head conv, 2 flow-head conv, 8 GRU, 16 motion conv, 32 conv pair back on the fp32 kernels
-_SIDE = {}
-
-
-def _side_stream(cur):
-    key = (cur.device_index, cur.cuda_stream)
-    if key not in _SIDE:
-        _SIDE[key] = torch.cuda.Stream(device=cur.device)
-    return _SIDE[key]
 
 
 def _new(rows, cols, dev, zero=False):
@@ -104,16 +84,16 @@ class FlowFormer(ParamTree):
             return pack_conv(p[name + ".weight"], cin_pad), (b.contiguous() if b is not None else None)
 
         def mlp_image(fc1_ln, fc2, proj):
-            """the split3 image of a block tail (projection + LayerNorm-folded fc1 + fc2), or None: CPU weights (tests of the pack layouts), switch off"""
-            if not (SPLIT3 and S3_MLP and FUSE_LN and FUSE_MLP and FUSE_PROJ and fc1_ln[0].is_cuda and fc1_ln[0].shape[1] == 128
+            """the split3 image of a block tail (projection + LayerNorm-folded fc1 + fc2), or None: CPU weights (tests of the pack layouts), ST_SPLIT3=0"""
+            if not (SPLIT3 and fc1_ln[0].is_cuda and fc1_ln[0].shape[1] == 128
                     and (proj is None or proj[0].shape == (128, 128))):
                 return None
             return ops.mlp128_split3_pack(fc1_ln[0], fc1_ln[1], fc2[0], proj=None if proj is None else (proj[0], proj[1]))
 
         def lin_image(w_b):
-            """the split3 image of a LayerNorm-folded Linear(128 -> N), or None (CPU weights, switch off)"""
+            """the split3 image of a LayerNorm-folded Linear(128 -> N), or None (CPU weights, ST_SPLIT3=0)"""
             w, b = w_b if isinstance(w_b, (tuple, list)) else (w_b, None)
-            if not (SPLIT3 and S3_LIN and FUSE_LN and w.is_cuda and w.shape[1] == 128 and w.shape[0] % 32 == 0 and w.is_contiguous()):
+            if not (SPLIT3 and w.is_cuda and w.shape[1] == 128 and w.shape[0] % 32 == 0 and w.is_contiguous()):
                 return None
             return ops.rowlin128_split3_pack(w, b)
 
@@ -156,8 +136,8 @@ class FlowFormer(ParamTree):
                          pe["f0"][0], pe["f2"][0], pe["f2"][1], pe["norm"][0], pe["norm"][1]]
         if SPLIT3 and pe["c4"][0].is_cuda:               # (a pack on the CPU -- layout tests -- has no planes: the module cannot run there anyway)
             pe["c4_s3"] = ops.split3_pack(pe["c4"][0])          # [64, 36 taps * 32]: the split3 form of PatchEmbed's third convolution
-            if S3_PE_TAIL:
-                pe["tail_s3"] = ops.pe_tail_split3_pack(pe["f0"][0], pe["f2"][0])       # ffn_with_coord (64 -> 128 -> 128) + LayerNorm as one launch
+            # ffn_with_coord (64 -> 128 -> 128) + LayerNorm: three HBM-bound launches over M P rows as one
+            pe["tail_s3"] = ops.pe_tail_split3_pack(pe["f0"][0], pe["f2"][0])
         pk["pe"] = pe
         pk["latents"] = p[c + "latent_tokens"][0].contiguous()
 
@@ -170,10 +150,9 @@ class FlowFormer(ParamTree):
                 d["qkv_s3"] = lin_image(d["qkv_ln"])
             d["kv"] = cat_lin([name + ".k", name + ".v"])
             d["f0_ln"] = ops.fold_layernorm(*d["n2"], *d["f0"])
-            if S3_CHAIN:
-                # the latent layers' tails are the same operator as the Block tails with hidden = 128 (proj + residual -> LN -> ffn.0 + GELU -> ffn.3 + residual)
-                d["mlp_s3"] = mlp_image(d["f0_ln"], d["f3"], d["proj"])
-                d["mlp_s3_plain"] = mlp_image(d["f0_ln"], d["f3"], None)
+            # the latent layers' tails are the same operator as the Block tails with hidden = 128 (proj + residual -> LN -> ffn.0 + GELU -> ffn.3 + residual)
+            d["mlp_s3"] = mlp_image(d["f0_ln"], d["f3"], d["proj"])
+            d["mlp_s3_plain"] = mlp_image(d["f0_ln"], d["f3"], None)
             return d
         pk["xin"] = attn_layer(c + "input_layer", False)
         # first layer: the queries are the (normalised, projected) latent tokens themselves -- constants of the weights.
@@ -282,23 +261,21 @@ class FlowFormer(ParamTree):
         if proj is not None:
             att, (pw, pb), pres = proj
             dev = att.device
-            if (fc1_ln is not None and FUSE_LN and FUSE_MLP and FUSE_PROJ and att.shape[1] == 128 and pw.is_contiguous()
+            if (fc1_ln is not None and att.shape[1] == 128 and pw.is_contiguous()
                     and fc2[0].is_contiguous() and fc1_ln[0].is_contiguous() and pw.data_ptr() % 16 == 0 and pb.data_ptr() % 16 == 0):
                 o = _new(att.shape[0], 128, dev) if out is None else out
                 return ops.mlp128(att, o, fc1_ln[0], fc1_ln[1], fc2[0], fc2[1], ln_eps=eps, res=extra_res, proj=(pw, pb, pres), image=image)
             x = _new(att.shape[0], att.shape[1], dev)
             ops.conv_gemm(att, pw, x, bias=pb, aux0=pres)
         dev = x.device
-        if fc1_ln is not None and FUSE_LN and FUSE_MLP and x.shape[1] == 128 and fc2[0].is_contiguous() and fc1_ln[0].is_contiguous():
-            o = _new(x.shape[0], 128, dev) if out is None else out
+        if fc1_ln is not None and x.shape[1] == 128 and fc2[0].is_contiguous() and fc1_ln[0].is_contiguous():
+            o = _new(x.shape[0], 128, dev) if out is None else out         # (projection weights the fused launch cannot read 16 B at a time)
             return ops.mlp128(x, o, fc1_ln[0], fc1_ln[1], fc2[0], fc2[1], ln_eps=eps, res=extra_res)
+        # C = 256 (Twins stage 2): LayerNorm, fc1 + GELU, fc2 + residual(s) as three launches
         h = _new(x.shape[0], fc1[0].shape[0], dev)
-        if fc1_ln is not None and FUSE_LN:
-            ops.conv_gemm(x, fc1_ln[0], h, bias=fc1_ln[1], act="gelu", ln_eps=eps)
-        else:
-            y = _new(x.shape[0], x.shape[1], dev)
-            ops.layernorm(x, n2[0], n2[1], y, eps)
-            ops.conv_gemm(y, fc1[0], h, bias=fc1[1], act="gelu")
+        y = _new(x.shape[0], x.shape[1], dev)
+        ops.layernorm(x, n2[0], n2[1], y, eps)
+        ops.conv_gemm(y, fc1[0], h, bias=fc1[1], act="gelu")
         o = _new(x.shape[0], x.shape[1], dev) if out is None else out
         if extra_res is None:
             ops.conv_gemm(h, fc2[0], o, bias=fc2[1], aux0=x)
@@ -323,11 +300,11 @@ class FlowFormer(ParamTree):
             L = t[f"l{s}"]
             y = _new(N, C, dev)
             qkv = _new(N, 3 * C, dev)
-            if L.get("qkv_s3") is not None and FUSE_LN:
+            if L.get("qkv_s3") is not None:
                 ops.rowlin128_split3(x, qkv, L["qkv_s3"], ln_eps=1e-6)
-            elif "qkv_ln" in L and FUSE_LN:
+            elif "qkv_ln" in L:
                 ops.conv_gemm(x, L["qkv_ln"][0], qkv, bias=L["qkv_ln"][1], ln_eps=1e-6)
-            else:
+            else:                                               # C = 256
                 ops.layernorm(x, L["n1"][0], L["n1"][1], y, 1e-6)
                 ops.conv_gemm(y, L["qkv"][0], qkv, bias=L["qkv"][1])
             att = _new(N, C, dev)
@@ -374,7 +351,7 @@ class FlowFormer(ParamTree):
             self._const[key] = tab
         # 64x64 maps: the first two convs run as one launch that keeps the first feature map (64 KiB per map, 537 MB per pair) on the CU
         s3, s4, f = _new(M * P, 64, dev), _new(M * P, 128, dev), _new(M * P, 128, dev)
-        if SPLIT3 and S3_PE and FUSE_PE and H2 == 64 and W2 == 64 and "c4_s3" in pe:
+        if H2 == 64 and W2 == 64 and "c4_s3" in pe:
             # Conv2d(32, 64, 6, 2, 2) -- 77 of the operator's 99 GFLOP -- on exact-split operands: the fused c0 + c2 launch emits bf16 planes
             # (no fp32 second feature map at all), in chunks of <= 16 384 maps (2 GiB buffer offsets)
             CH = 16384
@@ -384,7 +361,7 @@ class FlowFormer(ParamTree):
                 ops.patch_embed_split3(cost_maps[m0:m1], pe["embed11"], pe["f0"][0].stride(0), self._const[key], s2p, pe["c4_s3"],
                                        s3[m0 * P:m1 * P], s4[m0 * P:m1 * P], f[m0 * P:m1 * P], m1 - m0, H2, W2, tail_image=pe.get("tail_s3"))
             return f, P
-        s1 = None if (H2 == 64 and W2 == 64 and FUSE_PE) else _new(M * H1 * W1, 16, dev)
+        s1 = None if (H2 == 64 and W2 == 64) else _new(M * H1 * W1, 16, dev)
         s2 = _new(M * H2p * W2p, 32, dev)
         ops.patch_embed(cost_maps, pe["embed11"], pe["f0"][0].stride(0), self._const[key], s1, s2, s3, s4, f, M, H2, W2)
         return f, P
@@ -417,50 +394,27 @@ class FlowFormer(ParamTree):
                 proj_b = L["proj"][1]
             x1 = _new(M * nl, 128, dev)
             ops.conv_gemm(att, L["proj"][0], x1, bias=proj_b, aux0=lat, row_mod=nl)
-        else:
-            qkv = _new(M * nl, 384, dev)
-            if FUSE_LN and L.get("qkv_s3") is not None:
-                ops.rowlin128_split3(x, qkv, L["qkv_s3"], ln_eps=1e-5)
-            elif FUSE_LN:
-                ops.conv_gemm(x, L["qkv_ln"][0], qkv, bias=L["qkv_ln"][1], ln_eps=1e-5)
-            else:
-                y = _new(M * nl, 128, dev)
-                ops.layernorm(x, L["n1"][0], L["n1"][1], y, 1e-5)
-                ops.conv_gemm(y, L["qkv"][0], qkv, bias=L["qkv"][1])
-            att = _new(M * nl, 128, dev)
-            ops.attention_small(qkv[:, :128], (nl * 384, 384), qkv[:, 128:256], (nl * 384, 384), qkv[:, 256:], (nl * 384, 384),
-                                att, (nl * 128, 128), M, 8, nl, nl, 16, 16 ** -0.5)
-            if FUSE_CHAIN:
-                # proj + residual -> LayerNorm -> ffn.0 + GELU -> ffn.3 + residual in ONE launch: x1 and the hidden activation
-                # never leave the CU (encoder.py:163-172)
-                o = _new(M * nl, 128, dev)
-                if L.get("mlp_s3") is not None:                 # ... on the split3 kernel (st_mlp128_split3, hidden = 128)
-                    return ops.mlp128(att, o, L["f0_ln"][0], L["f0_ln"][1], L["f3"][0], L["f3"][1], ln_eps=1e-5, proj=(L["proj"][0], L["proj"][1], x), image=L["mlp_s3"])
-                return ops.linear_chain128(att, o, [dict(w=L["proj"][0], bias=L["proj"][1], res=x),
-                                                    dict(w=L["f0_ln"][0], bias=L["f0_ln"][1], act="gelu", ln_eps=1e-5),
-                                                    dict(w=L["f3"][0], bias=L["f3"][1], res=1)])
-            x1 = _new(M * nl, 128, dev)
-            ops.conv_gemm(att, L["proj"][0], x1, bias=L["proj"][1], aux0=x)
-        return self._mlp_plain(x1, L)
-
-    @staticmethod
-    def _mlp_plain(x, L):
-        dev = x.device
-        if FUSE_CHAIN:                                          # LayerNorm -> ffn.0 + GELU -> ffn.3 + residual, one launch
+            # LayerNorm -> ffn.0 + GELU -> ffn.3 + residual, one launch
+            o = _new(M * nl, 128, dev)
             if L.get("mlp_s3_plain") is not None:
-                return ops.mlp128(x, _new(x.shape[0], x.shape[1], dev), L["f0_ln"][0], L["f0_ln"][1], L["f3"][0], L["f3"][1], ln_eps=1e-5, image=L["mlp_s3_plain"])
-            return ops.linear_chain128(x, _new(x.shape[0], x.shape[1], dev),
-                                       [dict(w=L["f0_ln"][0], bias=L["f0_ln"][1], act="gelu", ln_eps=1e-5), dict(w=L["f3"][0], bias=L["f3"][1], res=0)])
-        h = _new(x.shape[0], L["f0"][0].shape[0], dev)
-        if FUSE_LN:
-            ops.conv_gemm(x, L["f0_ln"][0], h, bias=L["f0_ln"][1], act="gelu", ln_eps=1e-5)
+                return ops.mlp128(x1, o, L["f0_ln"][0], L["f0_ln"][1], L["f3"][0], L["f3"][1], ln_eps=1e-5, image=L["mlp_s3_plain"])
+            return ops.linear_chain128(x1, o, [dict(w=L["f0_ln"][0], bias=L["f0_ln"][1], act="gelu", ln_eps=1e-5), dict(w=L["f3"][0], bias=L["f3"][1], res=0)])
+        qkv = _new(M * nl, 384, dev)
+        if L.get("qkv_s3") is not None:
+            ops.rowlin128_split3(x, qkv, L["qkv_s3"], ln_eps=1e-5)
         else:
-            y = _new(x.shape[0], x.shape[1], dev)
-            ops.layernorm(x, L["n2"][0], L["n2"][1], y, 1e-5)
-            ops.conv_gemm(y, L["f0"][0], h, bias=L["f0"][1], act="gelu")
-        o = _new(x.shape[0], x.shape[1], dev)
-        ops.conv_gemm(h, L["f3"][0], o, bias=L["f3"][1], aux0=x)
-        return o
+            ops.conv_gemm(x, L["qkv_ln"][0], qkv, bias=L["qkv_ln"][1], ln_eps=1e-5)
+        att = _new(M * nl, 128, dev)
+        ops.attention_small(qkv[:, :128], (nl * 384, 384), qkv[:, 128:256], (nl * 384, 384), qkv[:, 256:], (nl * 384, 384),
+                            att, (nl * 128, 128), M, 8, nl, nl, 16, 16 ** -0.5)
+        # proj + residual -> LayerNorm -> ffn.0 + GELU -> ffn.3 + residual in ONE launch: x1 and the hidden activation
+        # never leave the CU (encoder.py:163-172)
+        o = _new(M * nl, 128, dev)
+        if L.get("mlp_s3") is not None:                 # ... on the split3 kernel (st_mlp128_split3, hidden = 128)
+            return ops.mlp128(att, o, L["f0_ln"][0], L["f0_ln"][1], L["f3"][0], L["f3"][1], ln_eps=1e-5, proj=(L["proj"][0], L["proj"][1], x), image=L["mlp_s3"])
+        return ops.linear_chain128(att, o, [dict(w=L["proj"][0], bias=L["proj"][1], res=x),
+                                            dict(w=L["f0_ln"][0], bias=L["f0_ln"][1], act="gelu", ln_eps=1e-5),
+                                            dict(w=L["f3"][0], bias=L["f3"][1], res=1)])
 
     def _vertical(self, V, x, ctx, B, H1, W1, nl, extra_res=None):
         """VerticalSelfAttentionLayer (encoder.py:121-125): Block(LSA ws7) -> Block(GSA sr4) with context
@@ -472,8 +426,6 @@ class FlowFormer(ParamTree):
         Cq = C + Cc
         # ---------------- local block
         y = _new(R, C, dev)
-        if not FUSE_LN:
-            ops.layernorm(x, V["ln1"][0], V["ln1"][1], y, 1e-5)
         z = _new(B * N, Cq, dev)                                             # [0 + code | context projection + code]
         ops.conv_gemm(ctx, V["lctx"][0], z[:, C:], bias=V["lctx"][1])
         ops.sine_pe(z, Cq, Wg=W1, ws=7, period=N, accumulate=C)             # window-local code (twins.py:285-288)
@@ -482,12 +434,10 @@ class FlowFormer(ParamTree):
         T = _new(B * N, 3 * C, dev)
         ops.conv_gemm(z, V["ltab"][0], T, bias=V["ltab"][1])
         qkv = _new(R, 3 * C, dev)
-        if FUSE_LN and V.get("lqkv_s3") is not None:
+        if V.get("lqkv_s3") is not None:
             ops.rowlin128_split3(x, qkv, V["lqkv_s3"], ln_eps=1e-5, aux=T, row_div=nl)
-        elif FUSE_LN:
-            ops.conv_gemm(x, V["lqkv_ln"][0], qkv, bias=V["lqkv_ln"][1], aux0=T, row_div=nl, ln_eps=1e-5)
         else:
-            ops.conv_gemm(y, V["lqkv"], qkv, aux0=T, row_div=nl)
+            ops.conv_gemm(x, V["lqkv_ln"][0], qkv, bias=V["lqkv_ln"][1], aux0=T, row_div=nl, ln_eps=1e-5)
         q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
         key = ("lsa_pad", id(V))
         if key not in self._const:
@@ -545,7 +495,7 @@ class FlowFormer(ParamTree):
                                 att[sl], (C, nl * C), nl, 8, N, Nk, 16, 16 ** -0.5)
         return self._mlp(None, V["gn2"], V["gfc1"], V["gfc2"], 1e-5, fc1_ln=V["gfc1_ln"], extra_res=extra_res, proj=(att, V["gproj"], x2), image=V.get("gmlp_s3"))
 
-    def _cost_encoder(self, cost_maps, ctx, B, H1, W1, ctx_ready=None):
+    def _cost_encoder(self, cost_maps, ctx, B, H1, W1):
         """CostPerceiverEncoder.forward (encoder.py:258-287) -> cost memory rows [B*N*8, 128]."""
         pk = self._pk
         M = B * H1 * W1
@@ -555,8 +505,6 @@ class FlowFormer(ParamTree):
         nl = pk["latents"].shape[0]
         for i in range(HP["encoder_depth"]):
             x = self._latent_layer(pk["self"][i], x, M, False)
-            if i == 0 and ctx_ready is not None:
-                torch.cuda.current_stream().wait_event(ctx_ready)            # ST_FORK: the context comes from the side stream
             # cost_encoder_res (encoder.py:281-282) adds the short-cut to the output of the last layer: a second residual operand
             # in that layer's final GEMM epilogue (no add pass, one k/v projection in the decoder)
             x = self._vertical(pk["vert"][i], x, ctx, B, H1, W1, nl, extra_res=short if i == HP["encoder_depth"] - 1 else None)
@@ -585,10 +533,10 @@ class FlowFormer(ParamTree):
             # shares hxA's strides (second A source of the q convs).  Every channel that is read is written first in each iteration:
             # hxA 0..127 by the q convs / proj_net, 128..253 by `conv`, 254..255 by flow_encode, 256..383 by the aggregate.
             S.update(hxA_p=ops.Planes(R, 384, dev), hxB_p=ops.Planes(R, 384, dev), cor1_p=ops.Planes(R, 256, dev), flo1_p=ops.Planes(R, 128, dev),
-                     corflo_p=ops.Planes(R, 256, dev), vT_p=ops.Planes(B * 128, N, dev))
+                     corflo_p=ops.Planes(R, 256, dev))
         return S
 
-    def _update_block(self, S, coords1, attn, gru_tab, B, H1, W1, enc_done=None):
+    def _update_block(self, S, coords1, attn, gru_tab, B, H1, W1):
         """GMAUpdateBlock.forward (gru.py:322-334) without the mask head: BasicMotionEncoder (gru.py:246-254), GMA
         aggregate (gma.py:102-115), SepConvGRU (gru.py:44-59), flow head (gru.py:5-13); coords1 += delta_flow
         (decoder.py:329).  Reads S['corr'] (cost_forward | cost_global), updates S['hxA'][:, :128] (net) and coords1."""
@@ -599,57 +547,27 @@ class FlowFormer(ParamTree):
         if S["s3"]:
             W3 = D["s3"]
             hxA_p = S["hxA_p"]
-            if S3_AGG and torch.is_tensor(attn):      # a caller that built the attention matrix itself (tests): its planes, here
-                attn = ops.split3_pack(attn.view(B * N, N))
             # convc1 (K = 160) stays on the fp32 kernel and emits cor1's planes; flow_encode emits flo1's and the flow's two channels
             ops.conv_gemm(corr, D["convc1"][0], S["cor1"], bias=D["convc1"][1], act="relu", out_planes=S["cor1_p"])
             ops.flow_encode_split3(coords1, D["convf1"][0], D["convf1"][1], S["flo1"], hxA[:, 254:256], B, H1, W1, S["flo1_p"], (hxA_p, 254))
-            nf = not (S3_OFF & 16)
-            if S3_OFF & 32:
-                ops.conv_gemm_pair((S["cor1"], D["convc2"][0], S["corflo"][:, :192], dict(geom=g3, bias=D["convc2"][1], act="relu", out_planes=S["corflo_p"].cols(0, 192))),
-                                   (S["flo1"], D["convf2"][0], S["corflo"][:, 192:], dict(geom=g3, bias=D["convf2"][1], act="relu", out_planes=S["corflo_p"].cols(192, 256))))
-            elif not S3_PAIR:
-                ops.conv_gemm(S["cor1_p"], W3["convc2"], S["corflo"][:, :192], geom=g3, bias=D["convc2"][1], act="relu", out_planes=S["corflo_p"].cols(0, 192), no_f32=nf)
-                ops.conv_gemm(S["flo1_p"], W3["convf2"], S["corflo"][:, 192:], geom=g3, bias=D["convf2"][1], act="relu", out_planes=S["corflo_p"].cols(192, 256), no_f32=nf)
-            else:
-                ops.conv_gemm_pair((S["cor1_p"], W3["convc2"], S["corflo"][:, :192],
-                                    dict(geom=g3, bias=D["convc2"][1], act="relu", out_planes=S["corflo_p"].cols(0, 192), no_f32=nf)),
-                                   (S["flo1_p"], W3["convf2"], S["corflo"][:, 192:],
-                                    dict(geom=g3, bias=D["convf2"][1], act="relu", out_planes=S["corflo_p"].cols(192, 256), no_f32=nf)))
-            if S3_OFF & 16:
-                ops.conv_gemm(S["corflo"], D["conv"][0], hxA[:, 128:254], geom=g3, bias=D["conv"][1], act="relu", out_planes=hxA_p.cols(128, 256))
-            else:
-                ops.conv_gemm(S["corflo_p"], W3["conv"], hxA[:, 128:254], geom=g3, bias=D["conv"][1], act="relu", out_planes=hxA_p.cols(128, 256))
-            if S3_AGG:
-                ops.gma_aggregate_split3(attn, hxA[:, 128:256], D["to_v"], D["gamma"], S["vT"], S["vT_p"], hxA[:, 256:], hxA_p.cols(256, 384), B, N)
-            else:
-                # the aggregate reads the whole attention matrix every iteration and is HBM-bound either way (fp32: 134 MB per launch, 64.8 us in
-                # the chain; planes: 201 MB, 66.2 us): it stays on the fp32 kernel, whose epilogue emits the planes of its result
-                ops.gma_aggregate(attn, hxA[:, 128:256], D["to_v"], D["gamma"], S["vT"], hxA[:, 256:], B, N, out_planes=hxA_p.cols(256, 384))
-            if S3_OFF & 8:
-                ops.sepconv_gru(hxA, hxB, S["zbuf"], gru_tab["1"], gru_tab["2"], D["zr1"], D["q1"], D["zr2"], D["q2"], B, H1, W1)
-                ops.split3_pack(hxA[:, :128], out=hxA_p.cols(0, 128))
-            else:
-                ops.sepconv_gru_split3(hxA, hxA_p, S["hxB_p"], S["zbuf"], gru_tab["1"], gru_tab["2"], W3["zr1"], W3["q1"], W3["zr2"], W3["q2"], B, H1, W1)
-            if S3_OFF & 2:
-                ops.conv_gemm(hxA[:, :128], D["fh1"][0], S["fh"], geom=g3, bias=D["fh1"][1], act="relu")
-            else:
-                ops.conv_gemm(hxA_p.cols(0, 128), W3["fh1"], S["fh"], geom=g3, bias=D["fh1"][1], act="relu")
+            ops.conv_gemm_pair((S["cor1_p"], W3["convc2"], S["corflo"][:, :192],
+                                dict(geom=g3, bias=D["convc2"][1], act="relu", out_planes=S["corflo_p"].cols(0, 192), no_f32=True)),
+                               (S["flo1_p"], W3["convf2"], S["corflo"][:, 192:],
+                                dict(geom=g3, bias=D["convf2"][1], act="relu", out_planes=S["corflo_p"].cols(192, 256), no_f32=True)))
+            ops.conv_gemm(S["corflo_p"], W3["conv"], hxA[:, 128:254], geom=g3, bias=D["conv"][1], act="relu", out_planes=hxA_p.cols(128, 256))
+            # the aggregate reads the whole attention matrix every iteration and is HBM-bound either way (fp32: 134 MB per launch, 64.8 us in
+            # the chain; planes: 201 MB, 66.2 us): it stays on the fp32 kernel, whose epilogue emits the planes of its result
+            ops.gma_aggregate(attn, hxA[:, 128:256], D["to_v"], D["gamma"], S["vT"], hxA[:, 256:], B, N, out_planes=hxA_p.cols(256, 384))
+            ops.sepconv_gru_split3(hxA, hxA_p, S["hxB_p"], S["zbuf"], gru_tab["1"], gru_tab["2"], W3["zr1"], W3["q1"], W3["zr2"], W3["q2"], B, H1, W1)
+            ops.conv_gemm(hxA_p.cols(0, 128), W3["fh1"], S["fh"], geom=g3, bias=D["fh1"][1], act="relu")
             ops.conv_gemm(S["fh"], D["fh2"][0], coords1, geom=g3, bias=D["fh2"][1], epi="add", aux1=coords1)
             return
         ops.conv_gemm(corr, D["convc1"][0], S["cor1"], bias=D["convc1"][1], act="relu")
-        if enc_done is not None:
-            torch.cuda.current_stream().wait_event(enc_done)         # ST_FORK_ENC: already enqueued on the side stream by _decoder
-        else:
-            ops.flow_encode(coords1, D["convf1"][0], D["convf1"][1], S["flo1"], hxA[:, 254:256], B, H1, W1)      # :321, gru.py:251,254
+        ops.flow_encode(coords1, D["convf1"][0], D["convf1"][1], S["flo1"], hxA[:, 254:256], B, H1, W1)      # :321, gru.py:251,254
         # convc2 (384 tiles) and convf2 (128 tiles) are independent and ready together: one launch, two workgroups per CU, no
         # split-K slabs (gru.py:252-253)
-        if PAIR_CONVS:
-            ops.conv_gemm_pair((S["cor1"], D["convc2"][0], S["corflo"][:, :192], dict(geom=g3, bias=D["convc2"][1], act="relu")),
-                               (S["flo1"], D["convf2"][0], S["corflo"][:, 192:], dict(geom=g3, bias=D["convf2"][1], act="relu")))
-        else:
-            ops.conv_gemm(S["cor1"], D["convc2"][0], S["corflo"][:, :192], geom=g3, bias=D["convc2"][1], act="relu", split_k=1)
-            ops.conv_gemm(S["flo1"], D["convf2"][0], S["corflo"][:, 192:], geom=g3, bias=D["convf2"][1], act="relu", split_k=1)
+        ops.conv_gemm_pair((S["cor1"], D["convc2"][0], S["corflo"][:, :192], dict(geom=g3, bias=D["convc2"][1], act="relu")),
+                           (S["flo1"], D["convf2"][0], S["corflo"][:, 192:], dict(geom=g3, bias=D["convf2"][1], act="relu")))
         ops.conv_gemm(S["corflo"], D["conv"][0], hxA[:, 128:254], geom=g3, bias=D["conv"][1], act="relu")
         # GMA aggregate: v^T = Wv . mf^T, out = mf + gamma * attn @ v
         ops.gma_aggregate(attn, hxA[:, 128:256], D["to_v"], D["gamma"], S["vT"], hxA[:, 256:], B, N)
@@ -661,7 +579,7 @@ class FlowFormer(ParamTree):
     def _mask_head(self, S, B, H1, W1):
         """mask = .25 * conv1x1(relu(conv3x3(net))) (gru.py:315-318,333) -> rows [R, 576]."""
         D = self._pk["dec"]
-        if S["s3"] and not (S3_OFF & 1):
+        if S["s3"]:
             ops.conv_gemm(S["hxA_p"].cols(0, 128), D["s3"]["m0"], S["fh"], geom=(B, H1, W1, 3, 3, 1, 1, 1, 1), bias=D["m0"][1], act="relu")
         else:
             ops.conv_gemm(S["hxA"][:, :128], D["m0"][0], S["fh"], geom=(B, H1, W1, 3, 3, 1, 1, 1, 1), bias=D["m0"][1], act="relu")
@@ -685,19 +603,16 @@ class FlowFormer(ParamTree):
         qk = _new(R, 256, dev)
         attn = torch.empty((B, N, N), device=dev)
         ops.gma_attention(inp, D["qk"], qk, attn, B, N)
-        if S["s3"] and S3_AGG:     # (ST_S3_AGG=1: the aggregate on planes too: the attention matrix's planes, once per pass)
-            attn = ops.split3_pack(attn.view(B * N, N))
         return dict(S=S, inp=inp, gru_tab=gru_tab, attn=attn, qk=qk)
 
-    def _decoder(self, mem, mem_short, ctx, cost_maps, B, H1, W1, iters, trace=None, pre=None):
+    def _decoder(self, mem, mem_short, ctx, cost_maps, B, H1, W1, iters, trace=None):
         """MemoryDecoder.forward eval branch (decoder.py:262-344)."""
         D = self._pk["dec"]
         dev = ctx.device
         N = H1 * W1
         R = B * N
         nl = self._pk["latents"].shape[0]
-        if pre is None:
-            pre = self._decoder_prologue(ctx, B, H1, W1)
+        pre = self._decoder_prologue(ctx, B, H1, W1)
         S, gru_tab, attn = pre["S"], pre["gru_tab"], pre["attn"]
         # k, v of the cost-memory cross attention, once (decoder.py:68-70); memory = x + short_cut (linear -> two GEMMs)
         ca = D["ca"]
@@ -711,19 +626,10 @@ class FlowFormer(ParamTree):
         coords1 = _new(R, 2, dev)
         ops.coords_grid(coords1, B, H1, W1)
         for it in range(iters):
-            enc_done = None
-            if FORK_ENC:
-                cur = torch.cuda.current_stream()
-                side = _side_stream(cur)
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    ops.flow_encode(coords1, D["convf1"][0], D["convf1"][1], S["flo1"], S["hxA"][:, 254:256], B, H1, W1)
-                    enc_done = torch.cuda.Event()
-                    enc_done.record(side)
             ops.cost_lookup9x9(cost_maps, coords1, S["corr"], R, H1, W1)                              # decoder.py:291
             # flow_token_encoder + cost-memory cross attention + FFN: one fused launch (decoder.py:305-312)
             ops.decoder_token_chain(S["corr"], coords1, kv, D["chain16"], R, nl)
-            self._update_block(S, coords1, attn, gru_tab, B, H1, W1, enc_done=enc_done)
+            self._update_block(S, coords1, attn, gru_tab, B, H1, W1)
             if trace is not None:
                 trace.append(dict(coords1=coords1.clone(), net=S["hxA"][:, :128].clone(), corr=S["corr"].clone()))
         # mask head + convex upsampling, last iteration only (gru.py:315-318,333; decoder.py:214-225)
@@ -777,29 +683,15 @@ class FlowFormer(ParamTree):
         x = _new(2 * B * H * W, 4, dev)
         ops.prep_image(image_a.contiguous(), x[:B * H * W], 4, 2.0, 255.0, 1.0)
         ops.prep_image(image_b.contiguous(), x[B * H * W:], 4, 2.0, 255.0, 1.0)
-        pre = ctx_ready = side = None
-        if FORK:
-            cur = torch.cuda.current_stream()
-            side = _side_stream(cur)
-            side_ws = ops.side_workspace(dev)                                # split-K slabs of the side branch (looked up on THIS stream)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side), ops.workspace_scope(side_ws):
-                ctx, H1, W1 = self._twins(pk["cnet"], x, 2 * B, H, W)
-                ctx_ready = torch.cuda.Event()
-                ctx_ready.record(side)
-                pre = self._decoder_prologue(ctx, 2 * B, H1, W1)
-        else:
-            ctx, H1, W1 = self._twins(pk["cnet"], x, 2 * B, H, W)          # context of a (pass a->b) then of b (pass b->a)
+        ctx, H1, W1 = self._twins(pk["cnet"], x, 2 * B, H, W)          # context of a (pass a->b) then of b (pass b->a)
         feats, _, _ = self._twins(pk["fnet"], x, 2 * B, H, W)
         N = H1 * W1
         feats = feats.view(2, B, N, 256)
         cost_maps = torch.empty((2 * B * N, N), device=dev)
         # the reverse direction's volume is the transpose of the forward one: one product, two stores
         ops.corr_volume_both(feats[0], feats[1], cost_maps[:B * N].view(B, N, N), cost_maps[B * N:].view(B, N, N))
-        mem, short = self._cost_encoder(cost_maps, ctx, 2 * B, H1, W1, ctx_ready=ctx_ready)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-        flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, 2 * B, H1, W1, iters, pre=pre)
+        mem, short = self._cost_encoder(cost_maps, ctx, 2 * B, H1, W1)
+        flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, 2 * B, H1, W1, iters)
         return flow_up, coords1, (2 * B, H1, W1)
 
     def forward(self, image1, image2, mask=None, output=None, flow_init=None):

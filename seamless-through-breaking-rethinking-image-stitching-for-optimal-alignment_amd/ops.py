@@ -111,19 +111,6 @@ def new_workspace(dev):
     return torch.empty((16 * 1024 * 1024,), device=dev, dtype=torch.float32)
 
 
-_WS_SIDE = {}
-
-
-def side_workspace(dev):
-    """the companion of the CURRENT workspace for a forked branch of the same forward (flowformer.FORK): two branches that run
-    concurrently must not share split-K slabs.  Call it before switching to the side stream."""
-    base = _workspace(dev)
-    k = (dev.type, dev.index, base.data_ptr())
-    if k not in _WS_SIDE:
-        _WS_SIDE[k] = new_workspace(dev)
-    return _WS_SIDE[k]
-
-
 class workspace_scope:
     """``with ops.workspace_scope(ws):`` -- every split-K GEMM launched inside uses ``ws``."""
 
@@ -493,8 +480,8 @@ def cost_lookup9x9(maps, coords, out, Nq, H2, W2):
 
 
 def patch_embed(cost_maps, weights11, ld_f0, pe_bias, s1, s2, s3, s4, tokens, M, H, W):
-    """s1 = None: the caller expects the fused c0 + c2 launch (64 x 64 maps).  Whether it fuses is the LIBRARY's decision (its own reading of
-    ST_FUSE_PE, operand alignment): if it declines (ST_EINVAL) the scratch is allocated here and the call repeated -- the two sides cannot
+    """s1 = None: the caller expects the fused c0 + c2 launch (64 x 64 maps).  Whether it fuses is the LIBRARY's decision (shape and operand
+    alignment): if it declines (ST_EINVAL) the scratch is allocated here and the call repeated -- the two sides cannot
     disagree into a hard failure."""
     arr = (C.c_void_p * 11)(*[w.data_ptr() for w in weights11])
 
@@ -631,10 +618,9 @@ def flow_warp(x, flow, mul=None):
     return out
 
 
-def resize_bilinear(x, oh, ow, align_corners, div=None, out=None):
+def resize_bilinear(x, oh, ow, align_corners, div=None):
     B, Cc, H, W = x.shape
-    if out is None:
-        out = torch.empty((B, Cc, oh, ow), device=x.device, dtype=torch.float32)
+    out = torch.empty((B, Cc, oh, ow), device=x.device, dtype=torch.float32)
     d0, d1, nd = (div[0], div[1], 2) if div is not None else (1.0, 1.0, 0)
     check(lib.st_resize_bilinear(_pc(x), _p(out), B * Cc, H, W, oh, ow, int(align_corners), d0, d1, nd, _stream()),
           "st_resize_bilinear")

@@ -15,10 +15,6 @@ eager2 = [m(a.cuda(), b.cuda(), type="test_out") for a, b in pairs]
 keys = ("blend_image", "output2", "mask2", "residual_flow", "occlusion_mask", "H")
 print("eager vs eager:", {k: all(torch.equal(e[k], f[k]) for e, f in zip(eager, eager2)) for k in keys})
 cpu_ref = [{k: e[k].cpu().clone() for k in keys} for e in eager]
-KEEP = os.environ.get("ST_EXP_KEEP") == "1"
-if KEEP:
-    with torch.no_grad():
-        nets_ref = [{k: v.clone() for k, v in m._test_out_nets(a.cuda().float().contiguous(), b.cuda().float().contiguous()).items()} for a, b in pairs]
 gs = [m.graphed_test_out() for _ in range(2)]
 streams = [torch.cuda.Stream() for _ in range(2)]
 bad = {k: 0 for k in keys}
@@ -33,13 +29,6 @@ for rep in range(reps):
             torch.cuda.synchronize()
     outs = [gs[i].finish(h) for i, h in enumerate(handles)]
     torch.cuda.synchronize()
-    if KEEP:
-        for i, h in enumerate(handles):
-            for kk in ("flow512", "back512", "residual", "back", "warp2_512"):
-                if not torch.equal(h[2][kk], nets_ref[i][kk]):
-                    dd = (h[2][kk] - nets_ref[i][kk]).abs()
-                    ix = (dd > 0).nonzero()
-                    print(f"rep {rep} pair {i} NETS {kk}: {int((dd > 0).sum())} differ, max {dd.max().item():.3e}; planes {ix[:, 1].unique().tolist()} rows {ix[:, 2].min().item()}..{ix[:, 2].max().item()} cols {ix[:, 3].min().item()}..{ix[:, 3].max().item()}", flush=True)
     for i, (e, o) in enumerate(zip(eager, outs)):
         for k in keys:
             if not torch.equal(e[k], o[k]):

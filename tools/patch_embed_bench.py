@@ -1,6 +1,6 @@
 """PatchEmbed's three conv launches stand-alone (M = 8192 cost maps of 64x64: one pair): ms per call of ops.patch_embed's conv part.
-    ST_PERSIST_CONV=0|1 python tools/patch_embed_bench.py"""
-import os, sys, torch
+    python tools/patch_embed_bench.py"""
+import sys, torch
 sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
 import stitch_amd
 ops = stitch_amd.ops
@@ -25,9 +25,8 @@ def timeit(fn, n=10):
     for _ in range(n): fn()
     b.record(); torch.cuda.synchronize()
     return a.elapsed_time(b) / n * 1e3
-tag = f"ST_PERSIST_CONV={os.environ.get('ST_PERSIST_CONV', '0')} ST_PERSIST_SLOTS={os.environ.get('ST_PERSIST_SLOTS', '512')}"
 t2, t4 = timeit(c2), timeit(c4)
-print(f"{tag}: c2 (2097152x32x576) {t2:.1f} us = {2 * 2097152 * 32 * 576 / t2 / 1e6 / 157.3:.3f} of peak; c4 (524288x64x1152) {t4:.1f} us = {2 * 524288 * 64 * 1152 / t4 / 1e6 / 157.3:.3f} of peak")
+print(f"c2 (2097152x32x576) {t2:.1f} us = {2 * 2097152 * 32 * 576 / t2 / 1e6 / 157.3:.3f} of peak; c4 (524288x64x1152) {t4:.1f} us = {2 * 524288 * 64 * 1152 / t4 / 1e6 / 157.3:.3f} of peak")
 # ---- the fused c0 + c2 launch (st_patch_conv12) against patch_conv1 + c2
 w0 = (torch.randn(36, 16, generator=g) * 0.1).to(dev); b0 = torch.randn(16, generator=g).to(dev)
 def c0():

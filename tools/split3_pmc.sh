@@ -1,8 +1,10 @@
 #!/bin/bash
 # SQ counters of conv_gemm_split3_kernel on 8192x256x1920 (1x5 conv), tiles 64x64 and 128x64: separate rocprofv3 --pmc passes
-# (GPU box, repo root) -> gpurun_out/r6_split3_sq_counters.txt.  ST_SPLIT3_DIAG=1|2 in the environment profiles the ingest-only / MFMA-only variants.
+# (GPU box, repo root): bash tools/split3_pmc.sh [OUT_DIR] -> OUT_DIR/r6_split3_sq_counters.txt and the raw passes under OUT_DIR/s3_pmc
+# (default OUT_DIR: a new temporary directory).
 export TMPDIR=/tmp
-O=gpurun_out/s3_pmc${ST_SPLIT3_DIAG}
+OUT=${1:-$(mktemp -d)}
+O=$OUT/s3_pmc
 rm -rf $O; mkdir -p $O
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU" \
@@ -11,10 +13,10 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE
   i=$((i+1))
   rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/p$i -o pmc -- python3 tools/split3_pmc.py > $O/p$i.log 2>&1 || echo "pass $i failed: $(tail -2 $O/p$i.log)"
 done
-python3 - $O <<'PY' | tee gpurun_out/r6_split3_sq_counters${ST_SPLIT3_DIAG}.txt
-import csv, glob, collections, sys, os
+python3 - $O <<'PY' | tee $OUT/r6_split3_sq_counters.txt
+import csv, glob, collections, sys
 O = sys.argv[1]
-print(f"# SQ counters of conv_gemm_split3_kernel on M=8192 N=256 K=1920 (1x5 conv, Cin 384), ST_SPLIT3_DIAG={os.environ.get('ST_SPLIT3_DIAG', '0')}")
+print("# SQ counters of conv_gemm_split3_kernel on M=8192 N=256 K=1920 (1x5 conv, Cin 384)")
 print("# rocprofv3 --kernel-trace --pmc <one group per pass> -- python3 tools/split3_pmc.py (tools/split3_pmc.sh); last of 5 launches per tile config")
 per, durs = collections.OrderedDict(), {}
 for p in (1, 2, 3):
