@@ -533,6 +533,24 @@ int st_mix_mul_mask(const float* img3, const float* mask, float* out3, int32_t h
 int st_blend_pair(const float* output1_3, const float* mask1_3, const float* output2_3, const float* mask2, int32_t mask2_planes,
                   uint8_t* blend3, int32_t h, int32_t w, void* stream);
 
+/* ---- Telea inpainting (core/inference/mix_methods/utils/cv_inpainter.py: cv2.inpaint(img, mask, 64, INPAINT_TELEA)), restated
+ *      ring by ring (d = L1 distance to the known set mask == 0; contract in README.md, CPU restatement tests/_telea_ref.py) ----- */
+/* cv_inpainter's preprocessing: img3 [3,h,w] -> img_hwc uint8 [h,w,3] (clamp to 0..255, truncate); mask [mask_planes,h,w]
+ * (1 plane = repeated) scaled by 255 and clamped when its max is <= 1.1 (else clamped), truncated, PIL luma ->
+ * mask_u8 [h,w] (nonzero = fill).  scratch: one device int32.                                                             */
+int st_inpaint_prep(const float* img3, const float* mask, int32_t mask_planes, uint8_t* img_hwc, uint8_t* mask_u8, int32_t* scratch,
+                    int32_t h, int32_t w, void* stream);
+/* *bytes (HOST int64) = workspace size of st_inpaint_telea_rings / _fill for h x w and radius (1..88).                     */
+int st_inpaint_telea_workspace(int32_t h, int32_t w, int32_t radius, int64_t* bytes);
+/* d, ring buckets and packed state in `work`; ring_counts [h + w + 1] (device) = number of pixels per ring k (k = 0: known).
+ * counts[0] == 0: no known pixel.  The caller reads ring_counts back once and passes it to st_inpaint_telea_fill.            */
+int st_inpaint_telea_rings(const uint8_t* img_hwc, const uint8_t* mask_u8, int32_t h, int32_t w, int32_t radius, void* work,
+                           int64_t work_bytes, int32_t* ring_counts, void* stream);
+/* one launch per ring 1..nrings (ring_counts_host: HOST copy of ring_counts, nrings + 1 entries, each ring nonempty), then
+ * out_hwc uint8 [h,w,3]; d_out int32 [h,w] and T_out fp32 [h,w] (ring index and arrival time) may be NULL.                 */
+int st_inpaint_telea_fill(const int32_t* ring_counts_host, int32_t nrings, int32_t h, int32_t w, int32_t radius, void* work,
+                          int64_t work_bytes, uint8_t* out_hwc, int32_t* d_out, float* T_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

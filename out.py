@@ -7,10 +7,12 @@ Same flags, `demo.txt` pair list (one directory per line holding input1.jpg / in
 result-directory naming as the reference.  The forward (`type="test_out"`) and the TPS post-pipeline
 (core/inference/tps_pipline.py, `stitch_amd.tps_pipeline`) run on the HIP kernels; the composition stage (out.py:277-312,
 `cfg.use_composition`) runs on the post-TPS canvases.  The `mix_fn` plug-in named by `TPS_PIPELINE_CONFIG.mix_method` runs too
-(`stitch_amd.mix_methods`).  Differences from the reference's files: the neural inpainter inside `mix_fn` (TransRef /
-diffusion: fetched weights + third-party CUDA ops) is out of scope and replaced by a pass-through, so in `warp2.jpg`,
-`mask2.jpg`, `ave_fusion.jpg`, `composition.jpg`, `learned_mask*.jpg` the thin border `mix_fn` leaves to the inpainter is not
-synthesised; with the shipped `tps_method="opencv"` the spline is this package's own pixel-unit TPS (OpenCV is not
+(`stitch_amd.mix_methods`).  Differences from the reference's files: the neural inpainters inside `mix_fn` (TransRef /
+diffusion: fetched weights + third-party CUDA ops) are out of scope and replaced by a pass-through, so with the shipped configs in
+`warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg`, `composition.jpg`, `learned_mask*.jpg` the thin border `mix_fn` leaves to the inpainter
+is not synthesised (with `inpaint_all_area`: no hole is); `--inf_cfg all_img1_with_inpaint_g12_cv` / `inpaint_all_area_g12_cv`
+select `cv_inpainter`, the reference's OpenCV Telea inpainter restated as GPU kernels (README.md; unpinned against OpenCV), which
+fills them; with the shipped `tps_method="opencv"` the spline is this package's own pixel-unit TPS (OpenCV is not
 installable here: unpinned against OpenCV)."""
 from __future__ import annotations
 
@@ -120,9 +122,10 @@ class _Saver:
 
 @torch.no_grad()
 def load_inpainter(name):
-    """out.py:341-346: `core.inference.mix_methods.utils.<name>.inpainter`.  The reference's inpainters (TransRef, diffusion)
-    need fetched weights and third-party CUDA ops and are out of scope; a module of that name dropped into
-    `stitch_amd/mix_methods/utils/` is picked up, otherwise the pass-through stand-in is used."""
+    """out.py:341-346: `core.inference.mix_methods.utils.<name>.inpainter`.  `cv_inpainter` (the reference's OpenCV Telea
+    inpainter, GPU kernels here) is shipped; the neural ones (TransRef, diffusion) need fetched weights and third-party CUDA ops and
+    are out of scope; a module of that name dropped into `stitch_amd/mix_methods/utils/` is picked up, otherwise the pass-through
+    stand-in is used."""
     import importlib
     try:
         return importlib.import_module(f"stitch_amd.mix_methods.utils.{name}").inpainter
@@ -134,9 +137,10 @@ def load_inpainter(name):
 
 def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_model=None, inpainter=None, forward=None, saver=None):
     """out.py:158-312: forward (`test_out`), TPS post-pipeline with the configured `mix_fn`, saves, composition.  The neural
-    inpainter the reference calls inside `mix_fn` is out of scope (pass-through stand-in unless the caller supplies one): in
-    `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the composition inputs the holes hold what `mix_fn` fills from image 1, the
-    thin border region it hands to the inpainter is not synthesised.
+    inpainters the reference calls inside `mix_fn` are out of scope (pass-through stand-in unless the config names
+    `cv_inpainter` or the caller supplies one): with the stand-in, in `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the
+    composition inputs the holes hold what `mix_fn` fills from image 1 and the thin border region it hands to the inpainter is not
+    synthesised; `cv_inpainter` (GPU Telea inpainting, unpinned against OpenCV) fills it.
 
     ``forward``: a callable returning the `test_out` dict of this pair whose network part is already in flight (``main``
     launches pair i + 1's hipGraph before it finishes pair i); default = load + ``warp_model(..., type="test_out")`` here.

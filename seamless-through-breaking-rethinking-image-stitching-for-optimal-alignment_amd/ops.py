@@ -903,3 +903,68 @@ def blend_pair(output1, mask1, output2, mask2):
     blend = torch.empty((1, 3, H, W), device=output1.device, dtype=torch.uint8)
     check(lib.st_blend_pair(_pc(output1), _pc(mask1), _pc(output2), _pc(mask2), mask2.shape[1], _p(blend), H, W, _stream()), "st_blend_pair")
     return blend
+
+
+# ---- Telea inpainting (cv_inpainter) ------------------------------------------------------------
+INPAINT_MAX_RADIUS = 88
+
+
+def inpaint_prep(img3, mask):
+    """cv_inpainter's preprocessing on the GPU: img3 fp32 [3,H,W] -> uint8 [H,W,3] (clamped to 0..255, truncated); mask fp32
+    [1 or 3,H,W] -> uint8 [H,W] nonzero where to fill (x255 + clamp when its max is <= 1.1, truncation, PIL's integer luma)."""
+    if img3.dim() != 3 or img3.shape[0] != 3 or img3.dtype != torch.float32:
+        raise ValueError(f"fp32 [3,H,W] image expected, got {img3.dtype} {tuple(img3.shape)}")
+    _, H, W = img3.shape
+    if mask.dim() != 3 or mask.shape[0] not in (1, 3) or tuple(mask.shape[1:]) != (H, W) or mask.dtype != torch.float32:
+        raise ValueError(f"fp32 [1 or 3,{H},{W}] mask expected, got {mask.dtype} {tuple(mask.shape)}")
+    dev = img3.device
+    img_hwc = torch.empty((H, W, 3), device=dev, dtype=torch.uint8)
+    mask_u8 = torch.empty((H, W), device=dev, dtype=torch.uint8)
+    scratch = torch.empty((1,), device=dev, dtype=torch.int32)
+    check(lib.st_inpaint_prep(_pc(img3), _pc(mask), mask.shape[0], _p(img_hwc), _p(mask_u8), _p(scratch), H, W, _stream()),
+          "st_inpaint_prep")
+    return img_hwc, mask_u8
+
+
+def inpaint_telea(img, mask, radius=64, return_fields=False):
+    """Telea inpainting (cv2.inpaint(img, mask, radius, cv2.INPAINT_TELEA) restated ring by ring: README.md, cv_inpainter):
+    img uint8 [H,W,3], mask uint8 / bool [H,W] (nonzero = fill) -> uint8 [H,W,3].  One device -> host read (the ring sizes),
+    then one launch per ring on the current stream.  return_fields: also the ring index d (int32 [H,W], 0 on the known set) and
+    the arrival time T (fp32 [H,W]) -- None when no kernel filled anything (no hole, or no known pixel: image returned as is)."""
+    if img.dim() != 3 or img.shape[2] != 3 or img.dtype != torch.uint8:
+        raise ValueError(f"uint8 [H,W,3] image expected, got {img.dtype} {tuple(img.shape)}")
+    H, W, _ = img.shape
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.uint8)
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W):
+        raise ValueError(f"uint8 [{H},{W}] mask expected, got {mask.dtype} {tuple(mask.shape)}")
+    if not 1 <= int(radius) <= INPAINT_MAX_RADIUS:
+        raise ValueError(f"radius must be in 1..{INPAINT_MAX_RADIUS}, got {radius}")
+    if mask.device != img.device:
+        raise ValueError("image and mask must be on the same device")
+    dev = img.device
+    nbytes = C.c_int64()
+    check(lib.st_inpaint_telea_workspace(H, W, int(radius), C.byref(nbytes)), "st_inpaint_telea_workspace")
+    work = torch.empty((nbytes.value,), device=dev, dtype=torch.uint8)
+    counts = torch.empty((H + W + 1,), device=dev, dtype=torch.int32)
+    check(lib.st_inpaint_telea_rings(_pc(img), _pc(mask), H, W, int(radius), _p(work), nbytes.value, _p(counts), _stream()),
+          "st_inpaint_telea_rings")
+    host = counts.cpu()                                  # the one device -> host read: ring sizes
+    nz = torch.nonzero(host).flatten()
+    nrings = int(nz[-1]) if len(nz) else 0
+    if int(host[0]) == 0 or nrings == 0:                 # no known pixel / nothing to fill: no fill kernel runs
+        out = img.clone()
+        return (out, None, None) if return_fields else out
+    ring_counts = (C.c_int32 * (nrings + 1))(*host[:nrings + 1].tolist())
+    out = torch.empty_like(img)
+    d = torch.empty((H, W), device=dev, dtype=torch.int32) if return_fields else None
+    T = torch.empty((H, W), device=dev, dtype=torch.float32) if return_fields else None
+    check(lib.st_inpaint_telea_fill(ring_counts, nrings, H, W, int(radius), _p(work), nbytes.value, _p(out), _p(d), _p(T), _stream()),
+          "st_inpaint_telea_fill")
+    return (out, d, T) if return_fields else out
+
+
+def inpaint_disc_size(radius=64):
+    """number of offsets 0 < |r| <= radius one filled pixel gathers over"""
+    from math import isqrt
+    return sum(2 * isqrt(radius * radius - y * y) + 1 for y in range(-radius, radius + 1)) - 1

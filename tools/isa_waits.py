@@ -5,7 +5,7 @@ usage: python tools/isa_waits.py [file.hip ...]"""
 import os, re, subprocess, sys, tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "seamless-through-breaking-rethinking-image-stitching-for-optimal-alignment_amd", "csrc")
-FLAGS = {"geom.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"], "composition.hip": ["-ffp-contract=off"], "tps_pipeline.hip": ["-ffp-contract=off"]}
+FLAGS = {"geom.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"], "composition.hip": ["-ffp-contract=off"], "tps_pipeline.hip": ["-ffp-contract=off"], "inpaint.hip": ["-ffp-contract=off"]}
 
 def summarize(path):
     name = os.path.basename(path)
