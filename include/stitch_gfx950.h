@@ -76,7 +76,8 @@ typedef struct st_gemm_desc {
                               producing kernel's epilogue), each blocked by 32-channel chunks: plane = [C / 32][rows][32] bf16, the planes
                               a_plane_stride / w_plane_stride ELEMENTS apart; a_rows = rows per chunk of the A planes (all pixels B*H*W of the
                               activation, >= what the geometry addresses), w_rows = rows per chunk of the W planes (>= N; W chunks follow the
-                              K order (ky, kx, c / 32)).  ldx / ldw are ignored; batch strides are bf16 elements inside each plane.  The six
+                              K order (ky, kx, c / 32)).  ldx / ldw are ignored; batch strides are bf16 elements inside each plane, whole rows (multiples of
+                              32), and with batch > 1 the last batch's rows must end inside a_rows / w_rows.  The six
                               products hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi are accumulated in fp32 (dropped terms <= 2^-23 |a||b|);
                               epilogue, split-K and outputs exactly as the fp32 kernels.  Cin % 32 == 0; tile_cfg 0 = auto, 31: 128x128,
                               32: 128x64, 33: 64x128, 34: 64x64, 37: 64x64 PERSISTENT walk over the tiles (many short tiles; the only one that

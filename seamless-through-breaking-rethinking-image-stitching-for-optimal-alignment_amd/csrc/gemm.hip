@@ -2202,6 +2202,12 @@ static int split3_prepare(const st_gemm_desc* desc, st_gemm_desc& d) {
                            (int64_t)d.Ho * d.Wo == d.M;
     const int64_t nimg = d.M / ((int64_t)d.Ho * d.Wo), in_rows = plain_mat ? d.M : nimg * d.H * d.W;
     if (in_rows > d.a_rows) return ST_EINVAL;
+    // batch b reads rows b * batch_stride / 32 onwards of every chunk (the kernels shift the base, not the buffer extents): the last batch's
+    // planes must end inside the caller's
+    if (d.batch > 1 && (d.batch_stride_a < 0 || d.batch_stride_w < 0 || (d.batch_stride_a & 31) || (d.batch_stride_w & 31) ||
+                        (int64_t)(d.batch - 1) * (d.batch_stride_a / 32) + in_rows > d.a_rows ||
+                        (int64_t)(d.batch - 1) * (d.batch_stride_w / 32) + d.N > d.w_rows))
+        return ST_EINVAL;
     // extents (bytes) from the plane-0 base to the end of plane 2; the 32-bit buffer offsets and the out-of-range sentinel need < 2 GiB
     const int64_t ab = 2 * (2 * d.a_plane_stride + (int64_t)(d.Cin / 32) * d.a_rows * 32);
     const int64_t wb = 2 * (2 * d.w_plane_stride + (int64_t)(d.K / 32) * d.w_rows * 32);

@@ -281,7 +281,11 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc[i][j] = acc[i][j] + tot[i][j];
         }
-        // the ring is dead (every DMA has landed, every fragment read has returned before the last barrier): the second group's partial tiles cross it
+        // The second group's partial tiles cross the ring, over the start of stage 0.  Every DMA has landed, but the fragments of the LAST step
+        // were requested after the last barrier of the loop (by the previous step's products; for ntiles == 1 right behind the first barrier), and
+        // when ntiles % STAGES == 1 they sit in stage 0: every consumer wave of both groups must have them back before group 1 overwrites it.
+        // (The loader waves have left: the barrier counts the waves that are still alive.)
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         float* const red = reinterpret_cast<float*>(sm) + (size_t)cw * (TM * TN * 16 * 64) + lane;
         if (grp == 1) {
 #pragma unroll
@@ -291,7 +295,7 @@ __device__ __forceinline__ void conv_gemm_split3_body(const st_gemm_desc& d, con
 #pragma unroll
                     for (int r = 0; r < 16; ++r) red[((i * TN + j) * 16 + r) * 64] = acc[i][j][r];
         }
-        __syncthreads();                                        // (the loader waves have left: the barrier counts the waves that are still alive)
+        __syncthreads();                                        // (consumer waves only, as above)
         if (grp == 1) return;
 #pragma unroll
         for (int i = 0; i < TM; ++i)

@@ -214,6 +214,13 @@ def conv_gemm(x, w, out, *, geom=None, bias=None, act="none", alpha=1.0, aux0=No
     return out
 
 
+def gemm_last_plan():
+    """[kernel family, tile_cfg, split_k, walk / pair flag] of this thread's last st_conv_gemm (st_gemm_last_plan, include/stitch_gfx950.h)"""
+    p = (C.c_int32 * 4)()
+    check(lib.st_gemm_last_plan(p), "st_gemm_last_plan")
+    return list(p)
+
+
 def conv_gemm_pair(call0, call1):
     """Two independent conv_gemm calls as ONE launch (st_conv_gemm_pair): each argument is (x, w, out, kwargs)."""
     d0 = conv_gemm(call0[0], call0[1], call0[2], _desc_only=True, **call0[3])

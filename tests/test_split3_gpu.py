@@ -242,6 +242,27 @@ def test_split3_rejects_what_it_cannot_run(ops):
         ops.conv_gemm(xp, wp, out, tile=13)                   # an fp32-kernel tile
     with pytest.raises(ops.StitchErrorBase):                      # planes of a result whose rows are not whole 32-row tiles
         ops.conv_gemm(dev(torch.randn(40, 64)), dev(torch.randn(32, 64)), torch.empty(40, 32, device="cuda"), out_planes=ops.Planes(40, 32, "cuda"))
+    # batched planes: the last batch's rows must lie inside the planes, batch strides whole rows.  The short views are carved from taller
+    # allocations (one 32-channel chunk each), so even a library without the check reads only memory this test owns.
+    Bb, M, N = 3, 64, 32
+    tall_a, tall_w = ops.Planes(256, 32, "cuda"), ops.Planes(128, 32, "cuda")
+    tall_a.t.zero_()
+    tall_w.t.zero_()
+
+    def rows(tall, n):
+        return ops.Planes(n, 32, None, t=tall.t[:, :, :n])
+
+    ob = torch.empty(Bb * M, N, device="cuda")
+    kw = dict(M=M, N=N, batch=Bb, bsc=M * N)
+    ops.conv_gemm(rows(tall_a, Bb * M), rows(tall_w, Bb * N), ob[:M], bsa=M * 32, bsw=N * 32, **kw)          # exact fit: accepted
+    torch.cuda.synchronize()
+    assert bool((ob == 0).all())
+    for a_rows, w_rows, bsa, bsw in [(Bb * M - 1, Bb * N, M * 32, N * 32),           # A one row short for the last batch
+                                     (Bb * M, Bb * N - 1, M * 32, N * 32),           # W one row short
+                                     (256, 128, M * 32 + 8, N * 32),                 # batch strides that are not whole rows
+                                     (256, 128, M * 32, N * 32 + 8)]:
+        with pytest.raises(ops.StitchErrorBase):
+            ops.conv_gemm(rows(tall_a, a_rows), rows(tall_w, w_rows), ob[:M], bsa=bsa, bsw=bsw, **kw)
 
 
 def test_split3_kernels_do_not_corrupt_their_neighbours(ops):
