@@ -552,6 +552,27 @@ int st_inpaint_telea_rings(const uint8_t* img_hwc, const uint8_t* mask_u8, int32
 int st_inpaint_telea_fill(const int32_t* ring_counts_host, int32_t nrings, int32_t h, int32_t w, int32_t radius, void* work,
                           int64_t work_bytes, uint8_t* out_hwc, int32_t* d_out, float* T_out, void* stream);
 
+/* ---- tps_method "other" of the post-pipeline (core/inference/tps_methods/other_tps.py, tps_pipline.py:405-421): per-axis
+ *      r^2 ln(r + 1e-6) splines in normalised coordinates and cv2.remap INTER_CUBIC in 8U fixed point (contract in README.md,
+ *      CPU restatement tests/_other_tps_ref.py) ----------------------------------------------------------------------- */
+/* fit of the two splines f(sites_i) = delta_i (sites = c_dst, delta = c_src - c_dst, both [n,2] float32, 3 <= n <= 4096):
+ * [[K, P], [P^T, 0]] theta = [delta; 0], K_ij = U(|sites_i - sites_j|), U(r) = r^2 ln(r + 1e-6), P = [1, x, y], in fp64 ->
+ * kernel_w [n,2], affine_w [3,2] float32.  work_f64: (n+3)*(n+6) doubles.  status (device int32, required): 0, or 1 when a
+ * pivot collapsed to rounding level (coincident or collinear sites).                                                      */
+int st_tps_other_solve(const float* sites, const float* delta, void* work_f64, float* kernel_w, float* affine_w, int32_t n,
+                       int32_t* status, void* stream);
+/* remap maps [h,w] float32 of the fitted splines (centers = sites [n,2], 1 <= n <= 4096): on the numpy.linspace(0, 1) float32
+ * grid x_j, y_i, dx = a0 + a1 x + a2 y + sum_k U(r_k) w_k in fp64 (index order, w_0 replaced by numpy's float32
+ * -np.sum(w_1..w_{n-1}): kernel_w[0] is ignored), mapx = float32((x + dx) * w), mapy = float32((y + dy) * h).              */
+int st_tps_other_maps(const float* centers, const float* kernel_w, const float* affine_w, int32_t n, int32_t h, int32_t w,
+                      float* mapx, float* mapy, void* stream);
+/* cv2.remap(src, mapx, mapy, INTER_CUBIC) with BORDER_CONSTANT 0 on uint8 data: src [planes,src_h,src_w] float32, each value
+ * truncated toward zero and clamped to 0..255 on load; maps [h,w]; out [planes,h,w] float32 holding 0..255.  table: the
+ * int16 [1024,16] coefficient table of ops.cubic_remap_table() in device memory, 16-byte aligned.  planes 1..64, src sides
+ * 1..32760.                                                                                                              */
+int st_remap_cubic_u8(const float* src, int32_t planes, int32_t src_h, int32_t src_w, const float* mapx, const float* mapy,
+                      int32_t h, int32_t w, const int16_t* table, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,10 @@
         if (e__ != hipSuccess) return (int)e__;   \
     } while (0)
 
+// a float sample as the reference's `to_pillow_fn` (`.to(torch.uint8)`) hands it to cv2: truncated toward zero, clamped to 0..255
+// (the TPS branches that warp uint8 data: tps2_warp_kernel mode 3, tps_other.hip)
+__device__ __forceinline__ float st_u8_trunc(float v) { return fminf(fmaxf(truncf(v), 0.f), 255.f); }
+
 // epilogue activations
 enum { ST_ACT_NONE = 0, ST_ACT_RELU = 1, ST_ACT_GELU = 2, ST_ACT_SIGMOID = 3, ST_ACT_TANH = 4 };
 // epilogue combine modes (v = act(alpha*acc + bias))

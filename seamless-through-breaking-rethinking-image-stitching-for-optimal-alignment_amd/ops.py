@@ -975,3 +975,117 @@ def inpaint_disc_size(radius=64):
     """number of offsets 0 < |r| <= radius one filled pixel gathers over"""
     from math import isqrt
     return sum(2 * isqrt(radius * radius - y * y) + 1 for y in range(-radius, radius + 1)) - 1
+
+
+# ---- tps_method="other" (csrc/tps_other.hip) -----------------------------------------------------
+REMAP_MAX_SIDE = 32760          # cv2.remap keeps tap coordinates in int16: a source side past this is not restated
+
+
+def cubic_remap_table():
+    """cv2.remap's INTER_CUBIC 8U coefficient table (OpenCV initInterTab2D(INTER_CUBIC, fixpt=true)), int16 [32*32, 16]: row
+    fy*32 + fx, entry k1*4 + k2 = weight of tap (sy-1+k1, sx-1+k2) in units of 2^-15.  The one place the table is built: the
+    device upload and the test restatement both call it.  Not checked against OpenCV itself (not importable here)."""
+    import numpy as np
+    f32 = np.float32
+    A = f32(-0.75)
+    t = (np.arange(32, dtype=f32) * f32(1.0 / 32)).astype(f32)
+    one = f32(1)
+    c0 = ((A * (t + one) - f32(5) * A) * (t + one) + f32(8) * A) * (t + one) - f32(4) * A
+    c1 = ((A + f32(2)) * t - (A + f32(3))) * t * t + one
+    c2 = ((A + f32(2)) * (one - t) - (A + f32(3))) * (one - t) * (one - t) + one
+    c3 = one - c0 - c1 - c2
+    c = np.stack([c0, c1, c2, c3], 1).astype(f32)                                  # [32 fractions, 4 taps]
+    prod = (c[:, None, :, None] * c[None, :, None, :]).astype(f32)                # [fy, fx, k1, k2] = cy[k1] * cx[k2] in fp32
+    # cvRound (half to even) saturated to int16: fraction (0, 0) has cy[1] * cx[1] = 1 -> 32767, and the correction below puts the
+    # missing 1 on tap (2, 2) (a copy stays exact: 32767 v + v' + 2^14 >> 15 == v for |v' - v| <= 255)
+    tab = np.clip(np.rint(prod * f32(32768)), -32768, 32767).astype(np.int32).reshape(32 * 32, 16)
+    for row in tab:
+        diff = int(row.sum()) - 32768
+        if diff == 0:
+            continue
+        mk = Mk = 2 * 4 + 2                                                        # scan the centre 2 x 2 from (2, 2)
+        for k1 in (2, 3):
+            for k2 in (2, 3):
+                k = k1 * 4 + k2
+                if row[k] < row[mk]:
+                    mk = k
+                elif row[k] > row[Mk]:
+                    Mk = k
+        if diff < 0:
+            row[Mk] -= diff
+        else:
+            row[mk] -= diff
+    return tab.astype(np.int16)
+
+
+_REMAP_TABLES = {}
+
+
+def _remap_table(dev):
+    """cubic_remap_table() uploaded once per device"""
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _REMAP_TABLES:
+        _REMAP_TABLES[key] = torch.from_numpy(cubic_remap_table()).to(dev).contiguous()
+    return _REMAP_TABLES[key]
+
+
+def tps_other_solve(c_src, c_dst):
+    """the two splines of tps_method="other": f(c_dst_i) = c_src_i - c_dst_i (float32 [n,2] each, normalised coordinates),
+    U(r) = r^2 ln(r + 1e-6), solved in fp64 -> (kernel_w [n,2], affine_w [3,2]) float32.  Raises SingularTPSError."""
+    n = c_dst.shape[0]
+    dev = c_dst.device
+    sites = c_dst.float().contiguous()
+    delta = (c_src.float().to(dev) - sites).contiguous()                  # float32, as the reference subtracts
+    work = torch.empty(((n + 3) * (n + 6),), device=dev, dtype=torch.float64)
+    kw = torch.empty((n, 2), device=dev, dtype=torch.float32)
+    aw = torch.empty((3, 2), device=dev, dtype=torch.float32)
+    status = torch.zeros((1,), device=dev, dtype=torch.int32)
+    check(lib.st_tps_other_solve(_pc(sites), _pc(delta), _p(work), _p(kw), _p(aw), n, _p(status), _stream()), "st_tps_other_solve")
+    if int(status.item()):
+        raise SingularTPSError(f"singular TPS system: {n} control points with collinear sites")
+    return kw, aw
+
+
+def tps_other_maps(points_src, points_dst, H, W, weights=None):
+    """cv2.remap maps (mapx, mapy) float32 [H,W] of tps_method="other" (other_tps.py tps_theta_from_points / tps_grid /
+    tps_grid_to_remap) for float32 normalised points [n,2] on the same device.  Coincident points_dst keep their first occurrence.
+    weights: (kernel_w [n,2], affine_w [3,2]) to use instead of the fit (kernel_w[0] is replaced by the reduced form)."""
+    dev = points_dst.device
+    c_src, c_dst = points_src.float().to(dev), points_dst.float()
+    if weights is None:
+        import numpy as np
+        _, first = np.unique(c_dst.cpu().numpy(), axis=0, return_index=True)
+        if len(first) < c_dst.shape[0]:
+            keep = torch.from_numpy(np.sort(first)).to(dev)
+            c_src, c_dst = c_src[keep], c_dst[keep]
+        if c_dst.shape[0] < 3:
+            raise SingularTPSError(f"singular TPS system: {c_dst.shape[0]} distinct control points")
+        weights = tps_other_solve(c_src, c_dst)
+    kw, aw = (w.float().contiguous().to(dev) for w in weights)
+    c_dst = c_dst.contiguous()
+    mapx = torch.empty((H, W), device=dev, dtype=torch.float32)
+    mapy = torch.empty((H, W), device=dev, dtype=torch.float32)
+    check(lib.st_tps_other_maps(_pc(c_dst), _pc(kw), _pc(aw), c_dst.shape[0], H, W, _p(mapx), _p(mapy), _stream()), "st_tps_other_maps")
+    return mapx, mapy
+
+
+def remap_cubic(planes, mapx, mapy):
+    """cv2.remap(INTER_CUBIC, BORDER_CONSTANT 0) of the uint8 image the planes truncate to: planes float32 [P,Hs,Ws] (or
+    [1,P,Hs,Ws]), maps float32 [H,W] -> float32 [P,H,W] (or [1,P,H,W]) holding 0..255."""
+    batched = planes.dim() == 4
+    if batched:
+        if planes.shape[0] != 1:
+            raise ValueError(f"batch 1 expected, got {tuple(planes.shape)}")
+        planes = planes[0]
+    if planes.dim() != 3 or planes.dtype != torch.float32:
+        raise ValueError(f"float32 [P,H,W] planes expected, got {planes.dtype} {tuple(planes.shape)}")
+    if mapx.shape != mapy.shape or mapx.dim() != 2 or mapx.dtype != torch.float32 or mapy.dtype != torch.float32:
+        raise ValueError(f"float32 [H,W] maps expected, got {tuple(mapx.shape)} / {tuple(mapy.shape)}")
+    if mapx.device != planes.device or mapy.device != planes.device:
+        raise ValueError("planes and maps must be on the same device")
+    P, Hs, Ws = planes.shape
+    H, W = mapx.shape
+    out = torch.empty((P, H, W), device=planes.device, dtype=torch.float32)
+    check(lib.st_remap_cubic_u8(_pc(planes), P, Hs, Ws, _pc(mapx), _pc(mapy), H, W, _p(_remap_table(planes.device)), _p(out), _stream()),
+          "st_remap_cubic_u8")
+    return out[None] if batched else out

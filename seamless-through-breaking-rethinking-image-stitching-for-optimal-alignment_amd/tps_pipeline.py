@@ -11,7 +11,9 @@ Same call signature and result keys.  What runs where:
 Back-ends: ``tps_method="kornia"`` is the reference's in-tree back-end (pinned by tests/golden/tps_pipeline.npz).
 ``tps_method="opencv"`` (the shipped default) is served by the same kernels in pixel units: the exact r^2 log r^2
 interpolating spline that OpenCV's ThinPlateSplineShapeTransformer fits, sampled bilinearly -- OpenCV itself is not
-installable here, so that path is UNPINNED against OpenCV.  ``"other"`` and the neural inpainters are out of
+installable here, so that path is UNPINNED against OpenCV.  ``tps_method="other"`` restates the reference's
+other_tps.py: two per-axis r^2 ln(r + 1e-6) splines (fp64 fit and maps) and cv2.remap INTER_CUBIC in OpenCV's 8U fixed point
+(README.md, "tps_method other"; the coefficient table is unpinned against OpenCV).  The neural inpainters are out of
 scope.  ``inpaint_fn`` is the reference's ``mix_fn`` plug-in hook (out.py:235-236): `stitch_amd.mix_methods.<name>.mix_fn`
 restates both shipped mix methods on the GPU and takes any object with the reference's inpainter protocol.
 """
@@ -158,6 +160,14 @@ def sample_init_points(residual_flow, out_height, out_width, width_min, height_m
     return src, tgt, sh(src), sh(tgt)
 
 
+def _normalised(points_src, points_dst, out_height, out_width):
+    """pixel points -> float32 (x / out_width, y / out_height), divided in float64 (tps_pipline.py:362-368, :407-415)"""
+    ps, pd = points_src.to(torch.float64), points_dst.to(torch.float64)
+    ps = torch.stack([ps[:, :, 0] / out_width, ps[:, :, 1] / out_height], 2).to(torch.float32)
+    pd = torch.stack([pd[:, :, 0] / out_width, pd[:, :, 1] / out_height], 2).to(torch.float32)
+    return ps, pd
+
+
 def warp_by_tps(H_warp, H_warp_mask, points_src, points_dst, out_height, out_width, tps_method, kernel_scale, affine_scale,
                 is_plot=False):
     """tps_pipline.py:339-426 -> warped [1, 3 + C_mask, h, w] on the GPU."""
@@ -169,9 +179,7 @@ def warp_by_tps(H_warp, H_warp_mask, points_src, points_dst, out_height, out_wid
         return x
     try:
         if tps_method == "kornia":
-            ps, pd = points_src.to(torch.float64), points_dst.to(torch.float64)
-            ps = torch.stack([ps[:, :, 0] / out_width, ps[:, :, 1] / out_height], 2).to(torch.float32)
-            pd = torch.stack([pd[:, :, 0] / out_width, pd[:, :, 1] / out_height], 2).to(torch.float32)
+            ps, pd = _normalised(points_src, points_dst, out_height, out_width)
             return ops.tps2_warp(x, pd[0], ps[0], kernel_scale, affine_scale, mode=0)      # get_tps_transform(dst, src), centres = src
         if tps_method == "opencv":
             # tensor2WarpImage_TPS (opencv_tps.py): `to_pillow_fn` truncates image AND mask to uint8 before cv2 sees them (a
@@ -184,12 +192,20 @@ def warp_by_tps(H_warp, H_warp_mask, points_src, points_dst, out_height, out_wid
                 keep = torch.from_numpy(np.sort(first))
                 a, b = a[keep], b[keep]
             return ops.tps2_warp(x, a, b, 1.0, 1.0, mode=3)
+        if tps_method == "other":
+            # tensor2_warp_image_cv (other_tps.py) on the points normalised as above, c_src = ps[0], c_dst = pd[0]: per-axis
+            # r^2 ln(r + 1e-6) splines, remap maps on the float32 linspace grid scaled by W and H (not W-1, H-1: the reference's
+            # own mismatch, kept), cv2.remap INTER_CUBIC of the uint8-truncated image and mask.  kernel_scale / affine_scale are
+            # not used on this branch.  Coincident sites keep their first occurrence (ops.tps_other_maps).
+            ps, pd = _normalised(points_src, points_dst, out_height, out_width)
+            mapx, mapy = ops.tps_other_maps(ps[0].to(x.device), pd[0].to(x.device), x.shape[-2], x.shape[-1])
+            return ops.remap_cubic(x, mapx, mapy)
     except ops.SingularTPSError as e:
         # the reference's solvers raise (kornia: torch.linalg.solve) or return garbage (cv2) on a singular system; a NaN canvas
         # would silently blank the blend, so leave the homography warp as it is and say so
         print(f"[tps_pipeline] {e}: TPS warp skipped (identity)")
         return x
-    raise NotImplementedError(f"tps_method={tps_method!r}: only 'kornia' (pinned) and 'opencv' (native pixel-unit spline) are built")
+    raise NotImplementedError(f"tps_method={tps_method!r}: the back-ends are 'kornia', 'opencv' and 'other'")
 
 
 def tps_H_warp(inputs, image_limit, tps_pipeline_config, inpaint_fn=None, is_plot=False):

@@ -32,7 +32,7 @@ def run(tps_method):
     ev[3].record(); torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     return [ev[i].elapsed_time(ev[i + 1]) for i in range(3)], wall, new["points_src"].shape[1], (out["out_height"], out["out_width"])
-for m in ("kornia", "opencv"):
+for m in ("kornia", "opencv", "other"):
     run(m)
     ts, wall, n, canvas = run(m)
     print(f"tps_method={m}: canvas {canvas}, {n} control points: forward {ts[0]:.2f} ms, post-pipeline {ts[1]:.2f} ms, composition {ts[2]:.2f} ms; wall {1e3*wall:.1f} ms")
@@ -42,7 +42,7 @@ from types import SimpleNamespace
 from oracle import tps_pipeline as otp
 case = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in otp.synthetic_case(5, 512, 544, -21, -13, 548, 588).items()}
 limit = dict(width_min=-21, height_min=-13, out_height=548, out_width=588)
-for m in ("kornia", "opencv"):
+for m in ("kornia", "opencv", "other"):
     tpc.tps_method = m
     for rep in range(2):
         torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -50,5 +50,43 @@ for m in ("kornia", "opencv"):
         torch.cuda.synchronize(); dt = time.perf_counter() - t0
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     pts_a, pts_b = new["points_dst"][0].float().cuda(), new["points_src"][0].float().cuda()
-    e0.record(); stitch_amd.ops.tps2_solve(pts_a, pts_b if m == "kornia" else pts_a, pts_b, mode=0 if m == "kornia" else 1); e1.record(); torch.cuda.synchronize()
+    e0.record()
+    if m == "other":
+        stitch_amd.ops.tps_other_solve(pts_b / torch.tensor([588.0, 548.0], device="cuda"), pts_a / torch.tensor([588.0, 548.0], device="cuda"))
+    else:
+        stitch_amd.ops.tps2_solve(pts_a, pts_b if m == "kornia" else pts_a, pts_b, mode=0 if m == "kornia" else 1)
+    e1.record(); torch.cuda.synchronize()
     print(f"synthetic 548x588 canvas, tps_method={m}: {new['points_src'].shape[1]} control points, tps_H_warp + mix_fn wall {1e3*dt:.2f} ms (TPS solve alone {e0.elapsed_time(e1):.2f} ms)")
+
+# warp_by_tps alone, "opencv" (pixel-unit spline sampled bilinearly, mode 3) next to "other" (per-axis splines, fp64 maps, bicubic
+# remap): on the synthetic canvas above and on the 533 x 567 chain canvas with its 101 control points (tests/golden/tps_illcond_points.npz)
+import os
+import numpy as np
+def time_warp(m, Hw, Hm, ps, pd, oh, ow, reps=20):
+    for _ in range(3):
+        stitch_amd.tps_pipeline.warp_by_tps(Hw, Hm, ps, pd, oh, ow, m, 1.0, 1.0)
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        stitch_amd.tps_pipeline.warp_by_tps(Hw, Hm, ps, pd, oh, ow, m, 1.0, 1.0)
+        torch.cuda.synchronize(); ts.append(time.perf_counter() - t0)
+    return 1e3 * float(np.median(ts))
+ch = np.load(os.path.join(__file__.rsplit("/tools/", 1)[0], "tests", "golden", "tps_illcond_points.npz"))
+coh, cow = (int(v) for v in ch["out_hw"])
+chain = otp.synthetic_case(3, 512, 512, -(cow - 512) // 2, -(coh - 512) // 2, coh, cow)
+cases = [("synthetic 548x588", case["H_warp"], case["H_warp_mask"], new["points_src"], new["points_dst"], 548, 588),
+         (f"chain {coh}x{cow}", chain["H_warp"].cuda(), chain["H_warp_mask"].cuda(), torch.from_numpy(ch["points_src"]),
+          torch.from_numpy(ch["points_dst"]), coh, cow)]
+for label, Hw, Hm, ps, pd, oh, ow in cases:
+    line = [f"{m} {time_warp(m, Hw, Hm, ps, pd, oh, ow):.3f} ms" for m in ("opencv", "other")]
+    # the two "other" kernels alone (HIP events, weights fitted once)
+    cs = torch.stack([ps[0, :, 0].double() / ow, ps[0, :, 1].double() / oh], 1).float().cuda()
+    cd = torch.stack([pd[0, :, 0].double() / ow, pd[0, :, 1].double() / oh], 1).float().cuda()
+    w = stitch_amd.ops.tps_other_solve(cs, cd)
+    x = torch.cat((Hw, Hm), 1).float().contiguous()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    for rep in range(5):
+        ev[0].record(); mx, my = stitch_amd.ops.tps_other_maps(cs, cd, oh, ow, weights=w); ev[1].record()
+        stitch_amd.ops.remap_cubic(x, mx, my); ev[2].record(); torch.cuda.synchronize()
+    print(f"warp_by_tps {label}, {ps.shape[1]} control points (median of 20, wall incl. host sync): " + ", ".join(line)
+          + f"; other kernels: maps {ev[0].elapsed_time(ev[1]):.3f} ms, remap {ev[1].elapsed_time(ev[2]):.3f} ms")
