@@ -35,7 +35,7 @@ typedef struct st_gemm_desc {
     int32_t kh, kw, sh, sw, ph, pw, Ho, Wo;
     int32_t ldw, ldc, ld_aux0, ld_aux1, ld_aux2;
     int32_t aux0_row_div, aux0_row_mod;   /* 0/1 = identity row mapping                            */
-    int32_t act;           /* 0 none, 1 relu, 2 gelu(erf), 3 sigmoid, 4 tanh                        */
+    int32_t act;           /* 0 none, 1 relu, 2 gelu(erf), 3 sigmoid, 4 tanh, 5 leaky relu (0.01)   */
     int32_t epi;           /* 0 store, 1 +aux1, 2 *aux1, 3 GRU blend, 4 aux1 + *scale_ptr * v,
                               5 z|r: cols<N/2 -> c, cols>=N/2 -> c2 = v*aux1                        */
     float alpha;           /* v = act(alpha*acc + bias + aux0)                                      */
@@ -572,6 +572,34 @@ int st_tps_other_maps(const float* centers, const float* kernel_w, const float* 
  * 1..32760.                                                                                                              */
 int st_remap_cubic_u8(const float* src, int32_t planes, int32_t src_h, int32_t src_w, const float* mapx, const float* mapy,
                       int32_t h, int32_t w, const int16_t* table, float* out, void* stream);
+
+/* ---- TransRef inpainter (core/inference/mix_methods/utils/transref_inpainter.py, TransRef/models/*.py; csrc/transref.hip) -------- */
+/* softmax(scale Q K^T) V per head, flash style on the fp32 matrix cores: q [Nq, ldq], k [Nk, ldk], v [Nk, ldv], out [Nq, ldo] row-major,
+ * head h in columns [h D, (h + 1) D).  D in {32, 64, 80, 128, 160, 256}, any Nq, Nk >= 1.  q and k 16-byte aligned, ldq and ldk
+ * multiples of 4.                                                                                                                 */
+int st_tr_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out, int64_t ldo,
+                    int32_t heads, int32_t Nq, int32_t Nk, int32_t D, float scale, void* stream);
+/* mmcv DeformConv2d 3x3 / pad 1 / one deformable group, sampling part: x channels-last [H W, ldx], off [H W, ldoff] (channel 2k = dy,
+ * 2k + 1 = dx of tap k = 3 ky + kx) -> cols [H W, 9 C] ((ky, kx, c) order, for a plain-matrix st_conv_gemm).                       */
+int st_tr_deform_im2col(const float* x, int64_t ldx, const float* off, int64_t ldoff, float* cols, int32_t H, int32_t W, int32_t C,
+                        void* stream);
+/* stride-2 transposed convolution, last step: phases [4, H W, C] (phase 2 py + px) -> out [(2H)(2W), ldo] (+ res, row stride ldr).  */
+int st_tr_phase_interleave(const float* phases, float* out, int64_t ldo, const float* res, int64_t ldr, int32_t H, int32_t W, int32_t C,
+                           void* stream);
+/* out = GELU(erf)(depthwise 3x3 pad 1 conv of x + bias): x / out channels-last [H W, ld], w9c [9, C] (tap-major).                    */
+int st_tr_dwconv3x3_gelu(const float* x, int64_t ldx, const float* w9c, const float* bias, float* out, int64_t ldo, int32_t H, int32_t W,
+                         int32_t C, void* stream);
+/* out = a + b over [rows, C] row-major views.                                                                                      */
+int st_tr_add(const float* a, int64_t lda, const float* b, int64_t ldb, float* out, int64_t ldo, int64_t rows, int32_t C, void* stream);
+/* wrapper, steps 1-2: img3 / ctl3 [3, hw] -> out6 [6, hw] = ((trunc-clamp-u8(x) / 255) - 0.5) / 0.5.                              */
+int st_tr_prep(const float* img3, const float* ctl3, float* out6, int64_t hw, void* stream);
+/* steps 4-6: rs6 [6, n] (resized out6), mask [n] (resized mask plane 0) -> x6 [n, 6] (hole fill, 1 - byte mask), ref3 [n, 3],
+ * detail3 [3, n].                                                                                                                 */
+int st_tr_pack(const float* rs6, const float* mask, float* x6, float* ref3, float* detail3, int64_t n, void* stream);
+/* step 7: fake3 [3, n] = out3 [n, 3] * mask + detail3 * (1 - mask), mask [mask_planes (1 or 3), n].                               */
+int st_tr_blend(const float* out3, const float* detail3, const float* mask, int32_t mask_planes, float* fake3, int64_t n, void* stream);
+/* step 8: uint8 (x * 127.5 + 127.5).round() clamped to 0..255.                                                                   */
+int st_tr_to_u8(const float* x, uint8_t* out, int64_t n, void* stream);
 
 #ifdef __cplusplus
 }

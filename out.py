@@ -7,8 +7,10 @@ Same flags, `demo.txt` pair list (one directory per line holding input1.jpg / in
 result-directory naming as the reference.  The forward (`type="test_out"`) and the TPS post-pipeline
 (core/inference/tps_pipline.py, `stitch_amd.tps_pipeline`) run on the HIP kernels; the composition stage (out.py:277-312,
 `cfg.use_composition`) runs on the post-TPS canvases.  The `mix_fn` plug-in named by `TPS_PIPELINE_CONFIG.mix_method` runs too
-(`stitch_amd.mix_methods`).  Differences from the reference's files: the neural inpainters inside `mix_fn` (TransRef /
-diffusion: fetched weights + third-party CUDA ops) are out of scope and replaced by a pass-through, so with the shipped configs in
+(`stitch_amd.mix_methods`).  Differences from the reference's files: the shipped configs name `transref_inpainter`, the TransRef
+network on the GPU (`stitch_amd.transref`), whose module loads the reference's `400_Trans.pth` from
+`stitch_amd/mix_methods/utils/TransRef/`; that checkpoint is not in the tree, and without it (or with the diffusion inpainter, out
+of scope) a pass-through stands in, so with the shipped configs in
 `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg`, `composition.jpg`, `learned_mask*.jpg` the thin border `mix_fn` leaves to the inpainter
 is not synthesised (with `inpaint_all_area`: no hole is); `--inf_cfg all_img1_with_inpaint_g12_cv` / `inpaint_all_area_g12_cv`
 select `cv_inpainter`, the reference's OpenCV Telea inpainter restated as GPU kernels (README.md; unpinned against OpenCV), which
@@ -123,9 +125,9 @@ class _Saver:
 @torch.no_grad()
 def load_inpainter(name):
     """out.py:341-346: `core.inference.mix_methods.utils.<name>.inpainter`.  `cv_inpainter` (the reference's OpenCV Telea
-    inpainter, GPU kernels here) is shipped; the neural ones (TransRef, diffusion) need fetched weights and third-party CUDA ops and
-    are out of scope; a module of that name dropped into `stitch_amd/mix_methods/utils/` is picked up, otherwise the pass-through
-    stand-in is used."""
+    inpainter, GPU kernels here) is shipped; `transref_inpainter` (the TransRef network, GPU kernels) is shipped but its module needs
+    the reference's checkpoint `mix_methods/utils/TransRef/400_Trans.pth` and raises ImportError without it; the diffusion inpainter
+    is out of scope.  A module that cannot be imported falls back to the pass-through stand-in."""
     import importlib
     try:
         return importlib.import_module(f"stitch_amd.mix_methods.utils.{name}").inpainter
@@ -136,9 +138,9 @@ def load_inpainter(name):
 
 
 def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_model=None, inpainter=None, forward=None, saver=None):
-    """out.py:158-312: forward (`test_out`), TPS post-pipeline with the configured `mix_fn`, saves, composition.  The neural
-    inpainters the reference calls inside `mix_fn` are out of scope (pass-through stand-in unless the config names
-    `cv_inpainter` or the caller supplies one): with the stand-in, in `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the
+    """out.py:158-312: forward (`test_out`), TPS post-pipeline with the configured `mix_fn`, saves, composition.  The inpainter
+    is the caller's, else the pass-through stand-in (`load_inpainter`: `transref_inpainter` needs its checkpoint, the diffusion one is
+    out of scope): with the stand-in, in `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the
     composition inputs the holes hold what `mix_fn` fills from image 1 and the thin border region it hands to the inpainter is not
     synthesised; `cv_inpainter` (GPU Telea inpainting, unpinned against OpenCV) fills it.
 

@@ -17,7 +17,7 @@
 __device__ __forceinline__ float st_u8_trunc(float v) { return fminf(fmaxf(truncf(v), 0.f), 255.f); }
 
 // epilogue activations
-enum { ST_ACT_NONE = 0, ST_ACT_RELU = 1, ST_ACT_GELU = 2, ST_ACT_SIGMOID = 3, ST_ACT_TANH = 4 };
+enum { ST_ACT_NONE = 0, ST_ACT_RELU = 1, ST_ACT_GELU = 2, ST_ACT_SIGMOID = 3, ST_ACT_TANH = 4, ST_ACT_LRELU = 5 };   // LRELU: nn.LeakyReLU(0.01)
 // epilogue combine modes (v = act(alpha*acc + bias))
 enum {
     ST_EPI_STORE = 0,     // out = v
@@ -72,6 +72,7 @@ __device__ __forceinline__ float st_act(float v, int act) {
         case ST_ACT_GELU: return st_gelu(v);
         case ST_ACT_SIGMOID: return st_sigmoid(v);
         case ST_ACT_TANH: return st_tanh(v);
+        case ST_ACT_LRELU: return v > 0.f ? v : v * 0.01f;
         default: return v;
     }
 }

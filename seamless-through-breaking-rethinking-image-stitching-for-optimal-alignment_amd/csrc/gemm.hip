@@ -293,6 +293,10 @@ __device__ __forceinline__ void gemm_epilogue_store(const st_gemm_desc& d, float
 #pragma unroll
                     for (int r = 0; r < 16; ++r) v[r] = st_act(v[r], ST_ACT_TANH);
                     break;
+                case ST_ACT_LRELU:
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) v[r] = st_act(v[r], ST_ACT_LRELU);
+                    break;
                 default: break;
             }
             // plane copy: byte offset of (this lane's first row, its channel) inside plane 0; a 32-row sub-tile is wholly inside M

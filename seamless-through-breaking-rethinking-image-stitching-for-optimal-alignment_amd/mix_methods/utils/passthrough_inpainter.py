@@ -1,5 +1,5 @@
-"""Stand-in for the reference's neural inpainters (core/inference/mix_methods/utils/{transref_,}inpainter.py: fetched
-weights and third-party CUDA ops, out of scope): same protocol, returns the control image (or the input) unchanged, so the
+"""Stand-in for the reference's neural inpainters (core/inference/mix_methods/utils/inpainter.py, diffusion: fetched weights, out
+of scope; transref_inpainter.py without its checkpoint): same protocol, returns the control image (or the input) unchanged, so the
 post-pipeline runs end to end and the holes keep what `mix_fn` filled from image 1."""
 
 

@@ -9,7 +9,7 @@ import torch
 from ._lib import ChainDesc, GemmDesc, MlpDesc, check, lib
 from ._lib import StitchError as StitchErrorBase
 
-ACT = dict(none=0, relu=1, gelu=2, sigmoid=3, tanh=4)
+ACT = dict(none=0, relu=1, gelu=2, sigmoid=3, tanh=4, lrelu=5)
 EPI = dict(store=0, add=1, mul=2, gru=3, axpy=4, zr=5)
 
 assert lib.st_abi_gemm_desc_size() == C.sizeof(GemmDesc), "st_gemm_desc ABI mismatch between header and binding"
@@ -1089,3 +1089,61 @@ def remap_cubic(planes, mapx, mapy):
     check(lib.st_remap_cubic_u8(_pc(planes), P, Hs, Ws, _pc(mapx), _pc(mapy), H, W, _p(_remap_table(planes.device)), _p(out), _stream()),
           "st_remap_cubic_u8")
     return out[None] if batched else out
+
+
+# ---- TransRef inpainter (mix_methods/utils/transref_inpainter.py, stitch_amd/transref.py) --------------------------------------
+TR_ATTENTION_D = (32, 64, 80, 128, 160, 256)
+
+
+def tr_attention(q, k, v, out, heads, D, scale):
+    """out[:, h D:(h+1) D] = softmax(scale q_h k_h^T) v_h for every head h (st_tr_attention): 2-D row-major views, last dim contiguous."""
+    check(lib.st_tr_attention(_p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(out), _ld(out), heads, q.shape[0], k.shape[0], D,
+                              float(scale), _stream()), "st_tr_attention")
+    return out
+
+
+def tr_deform_im2col(x, off, cols, H, W):
+    """mmcv DeformConv2d (3x3, pad 1) sampling: x [H W, C] view, off [H W, >=18] view -> cols [H W, 9 C] dense."""
+    Cc = x.shape[1]
+    assert cols.shape == (H * W, 9 * Cc) and cols.is_contiguous()
+    check(lib.st_tr_deform_im2col(_p(x), _ld(x), _p(off), _ld(off), _p(cols), H, W, Cc, _stream()), "st_tr_deform_im2col")
+    return cols
+
+
+def tr_phase_interleave(phases, out, H, W, res=None):
+    """phases [4, H W, C] dense -> out [(2H)(2W), C] view (+ res, same geometry)."""
+    Cc = phases.shape[-1]
+    assert phases.is_contiguous() and phases.numel() == 4 * H * W * Cc
+    check(lib.st_tr_phase_interleave(_p(phases), _p(out), _ld(out), _p(res), _ld(res) if res is not None else 0, H, W, Cc, _stream()),
+          "st_tr_phase_interleave")
+    return out
+
+
+def tr_dwconv3x3_gelu(x, w9c, bias, out, H, W):
+    check(lib.st_tr_dwconv3x3_gelu(_p(x), _ld(x), _pc(w9c), _pc(bias), _p(out), _ld(out), H, W, x.shape[1], _stream()),
+          "st_tr_dwconv3x3_gelu")
+    return out
+
+
+def tr_add(a, b, out):
+    check(lib.st_tr_add(_p(a), _ld(a), _p(b), _ld(b), _p(out), _ld(out), a.shape[0], a.shape[1], _stream()), "st_tr_add")
+    return out
+
+
+def tr_prep(img3, ctl3, out6):
+    check(lib.st_tr_prep(_pc(img3), _pc(ctl3), _pc(out6), img3[0].numel(), _stream()), "st_tr_prep")
+    return out6
+
+
+def tr_pack(rs6, mask0, x6, ref3, detail3):
+    check(lib.st_tr_pack(_pc(rs6), _pc(mask0), _pc(x6), _pc(ref3), _pc(detail3), mask0.numel(), _stream()), "st_tr_pack")
+
+
+def tr_blend(out3, detail3, mask, fake3):
+    check(lib.st_tr_blend(_pc(out3), _pc(detail3), _pc(mask), mask.shape[0], _pc(fake3), detail3[0].numel(), _stream()), "st_tr_blend")
+    return fake3
+
+
+def tr_to_u8(x, out):
+    check(lib.st_tr_to_u8(_pc(x), _pc(out), x.numel(), _stream()), "st_tr_to_u8")
+    return out
