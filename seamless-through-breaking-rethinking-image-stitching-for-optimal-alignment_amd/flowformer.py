@@ -49,6 +49,11 @@ def _new(rows, cols, dev, zero=False):
     return (torch.zeros if zero else torch.empty)((rows, cols), device=dev, dtype=torch.float32)
 
 
+def _planes_copy(p):
+    """a copy of a plane image (the trace hooks: the live one is overwritten by the next iteration)"""
+    return ops.Planes(p.rows, p.C, None, t=p.t.clone(), c0=p.c0, ncols=p.ncols)
+
+
 class FlowFormer(ParamTree):
     def __init__(self, cfg=None):
         super().__init__(flow_spec())
@@ -284,8 +289,9 @@ class FlowFormer(ParamTree):
         return o
 
     # ------------------------------------------------------------------ Twins-SVT-L stages 1-2
-    def _twins(self, t, x, B, H, W):
-        """encoders.py:21-40; x: prepped image rows [B*H*W, 4] -> feature rows [B*(H/8)*(W/8), 256]."""
+    def _twins(self, t, x, B, H, W, trace=None):
+        """encoders.py:21-40; x: prepped image rows [B*H*W, 4] -> feature rows [B*(H/8)*(W/8), 256].  trace (a list): one record per stage
+        with the rows after the patch embedding + LayerNorm, the LSA block, the PEG and the GSA block."""
         dev = x.device
         dims, heads, srs, patch = (128, 256), (4, 8), (8, 4), (4, 2)
         for s in range(2):
@@ -329,7 +335,11 @@ class FlowFormer(ParamTree):
             ops.conv_gemm(xsn, Gk["kv"][0], kv, bias=Gk["kv"][1])
             ops.attention_kvlds(q, (H * W * C, C), kv[:, :C], (Nk * 2 * C, 2 * C), kv[:, C:], (Nk * 2 * C, 2 * C), att,
                                 (H * W * C, C), B, hd, H * W, Nk, C // hd, (C // hd) ** -0.5)
+            if trace is not None:
+                trace.append(dict(H=H, W=W, pe=x.clone(), lsa=x2.clone(), peg=x3.clone()))
             x = self._mlp(None, Gk["n2"], Gk["fc1"], Gk["fc2"], 1e-6, fc1_ln=Gk.get("fc1_ln"), proj=(att, Gk["proj"], x3), image=Gk.get("mlp_s3"))
+            if trace is not None:
+                trace[-1]["gsa"] = x.clone()
         return x, H, W
 
     # ------------------------------------------------------------------ cost-volume encoder
@@ -495,19 +505,26 @@ class FlowFormer(ParamTree):
                                 att[sl], (C, nl * C), nl, 8, N, Nk, 16, 16 ** -0.5)
         return self._mlp(None, V["gn2"], V["gfc1"], V["gfc2"], 1e-5, fc1_ln=V["gfc1_ln"], extra_res=extra_res, proj=(att, V["gproj"], x2), image=V.get("gmlp_s3"))
 
-    def _cost_encoder(self, cost_maps, ctx, B, H1, W1):
-        """CostPerceiverEncoder.forward (encoder.py:258-287) -> cost memory rows [B*N*8, 128]."""
+    def _cost_encoder(self, cost_maps, ctx, B, H1, W1, trace=None):
+        """CostPerceiverEncoder.forward (encoder.py:258-287) -> cost memory rows [B*N*8, 128].  trace (a dict): the PatchEmbed tokens, the input
+        layer's output, and the output of every latent self layer and vertical layer."""
         pk = self._pk
         M = B * H1 * W1
         tokens, P = self._patch_embed(cost_maps, M, H1, W1)
         x = self._latent_layer(pk["xin"], None, M, True, tokens, P)
+        if trace is not None:
+            trace.update(tokens=tokens.clone(), latent_in=x.clone(), self=[], vert=[])
         short = x
         nl = pk["latents"].shape[0]
         for i in range(HP["encoder_depth"]):
             x = self._latent_layer(pk["self"][i], x, M, False)
+            if trace is not None:
+                trace["self"].append(x.clone())
             # cost_encoder_res (encoder.py:281-282) adds the short-cut to the output of the last layer: a second residual operand
             # in that layer's final GEMM epilogue (no add pass, one k/v projection in the decoder)
             x = self._vertical(pk["vert"][i], x, ctx, B, H1, W1, nl, extra_res=short if i == HP["encoder_depth"] - 1 else None)
+            if trace is not None:
+                trace["vert"].append(x.clone())
         return x, None
 
     # ------------------------------------------------------------------ decoder
@@ -536,10 +553,12 @@ class FlowFormer(ParamTree):
                      corflo_p=ops.Planes(R, 256, dev))
         return S
 
-    def _update_block(self, S, coords1, attn, gru_tab, B, H1, W1):
+    def _update_block(self, S, coords1, attn, gru_tab, B, H1, W1, trace=None):
         """GMAUpdateBlock.forward (gru.py:322-334) without the mask head: BasicMotionEncoder (gru.py:246-254), GMA
         aggregate (gma.py:102-115), SepConvGRU (gru.py:44-59), flow head (gru.py:5-13); coords1 += delta_flow
-        (decoder.py:329).  Reads S['corr'] (cost_forward | cost_global), updates S['hxA'][:, :128] (net) and coords1."""
+        (decoder.py:329).  Reads S['corr'] (cost_forward | cost_global), updates S['hxA'][:, :128] (net) and coords1.
+        trace (a dict): the state it starts from and the output of every sub-stage (split3 build: corflo as its planes, and a copy of every
+        plane image once the iteration is done)."""
         D = self._pk["dec"]
         N = H1 * W1
         hxA, hxB, corr = S["hxA"], S["hxB"], S["corr"]
@@ -548,48 +567,75 @@ class FlowFormer(ParamTree):
             W3 = D["s3"]
             hxA_p = S["hxA_p"]
             # convc1 (K = 160) stays on the fp32 kernel and emits cor1's planes; flow_encode emits flo1's and the flow's two channels
+            if trace is not None:
+                trace.update(coords_in=coords1.clone(), net_in=hxA[:, :128].clone())
             ops.conv_gemm(corr, D["convc1"][0], S["cor1"], bias=D["convc1"][1], act="relu", out_planes=S["cor1_p"])
             ops.flow_encode_split3(coords1, D["convf1"][0], D["convf1"][1], S["flo1"], hxA[:, 254:256], B, H1, W1, S["flo1_p"], (hxA_p, 254))
             ops.conv_gemm_pair((S["cor1_p"], W3["convc2"], S["corflo"][:, :192],
                                 dict(geom=g3, bias=D["convc2"][1], act="relu", out_planes=S["corflo_p"].cols(0, 192), no_f32=True)),
                                (S["flo1_p"], W3["convf2"], S["corflo"][:, 192:],
                                 dict(geom=g3, bias=D["convf2"][1], act="relu", out_planes=S["corflo_p"].cols(192, 256), no_f32=True)))
+            if trace is not None:
+                trace.update(cor1=S["cor1"].clone(), flo1=S["flo1"].clone(), flow=hxA[:, 254:256].clone(), corflo_p=_planes_copy(S["corflo_p"]))
             ops.conv_gemm(S["corflo_p"], W3["conv"], hxA[:, 128:254], geom=g3, bias=D["conv"][1], act="relu", out_planes=hxA_p.cols(128, 256))
+            if trace is not None:
+                trace.update(motion=hxA[:, 128:254].clone())
             # the aggregate reads the whole attention matrix every iteration and is HBM-bound either way (fp32: 134 MB per launch, 64.8 us in
             # the chain; planes: 201 MB, 66.2 us): it stays on the fp32 kernel, whose epilogue emits the planes of its result
             ops.gma_aggregate(attn, hxA[:, 128:256], D["to_v"], D["gamma"], S["vT"], hxA[:, 256:], B, N, out_planes=hxA_p.cols(256, 384))
+            if trace is not None:
+                trace.update(aggregate=hxA[:, 256:].clone())
             ops.sepconv_gru_split3(hxA, hxA_p, S["hxB_p"], S["zbuf"], gru_tab["1"], gru_tab["2"], W3["zr1"], W3["q1"], W3["zr2"], W3["q2"], B, H1, W1)
+            if trace is not None:
+                trace.update(gru=hxA[:, :128].clone())
             ops.conv_gemm(hxA_p.cols(0, 128), W3["fh1"], S["fh"], geom=g3, bias=D["fh1"][1], act="relu")
             ops.conv_gemm(S["fh"], D["fh2"][0], coords1, geom=g3, bias=D["fh2"][1], epi="add", aux1=coords1)
+            if trace is not None:
+                trace.update(fh=S["fh"].clone(), coords_out=coords1.clone(), hxA=hxA.clone(),
+                             planes={k: _planes_copy(S[k]) for k in ("hxA_p", "cor1_p", "flo1_p", "corflo_p")})
             return
+        if trace is not None:
+            trace.update(coords_in=coords1.clone(), net_in=hxA[:, :128].clone())
         ops.conv_gemm(corr, D["convc1"][0], S["cor1"], bias=D["convc1"][1], act="relu")
         ops.flow_encode(coords1, D["convf1"][0], D["convf1"][1], S["flo1"], hxA[:, 254:256], B, H1, W1)      # :321, gru.py:251,254
         # convc2 (384 tiles) and convf2 (128 tiles) are independent and ready together: one launch, two workgroups per CU, no
         # split-K slabs (gru.py:252-253)
         ops.conv_gemm_pair((S["cor1"], D["convc2"][0], S["corflo"][:, :192], dict(geom=g3, bias=D["convc2"][1], act="relu")),
                            (S["flo1"], D["convf2"][0], S["corflo"][:, 192:], dict(geom=g3, bias=D["convf2"][1], act="relu")))
+        if trace is not None:
+            trace.update(cor1=S["cor1"].clone(), flo1=S["flo1"].clone(), flow=hxA[:, 254:256].clone(), corflo=S["corflo"].clone())
         ops.conv_gemm(S["corflo"], D["conv"][0], hxA[:, 128:254], geom=g3, bias=D["conv"][1], act="relu")
+        if trace is not None:
+            trace.update(motion=hxA[:, 128:254].clone())
         # GMA aggregate: v^T = Wv . mf^T, out = mf + gamma * attn @ v
         ops.gma_aggregate(attn, hxA[:, 128:256], D["to_v"], D["gamma"], S["vT"], hxA[:, 256:], B, N)
+        if trace is not None:
+            trace.update(aggregate=hxA[:, 256:].clone())
         # SepConvGRU: horizontal 1x5 then vertical 5x1
         ops.sepconv_gru(hxA, hxB, S["zbuf"], gru_tab["1"], gru_tab["2"], D["zr1"], D["q1"], D["zr2"], D["q2"], B, H1, W1)
+        if trace is not None:
+            trace.update(gru=hxA[:, :128].clone())
         ops.conv_gemm(hxA[:, :128], D["fh1"][0], S["fh"], geom=g3, bias=D["fh1"][1], act="relu")
         ops.conv_gemm(S["fh"], D["fh2"][0], coords1, geom=g3, bias=D["fh2"][1], epi="add", aux1=coords1)
+        if trace is not None:
+            trace.update(fh=S["fh"].clone(), coords_out=coords1.clone(), hxA=hxA.clone())
 
-    def _mask_head(self, S, B, H1, W1):
+    def _mask_head(self, S, B, H1, W1, trace=None):
         """mask = .25 * conv1x1(relu(conv3x3(net))) (gru.py:315-318,333) -> rows [R, 576]."""
         D = self._pk["dec"]
         if S["s3"]:
             ops.conv_gemm(S["hxA_p"].cols(0, 128), D["s3"]["m0"], S["fh"], geom=(B, H1, W1, 3, 3, 1, 1, 1, 1), bias=D["m0"][1], act="relu")
         else:
             ops.conv_gemm(S["hxA"][:, :128], D["m0"][0], S["fh"], geom=(B, H1, W1, 3, 3, 1, 1, 1, 1), bias=D["m0"][1], act="relu")
+        if trace is not None:
+            trace.update(mask_hidden=S["fh"].clone())
         mask = _new(S["hxA"].shape[0], 576, S["hxA"].device)
         ops.conv_gemm(S["fh"], D["m2"][0], mask, bias=D["m2"][1], alpha=0.25)
         return mask
 
-    def _decoder_prologue(self, ctx, B, H1, W1):
+    def _decoder_prologue(self, ctx, B, H1, W1, trace=None):
         """what the decoder derives from the context alone, once per pass: net / inp (decoder.py:283-287), the SepConvGRU tables, the GMA
-        attention matrix (gma.py:54-76)."""
+        attention matrix (gma.py:54-76).  trace (a dict): copies of all of them."""
         D = self._pk["dec"]
         dev = ctx.device
         N = H1 * W1
@@ -603,16 +649,23 @@ class FlowFormer(ParamTree):
         qk = _new(R, 256, dev)
         attn = torch.empty((B, N, N), device=dev)
         ops.gma_attention(inp, D["qk"], qk, attn, B, N)
+        if trace is not None:
+            trace.update(net=S["hxA"][:, :128].clone(), inp=inp.clone(), gru_tab={k: v.clone() for k, v in gru_tab.items()}, attn=attn.clone(),
+                         qk=qk.clone())
+            if S["s3"]:
+                trace.update(net_p=_planes_copy(S["hxA_p"]))
         return dict(S=S, inp=inp, gru_tab=gru_tab, attn=attn, qk=qk)
 
     def _decoder(self, mem, mem_short, ctx, cost_maps, B, H1, W1, iters, trace=None):
-        """MemoryDecoder.forward eval branch (decoder.py:262-344)."""
+        """MemoryDecoder.forward eval branch (decoder.py:262-344).  trace (a list whose last entry is the encoder's record): the prologue goes
+        into that record's "prologue", then one record per iteration (coords1, net and corr after it, plus _update_block's sub-stages); the
+        last one also holds the mask head and the upsampled flow."""
         D = self._pk["dec"]
         dev = ctx.device
         N = H1 * W1
         R = B * N
         nl = self._pk["latents"].shape[0]
-        pre = self._decoder_prologue(ctx, B, H1, W1)
+        pre = self._decoder_prologue(ctx, B, H1, W1, trace=None if trace is None else trace[-1].setdefault("prologue", {}))
         S, gru_tab, attn = pre["S"], pre["gru_tab"], pre["attn"]
         # k, v of the cost-memory cross attention, once (decoder.py:68-70); memory = x + short_cut (linear -> two GEMMs)
         ca = D["ca"]
@@ -623,19 +676,25 @@ class FlowFormer(ParamTree):
             kv0 = _new(R * nl, 128, dev)
             ops.conv_gemm(mem_short, ca["kv"][0], kv0, bias=ca["kv"][1])
             ops.conv_gemm(mem, ca["kv"][0], kv, aux0=kv0)
+        if trace is not None:
+            trace[-1]["prologue"]["kv"] = kv.clone()
         coords1 = _new(R, 2, dev)
         ops.coords_grid(coords1, B, H1, W1)
         for it in range(iters):
             ops.cost_lookup9x9(cost_maps, coords1, S["corr"], R, H1, W1)                              # decoder.py:291
             # flow_token_encoder + cost-memory cross attention + FFN: one fused launch (decoder.py:305-312)
             ops.decoder_token_chain(S["corr"], coords1, kv, D["chain16"], R, nl)
-            self._update_block(S, coords1, attn, gru_tab, B, H1, W1)
+            rec = None if trace is None else {}
+            self._update_block(S, coords1, attn, gru_tab, B, H1, W1, trace=rec)
             if trace is not None:
-                trace.append(dict(coords1=coords1.clone(), net=S["hxA"][:, :128].clone(), corr=S["corr"].clone()))
+                rec.update(coords1=coords1.clone(), net=S["hxA"][:, :128].clone(), corr=S["corr"].clone())
+                trace.append(rec)
         # mask head + convex upsampling, last iteration only (gru.py:315-318,333; decoder.py:214-225)
-        mask = self._mask_head(S, B, H1, W1)
+        mask = self._mask_head(S, B, H1, W1, trace=None if trace is None else trace[-1])
         flow_up = torch.empty((B, 2, 8 * H1, 8 * W1), device=dev)
         ops.convex_upsample(coords1, mask, flow_up, B, H1, W1)
+        if trace is not None:
+            trace[-1].update(mask=mask.clone(), flow_up=flow_up.clone())
         return flow_up, coords1
 
     # ================================================================== forward
@@ -649,29 +708,33 @@ class FlowFormer(ParamTree):
         if H % 32 or W % 32:
             raise RuntimeError(f"input size {H}x{W} must be a multiple of 32 (reference runs both nets at 512x512)")
         dev = image1.device
+        tr = None if trace is None else dict(cnet=[], fnet=[], encoder={})
         x = _new(2 * B * H * W, 4, dev)
         ops.prep_image(image1.contiguous(), x[:B * H * W], 4, 2.0, 255.0, 1.0)        # transformer.py:53-54
         ops.prep_image(image2.contiguous(), x[B * H * W:], 4, 2.0, 255.0, 1.0)
-        ctx, H1, W1 = self._twins(pk["cnet"], x[:B * H * W], B, H, W)                 # context = cnet(image1)
-        feats, _, _ = self._twins(pk["fnet"], x, 2 * B, H, W)                        # fnet(image1), fnet(image2)
+        ctx, H1, W1 = self._twins(pk["cnet"], x[:B * H * W], B, H, W, trace=tr and tr["cnet"])      # context = cnet(image1)
+        feats, _, _ = self._twins(pk["fnet"], x, 2 * B, H, W, trace=tr and tr["fnet"])             # fnet(image1), fnet(image2)
         N = H1 * W1
         feats = feats.view(2, B, N, 256)
         cost_maps = torch.empty((B * N, N), device=dev)                              # all-pairs volume (encoder.py:359-369)
         ops.corr_volume(feats[0], feats[1], cost_maps.view(B, N, N))
-        mem, short = self._cost_encoder(cost_maps, ctx, B, H1, W1)
+        mem, short = self._cost_encoder(cost_maps, ctx, B, H1, W1, trace=tr and tr["encoder"])
         if trace is not None:
-            trace.append(dict(context=ctx, feats=feats, cost_maps=cost_maps, mem=mem, short=short))
+            trace.append(dict(context=ctx, feats=feats, cost_maps=cost_maps, mem=mem, short=short, **tr))
         flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, B, H1, W1, iters, trace)
         return flow_up, coords1, (B, H1, W1)
 
-    def flow_rows_pair(self, image_a, image_b, iters=None):
+    def flow_rows_pair(self, image_a, image_b, iters=None, trace=None):
         """Both directions at once: returns flow_up [2B,2,H,W] = [flow a->b ; flow b->a].
 
         The stitching path always needs the forward AND the backward flow of the same image pair
         (flowHomoAdpater.py:167,178 / :236,326) and the two FlowFormer passes are independent, so they run
         as one batch of 2B: the feature encoder sees each image once instead of twice (the reference
         recomputes fnet(a), fnet(b) in the second pass), every GEMM of the encoder/decoder has twice the
-        rows (M = 8192 instead of 4096 per launch), and the launch count per pair halves."""
+        rows (M = 8192 instead of 4096 per launch), and the launch count per pair halves.
+
+        trace: as flow_rows' (a list that gets the encoder's record, with the per-block Twins / cost-encoder / decoder-prologue copies, then
+        one record per refinement iteration); the hooks only clone tensors, so the launch sequence is the same with and without it."""
         if not image_a.is_cuda:
             raise RuntimeError("FlowFormer runs on the MI355X HIP kernels only: move the module and inputs to cuda")
         pk = self._pk or self.pack()
@@ -680,18 +743,21 @@ class FlowFormer(ParamTree):
         if H % 32 or W % 32:
             raise RuntimeError(f"input size {H}x{W} must be a multiple of 32 (reference runs both nets at 512x512)")
         dev = image_a.device
+        tr = None if trace is None else dict(cnet=[], fnet=[], encoder={})
         x = _new(2 * B * H * W, 4, dev)
         ops.prep_image(image_a.contiguous(), x[:B * H * W], 4, 2.0, 255.0, 1.0)
         ops.prep_image(image_b.contiguous(), x[B * H * W:], 4, 2.0, 255.0, 1.0)
-        ctx, H1, W1 = self._twins(pk["cnet"], x, 2 * B, H, W)          # context of a (pass a->b) then of b (pass b->a)
-        feats, _, _ = self._twins(pk["fnet"], x, 2 * B, H, W)
+        ctx, H1, W1 = self._twins(pk["cnet"], x, 2 * B, H, W, trace=tr and tr["cnet"])          # context of a (pass a->b) then of b (pass b->a)
+        feats, _, _ = self._twins(pk["fnet"], x, 2 * B, H, W, trace=tr and tr["fnet"])
         N = H1 * W1
         feats = feats.view(2, B, N, 256)
         cost_maps = torch.empty((2 * B * N, N), device=dev)
         # the reverse direction's volume is the transpose of the forward one: one product, two stores
         ops.corr_volume_both(feats[0], feats[1], cost_maps[:B * N].view(B, N, N), cost_maps[B * N:].view(B, N, N))
-        mem, short = self._cost_encoder(cost_maps, ctx, 2 * B, H1, W1)
-        flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, 2 * B, H1, W1, iters)
+        mem, short = self._cost_encoder(cost_maps, ctx, 2 * B, H1, W1, trace=tr and tr["encoder"])
+        if trace is not None:
+            trace.append(dict(context=ctx, feats=feats, cost_maps=cost_maps, mem=mem, short=short, **tr))
+        flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, 2 * B, H1, W1, iters, trace)
         return flow_up, coords1, (2 * B, H1, W1)
 
     def forward(self, image1, image2, mask=None, output=None, flow_init=None):
