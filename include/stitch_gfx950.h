@@ -333,7 +333,8 @@ int st_convex_upsample(const float* coords1, const float* mask, int32_t ldm, flo
  * motion[B,4,2]*(mscale_x, mscale_y), both divided by `div` -> H [B,3,3].                           */
 int st_dlt4(const float* src4x2, const float* motion, float* H, int32_t B, float mscale_x, float mscale_y,
             float div, void* stream);
-/* out[b] = L @ (invert ? X[b]^-1 : X[b]) @ R (flowHomoAdpater.py:108,112,226,307).                  */
+/* out[b] = L @ (invert ? X[b]^-1 : X[b]) @ R (flowHomoAdpater.py:108,112,226,307).  invert == 1: torch.inverse
+ * of a contiguous X; invert == 2: torch.inverse of a column-major X (another torch.inverse's result, warp_utils.py:24). */
 int st_mat3_sandwich(const float* L, const float* X, const float* R, float* out, int32_t B, int32_t invert,
                      void* stream);
 /* torch_homo_transform.transformer (core/udis_utils/torch_homo_transform.py:5-151); the last n_ones
@@ -346,6 +347,11 @@ int st_mesh_bounds(const float* H, float* out4, int32_t B, float width, float he
 /* warp() = grid_sample(bilinear, zeros, align_corners=True) at pix+flow (core/warp_utils.py:54-80). */
 int st_flow_warp(const float* x, const float* flow, const float* mul, float* out, int32_t B, int32_t C,
                  int32_t H, int32_t W, void* stream);
+/* use_combine_h_flow branch of train_eval_foward (flowHomoAdpater.py:150-164): Hi = inverse(H8) (optional output [B,3,3]), mesh of
+ * the per-pixel rigid grid through inverse(Hi) (warp_utils.py:10-34), final_flow = mesh - grid + flow, out6 = warp(cat(image2,
+ * ones), final_flow) [B,6,H,W], overlap = mean(out6[:,3:6]) < 0.9 [B,H,W].  image2 [B,3,H,W], H8 [B,3,3], flow [B,2,H,W]. */
+int st_homo_flow_warp(const float* image2, const float* H8, const float* flow, float* out6, float* overlap, float* Hi,
+                      int32_t B, int32_t H, int32_t W, void* stream);
 /* F.interpolate bilinear: resize_flow (warp_utils.py:38-46) / Resize((512,512)) (flowHomoAdpater.py:14);
  * align_corners == 2: scale_factor form of out.py:281 (half-pixel centres, source step (div0, div1) = 1/scale). */
 int st_resize_bilinear(const float* x, float* out, int32_t planes, int32_t H, int32_t W, int32_t oh, int32_t ow,
@@ -359,6 +365,10 @@ int st_morph_open(const float* mask, float* out, void* scratch_u8x2, int32_t N, 
 int st_eval_finish(float* final6, const float* occ, float* overlap, int32_t B, int32_t H, int32_t W, void* stream);
 int st_blend(const float* homo1, const float* homo2, float* fin, const float* occ, float* output2, float* mask1,
              float* mask2, uint8_t* blend, int32_t h, int32_t w, void* stream);          /* :339-360 */
+/* test_out without the consistency mask (flowHomoAdpater.py:349-360): st_blend's outputs, fin read only, no occlusion and no
+ * non_overlap_mask factor. */
+int st_blend_plain(const float* homo1, const float* homo2, const float* fin, float* output2, float* mask1, float* mask2,
+                   uint8_t* blend, int32_t h, int32_t w, void* stream);
 int st_mean_threshold(const float* x, float* out, int32_t B, int32_t C, int32_t H, int32_t W, float thr,
                       void* stream);                                                      /* :233-234 */
 /* UDIS2 TPS transformer (core/udis_utils/torch_tps_transform.py:7-190): fp64 solve -> T [B,2,N+3],

@@ -4,10 +4,13 @@ Same constructor, same ``forward(input1_tensor, input2_tensor, type, pad_mode, p
 same output-dict keys / shapes / dtypes, same checkpoint key set (``homo_backbone.*``,
 ``flow_backbone.*``; a DataParallel ``module.`` prefix is accepted).  Inputs are float32
 ``[B,3,H,W]`` RGB in 0..255.  Everything below runs in HIP kernels through the C-ABI; PyTorch only
-owns the device buffers.  The live configuration is the shipped one (configs/last_config.py +
-inf_configs/*): only_homo=False, use_forward=False, use_combine_h_flow=False,
-use_fb_consistency_mask=True, test_not_use_combine_h_flow=True, use_whole_resolution=False; the
-reference's other branches raise ``NotImplementedError`` here exactly where they are dead/buggy there.
+owns the device buffers.  The shipped configuration (configs/last_config.py + inf_configs/*) is
+only_homo=False, use_forward=False, use_combine_h_flow=False, use_fb_consistency_mask=True,
+test_not_use_combine_h_flow=True, use_whole_resolution=False.  The reference's other live branches run too:
+``test_eval`` with only_homo=True (homography only, no flow network; flowHomoAdpater.py:115-118) or with
+use_combine_h_flow=True and the consistency mask off (:144-164), and ``test_out`` with the consistency mask off
+(:347-353).  The branches that are dead or broken in the reference raise ``NotImplementedError``: use_forward=True,
+use_combine_h_flow with the mask on, test_not_use_combine_h_flow=False, use_whole_resolution=True.
 """
 from __future__ import annotations
 
@@ -139,10 +142,36 @@ class FlowHomoAdpater(nn.Module):
         """hipGraph replay of ``forward(type=...)`` for fixed-shape inputs (see ``GraphedForward``)."""
         return GraphedForward(self, type)
 
+    # ------------------------------------------------------------------ branch selection
+    def eval_branch(self):
+        """The branch ``train_eval_foward`` takes for the current cfg, in the reference's order (:115-186): "only_homo" (checked
+        first, so it wins over use_forward / use_combine_h_flow), then use_forward (raises: H_flow is used undefined at :128),
+        then "combine" (raises with the consistency mask on, as :145-146 does), else the shipped branch: "shipped" with the
+        consistency mask, "shipped_no_mask" without it (one flow pass, no occlusion factor, no origin_occlusion_mask).  Every
+        distinct name is a distinct launch sequence: the graph holders key their captures by it."""
+        if _flag(self.cfg, "only_homo"):
+            return "only_homo"
+        if self.use_forward:
+            raise NotImplementedError("use_forward=True is dead in the reference (H_flow undefined, flowHomoAdpater.py:128)")
+        if _flag(self.cfg, "use_combine_h_flow"):
+            if _flag(self.cfg, "use_fb_consistency_mask"):
+                raise NotImplementedError("use_combine_h_flow with use_fb_consistency_mask raises in the reference (flowHomoAdpater.py:145-146)")
+            return "combine"
+        return "shipped" if _flag(self.cfg, "use_fb_consistency_mask") else "shipped_no_mask"
+
+    def test_out_branch(self):
+        """The branch of ``test_out_forward``: "fb" (consistency mask, :318-346) or "plain" (:347-353).  only_homo and
+        use_combine_h_flow are not read there (as in the reference)."""
+        if self.use_forward:
+            raise NotImplementedError("use_forward=True raises in the reference's test_out (flowHomoAdpater.py:295-296)")
+        if not _flag(self.cfg, "test_not_use_combine_h_flow") or _flag(self.cfg, "use_whole_resolution"):
+            raise NotImplementedError("test_not_use_combine_h_flow=False and use_whole_resolution=True raise in the reference "
+                                      "(flowHomoAdpater.py:300-301,362-363)")
+        return "fb" if _flag(self.cfg, "use_fb_consistency_mask") else "plain"
+
     # ------------------------------------------------------------------ eval @ fixed size (:83-191)
     def train_eval_foward(self, input1_tensor, input2_tensor):
-        if self.use_forward or _flag(self.cfg, "use_combine_h_flow") or _flag(self.cfg, "only_homo"):
-            raise NotImplementedError("only the shipped branch (flowHomoAdpater.py:165-186) is implemented")
+        branch = self.eval_branch()
         dev = input1_tensor.device
         B, _, img_h, img_w = input1_tensor.shape
         motion = self.predict_homo(input1_tensor, input2_tensor)
@@ -154,7 +183,15 @@ class FlowHomoAdpater(nn.Module):
         ops.mat3_sandwich(Minv, H, M, H_inv_mat, invert=True)                                          # :112
         output_H = ops.homo_warp(input2_tensor, H_mat.view(B, 9), (img_h, img_w), n_ones=3)            # :111
         output_H_inv = ops.homo_warp(input1_tensor, H_inv_mat.view(B, 9), (img_h, img_w), n_ones=3)    # :113
+        if branch == "only_homo":                                                                      # :115-118
+            return dict(output_H=output_H, output_H_inv=output_H_inv, final_warp_output=output_H, overlap=None,
+                        flow_predictions=None, H=H)
         warp2 = output_H[:, 0:3].contiguous()
+        if branch == "combine":
+            flow = self.predict_flow(input1_tensor, warp2)[0]                                          # :148
+            final, overlap, Hi = ops.homo_flow_warp(input2_tensor, H, flow)                            # :150-164
+            return dict(output_H=output_H, output_H_inv=output_H_inv, final_warp_output=final, overlap=overlap,
+                        flow_predictions=[flow], H=Hi)                                                 # H reassigned at :150
         fb = _flag(self.cfg, "use_fb_consistency_mask")              # missing key = False, as hasattr(...) and ... (:176)
         if fb:
             flow_ij, flow_ji = self.predict_flow_pair(input1_tensor, warp2)                            # :167 and :178, one batch
@@ -181,14 +218,9 @@ class FlowHomoAdpater(nn.Module):
     def _test_out_nets(self, input1_tensor, input2_tensor):
         """First part of test_out_forward (:204-266): both networks at 512x512, native-resolution DLT and the mesh bounds.
         No host synchronisation and a fixed launch sequence for a given input shape, so it can be replayed from a hipGraph
-        (``GraphedTestOut``); everything it returns is a device tensor."""
-        if self.use_forward:
-            raise NotImplementedError
-        if not _flag(self.cfg, "test_not_use_combine_h_flow") or _flag(self.cfg, "use_whole_resolution"):
-            raise NotImplementedError("only the shipped branch (test_not_use_combine_h_flow=True, use_whole_resolution=False, "
-                                      "flowHomoAdpater.py:303-360) is implemented")
-        if not _flag(self.cfg, "use_fb_consistency_mask"):
-            raise NotImplementedError("shipped inference config sets use_fb_consistency_mask=True (flowHomoAdpater.py:324)")
+        (``GraphedTestOut``); everything it returns is a device tensor.  Without the consistency mask only the forward flow
+        is computed (one flow-network pass) and ``back`` is None."""
+        fb = self.test_out_branch() == "fb"
         dev = input1_tensor.device
         B, _, img_h, img_w = input1_tensor.shape
         if B != 1:
@@ -204,9 +236,14 @@ class FlowHomoAdpater(nn.Module):
         out_H = ops.homo_warp(b512, th.view(B, 9), (512, 512), n_ones=3)                               # :230
         warp2_512 = out_H[:, 0:3].contiguous()
         warp_mask_512 = ops.mean_threshold(out_H[:, 3:6].contiguous(), 0.5)                            # :233-234
-        flow512, back512 = self.predict_flow_pair(a512, warp2_512)                                     # :236 and :326, one batch
+        if fb:
+            flow512, back512 = self.predict_flow_pair(a512, warp2_512)                                 # :236 and :326, one batch
+        else:
+            flow512, back512 = self.predict_flow(a512, warp2_512)[0], None                             # :236
         residual = ops.resize_bilinear(flow512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))  # :241
-        back = ops.resize_bilinear(back512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))
+        back = None
+        if fb:
+            back = ops.resize_bilinear(back512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))
         H = torch.empty((B, 3, 3), device=dev)
         ops.dlt4(self._corners(dev, float(img_w), float(img_h)), motion, H, B, img_w / 512.0, img_h / 512.0, 1.0)  # :244-253
         bounds = torch.empty((4,), device=dev)
@@ -215,7 +252,8 @@ class FlowHomoAdpater(nn.Module):
 
     def _test_out_canvas(self, input1_tensor, input2_tensor, nets):
         """Second part (:268-377): the canvas size is read back to the host (the path's one sync), then the canvas-sized
-        homography warps, the flow warp, occlusion mask and the blend."""
+        homography warps, the flow warp, occlusion mask and the blend.  The branch is the one ``nets`` was computed for:
+        no backward flow (``back`` None) means the blend without the consistency mask (:347-353)."""
         dev = input1_tensor.device
         B, _, img_h, img_w = input1_tensor.shape
         residual, back, H = nets["residual"], nets["back"], nets["H"]
@@ -238,16 +276,22 @@ class FlowHomoAdpater(nn.Module):
         homo_output2 = ops.homo_warp(input2_tensor, H_mat.view(B, 9), canvas, n_ones=3)                # :310
         rf = ops.homo_warp(residual, I_mat.view(1, 9), canvas, n_ones=1)                               # :313-314
         final = ops.flow_warp(homo_output2, rf[:, 0:2].contiguous(), rf[:, 2:3].contiguous())          # :316-317
-        occ = ops.occlusion_from_range(ops.range_map(back), False)                                     # :332
-        origin_occ = ops.morph_open(occ, 19)                                                           # :333-334
-        occ_c = ops.homo_warp(origin_occ, I_mat.view(1, 9), canvas)                                    # :335
-        occ_c = ops.morph_open(occ_c, 19)                                                              # :336
-        output2, mask1, mask2, blend = ops.blend(homo_output, homo_output2, final, occ_c)              # :339-360
-        return dict(H_warp=homo_output2[:, 0:3], final_warp=final[:, 0:3], output1=homo_output[:, 0:3], output2=output2,
-                    mask1=mask1, mask2=mask2, blend_image=blend, residual_flow=residual, width_min=width_min,
-                    height_min=height_min, out_height=out_height, out_width=out_width, H=Hc,
-                    warp_input2_mask=nets["warp_mask_512"], warp_input2_tensor_512=nets["warp2_512"], I_mat=I_mat,
-                    H_warp_mask=homo_output2[:, 3:6], occlusion_mask=occ_c, origin_occlusion_mask=origin_occ)
+        if back is not None:
+            occ = ops.occlusion_from_range(ops.range_map(back), False)                                 # :332
+            origin_occ = ops.morph_open(occ, 19)                                                       # :333-334
+            occ_c = ops.homo_warp(origin_occ, I_mat.view(1, 9), canvas)                                # :335
+            occ_c = ops.morph_open(occ_c, 19)                                                          # :336
+            output2, mask1, mask2, blend = ops.blend(homo_output, homo_output2, final, occ_c)          # :339-360
+        else:
+            output2, mask1, mask2, blend = ops.blend_plain(homo_output, homo_output2, final)           # :347-360
+        out = dict(H_warp=homo_output2[:, 0:3], final_warp=final[:, 0:3], output1=homo_output[:, 0:3], output2=output2,
+                   mask1=mask1, mask2=mask2, blend_image=blend, residual_flow=residual, width_min=width_min,
+                   height_min=height_min, out_height=out_height, out_width=out_width, H=Hc,
+                   warp_input2_mask=nets["warp_mask_512"], warp_input2_tensor_512=nets["warp2_512"], I_mat=I_mat,
+                   H_warp_mask=homo_output2[:, 3:6])
+        if back is not None:
+            out.update(occlusion_mask=occ_c, origin_occlusion_mask=origin_occ)
+        return out
 
     def graphed_test_out(self):
         """hipGraph replay of the network part of ``forward(type="test_out")`` (see ``GraphedTestOut``)."""
@@ -273,7 +317,7 @@ class GraphedTestOut:
         m = self.model
         if m.training:
             raise NotImplementedError("inference-only drop-in: call .eval() first")
-        key = (tuple(input1_tensor.shape), input1_tensor.device.index)
+        key = (tuple(input1_tensor.shape), input1_tensor.device.index, m.test_out_branch())     # a cfg flip re-captures
         ent = self._graphs.get(key)
         gen = m.weights_generation()
         if ent is not None and ent[5] != gen:          # weights re-packed since the capture: the graph reads dead copies
@@ -323,7 +367,7 @@ class GraphedForward:
         self._graphs = {}
 
     def __call__(self, input1_tensor, input2_tensor):
-        key = (tuple(input1_tensor.shape), input1_tensor.device.index)
+        key = (tuple(input1_tensor.shape), input1_tensor.device.index, self.model.eval_branch())   # a cfg flip re-captures
         ent = self._graphs.get(key)
         if ent is not None and ent[5] != self.model.weights_generation():       # weights re-packed since the capture
             ent = None

@@ -109,15 +109,9 @@ __device__ __forceinline__ void mat3_mul(const float* A, const float* Bm, float*
             o[r * 3 + c] = acc;
         }
 }
-// torch.inverse of a 3x3 (flowHomoAdpater.py:112, warp_utils.py:24) = sgetrf(A^T) + sgetrs('T', I) in MKL's order:
-// column 0 scaled by the pivot's reciprocal, column 1 divided, fused trailing updates; U's diagonal by reciprocal.
-__device__ __forceinline__ void mat3_inv(const float* Ain, float* o) {
-    float A[3][3], Bm[3][3];
-    int piv[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) A[i][j] = Ain[j * 3 + i];
+// MKL's sgetrf of a 3x3 held as A[row][col] (LAPACK's matrix): partial pivoting, column 0 scaled by the pivot's reciprocal,
+// column 1 divided, fused trailing updates.  L (unit diagonal) below, U on and above the diagonal, row swaps in piv.
+__device__ __forceinline__ void mat3_lu(float (&A)[3][3], int (&piv)[3]) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         int p = k;
@@ -138,6 +132,18 @@ __device__ __forceinline__ void mat3_inv(const float* Ain, float* o) {
 #pragma unroll
             for (int j = k + 1; j < 3; ++j) A[i][j] = __fmaf_rn(-A[i][k], A[k][j], A[i][j]);
     }
+}
+
+// torch.inverse of a row-major (contiguous) 3x3 (flowHomoAdpater.py:112, warp_utils.py:24): ATen's linalg_solve factors A^T,
+// sgetrf(A^T) + sgetrs('T', I) in MKL's order; U's diagonal by reciprocal.
+__device__ __forceinline__ void mat3_inv(const float* Ain, float* o) {
+    float A[3][3], Bm[3][3];
+    int piv[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) A[i][j] = Ain[j * 3 + i];
+    mat3_lu(A, piv);
     const float r0 = 1.0f / A[0][0], r1 = 1.0f / A[1][1], r2 = 1.0f / A[2][2];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -163,14 +169,55 @@ __device__ __forceinline__ void mat3_inv(const float* Ain, float* o) {
         for (int j = 0; j < 3; ++j) o[i * 3 + j] = Bm[i][j];
 }
 
-// out[b] = L @ (invert ? inv(X[b]) : X[b]) @ R   with L, R shared 3x3 (flowHomoAdpater.py:108,112,226,307)
+// torch.inverse of a COLUMN-major 3x3, e.g. the result of another torch.inverse (warp_utils.py:24 inverting :150's output):
+// ATen's linalg_solve factors A itself, sgetrf(A) + sgetrs('N', I).  MKL's solve order, measured bit for bit against
+// torch.inverse on column-major inputs (tests/test_branches_cpu.py): rows swapped into the identity column, L y = b with
+// unfused products (y2 = b2 - (l20 y0 + l21 y1)), U x = y with x1 = fma(-u12, x2, y1) and x0 = y0 - fma(u02, x2, u01 x1);
+// U's diagonal by reciprocal for the first two right-hand sides and by division for the third.  Ain / o are row-major values.
+__device__ __forceinline__ void mat3_inv_cm(const float* Ain, float* o) {
+    float A[3][3];
+    int piv[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) A[i][j] = Ain[i * 3 + j];
+    mat3_lu(A, piv);
+    const float r0 = 1.0f / A[0][0], r1 = 1.0f / A[1][1], r2 = 1.0f / A[2][2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float b[3] = {(c == 0) ? 1.f : 0.f, (c == 1) ? 1.f : 0.f, (c == 2) ? 1.f : 0.f};
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int q = 1; q < 3; ++q)
+                if (q > k && piv[k] == q) { const float t = b[k]; b[k] = b[q]; b[q] = t; }
+        const float y0 = b[0];
+        const float y1 = b[1] - A[1][0] * y0;
+        const float y2 = b[2] - (A[2][0] * y0 + A[2][1] * y1);
+        float x0, x1, x2;
+        if (c < 2) {
+            x2 = y2 * r2;
+            x1 = __fmaf_rn(-A[1][2], x2, y1) * r1;
+            x0 = (y0 - __fmaf_rn(A[0][2], x2, A[0][1] * x1)) * r0;
+        } else {
+            x2 = y2 / A[2][2];
+            x1 = __fmaf_rn(-A[1][2], x2, y1) / A[1][1];
+            x0 = (y0 - __fmaf_rn(A[0][2], x2, A[0][1] * x1)) / A[0][0];
+        }
+        o[c] = x0; o[3 + c] = x1; o[6 + c] = x2;
+    }
+}
+
+// out[b] = L @ (invert ? inv(X[b]) : X[b]) @ R   with L, R shared 3x3 (flowHomoAdpater.py:108,112,226,307);
+// invert == 2: X[b] is inverted as torch.inverse does a column-major operand (mat3_inv_cm)
 __global__ void mat3_sandwich_kernel(const float* __restrict__ L, const float* __restrict__ X, const float* __restrict__ R,
                                      float* __restrict__ out, int B, int invert) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     float l[9], r[9], x[9], t[9], u[9];
     for (int k = 0; k < 9; ++k) { l[k] = L[k]; r[k] = R[k]; x[k] = X[9 * b + k]; }
-    if (invert) { mat3_inv(x, t); for (int k = 0; k < 9; ++k) x[k] = t[k]; }
+    if (invert == 2) { mat3_inv_cm(x, t); for (int k = 0; k < 9; ++k) x[k] = t[k]; }
+    else if (invert) { mat3_inv(x, t); for (int k = 0; k < 9; ++k) x[k] = t[k]; }
     mat3_mul(l, x, t);
     mat3_mul(t, r, u);
     for (int k = 0; k < 9; ++k) out[9 * b + k] = u[k];
@@ -323,6 +370,40 @@ extern "C" int st_mesh_bounds(const float* H, float* out4, int32_t B, float widt
 // Backward flow warp = F.grid_sample(bilinear, zeros, align_corners=True) of x at pix + flow
 // (core/warp_utils.py:54-80).  x [B,C,H,W], flow [B,2,H,W] NCHW -> out [B,C,H,W];
 // optional per-pixel multiplier mul [B,1,H,W] (flowHomoAdpater.py:317).
+struct FlowTap { int x0, y0; float nw, ne, sw, se; bool fin, t00, t01, t10, t11; };
+
+// warp()'s normalisation and grid_sample's unnormalisation of pixel (i, j) moved by (fx, fy), and the four bilinear taps
+__device__ __forceinline__ FlowTap flow_tap(int i, int j, float fx, float fy, int H, int W) {
+    FlowTap t;
+    const float wm = (float)(W - 1 > 1 ? W - 1 : 1), hm = (float)(H - 1 > 1 ? H - 1 : 1);
+    const float gx = 2.0f * ((float)j + fx) / wm - 1.0f;
+    const float gy = 2.0f * ((float)i + fy) / hm - 1.0f;
+    const float ix = ((gx + 1.0f) / 2.0f) * (float)(W - 1), iy = ((gy + 1.0f) / 2.0f) * (float)(H - 1);
+    const float x0f = floorf(ix), y0f = floorf(iy);
+    const float x1f = x0f + 1.0f, y1f = y0f + 1.0f;
+    t.nw = (x1f - ix) * (y1f - iy); t.ne = (ix - x0f) * (y1f - iy);
+    t.sw = (x1f - ix) * (iy - y0f); t.se = (ix - x0f) * (iy - y0f);
+    t.fin = fabsf(ix) < 1e9f && fabsf(iy) < 1e9f;
+    t.x0 = t.fin ? (int)x0f : -2; t.y0 = t.fin ? (int)y0f : -2;
+    const int x1 = t.x0 + 1, y1 = t.y0 + 1;
+    const bool xin0 = t.x0 >= 0 && t.x0 < W, xin1 = x1 >= 0 && x1 < W, yin0 = t.y0 >= 0 && t.y0 < H, yin1 = y1 >= 0 && y1 < H;
+    t.t00 = xin0 && yin0; t.t01 = xin1 && yin0; t.t10 = xin0 && yin1; t.t11 = xin1 && yin1;
+    return t;
+}
+
+// one channel at the taps; im == nullptr samples the all-ones image the reference concatenates (torch.ones_like)
+__device__ __forceinline__ float flow_tap_sample(const float* __restrict__ im, const FlowTap& t, int W) {
+    const size_t r0 = (size_t)t.y0 * W, r1 = r0 + W;
+    // ATen's CPU grid_sample accumulates nw*v + ne*v + sw*v + se*v as one product followed by three fused
+    // multiply-adds (measured bit for bit), out-of-range taps contributing 0
+    float v = (t.t00 ? (im ? im[r0 + t.x0] : 1.f) : 0.f) * t.nw;
+    v = __fmaf_rn(t.t01 ? (im ? im[r0 + t.x0 + 1] : 1.f) : 0.f, t.ne, v);
+    v = __fmaf_rn(t.t10 ? (im ? im[r1 + t.x0] : 1.f) : 0.f, t.sw, v);
+    v = __fmaf_rn(t.t11 ? (im ? im[r1 + t.x0 + 1] : 1.f) : 0.f, t.se, v);
+    if (!t.fin) v = 0.f;                                 // non-finite coordinate: ATen's bounds tests all fail -> 0 (0 * NaN weights would give NaN)
+    return v;
+}
+
 __global__ __launch_bounds__(256) void flow_warp_kernel(const float* __restrict__ x, const float* __restrict__ flow,
                                                         const float* __restrict__ mul, float* __restrict__ out, int C, int H,
                                                         int W) {
@@ -331,30 +412,63 @@ __global__ __launch_bounds__(256) void flow_warp_kernel(const float* __restrict_
     const int b = blockIdx.z;
     if (i >= H || j >= W) return;
     const size_t hw = (size_t)H * W, pix = (size_t)i * W + j;
-    const float fx = flow[(size_t)b * 2 * hw + pix], fy = flow[(size_t)b * 2 * hw + hw + pix];
-    const float wm = (float)(W - 1 > 1 ? W - 1 : 1), hm = (float)(H - 1 > 1 ? H - 1 : 1);
-    const float gx = 2.0f * ((float)j + fx) / wm - 1.0f;
-    const float gy = 2.0f * ((float)i + fy) / hm - 1.0f;
-    const float ix = ((gx + 1.0f) / 2.0f) * (float)(W - 1), iy = ((gy + 1.0f) / 2.0f) * (float)(H - 1);
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const float x1f = x0f + 1.0f, y1f = y0f + 1.0f;
-    const float nw = (x1f - ix) * (y1f - iy), ne = (ix - x0f) * (y1f - iy);
-    const float sw = (x1f - ix) * (iy - y0f), se = (ix - x0f) * (iy - y0f);
-    const bool fin = fabsf(ix) < 1e9f && fabsf(iy) < 1e9f;
-    const int x0 = fin ? (int)x0f : -2, y0 = fin ? (int)y0f : -2, x1 = x0 + 1, y1 = y0 + 1;
-    const bool xin0 = x0 >= 0 && x0 < W, xin1 = x1 >= 0 && x1 < W, yin0 = y0 >= 0 && y0 < H, yin1 = y1 >= 0 && y1 < H;
+    const FlowTap t = flow_tap(i, j, flow[(size_t)b * 2 * hw + pix], flow[(size_t)b * 2 * hw + hw + pix], H, W);
     const float m = mul ? mul[(size_t)b * hw + pix] : 1.0f;
     for (int c = 0; c < C; ++c) {
-        const float* im = x + ((size_t)b * C + c) * hw;
-        // ATen's CPU grid_sample accumulates nw*v + ne*v + sw*v + se*v as one product followed by three fused
-        // multiply-adds (measured bit for bit), out-of-range taps contributing 0
-        float v = (xin0 && yin0 ? im[(size_t)y0 * W + x0] : 0.f) * nw;
-        v = __fmaf_rn(xin1 && yin0 ? im[(size_t)y0 * W + x1] : 0.f, ne, v);
-        v = __fmaf_rn(xin0 && yin1 ? im[(size_t)y1 * W + x0] : 0.f, sw, v);
-        v = __fmaf_rn(xin1 && yin1 ? im[(size_t)y1 * W + x1] : 0.f, se, v);
-        if (!fin) v = 0.f;                               // non-finite coordinate: ATen's bounds tests all fail -> 0 (0 * NaN weights would give NaN)
+        const float v = flow_tap_sample(x + ((size_t)b * C + c) * hw, t, W);
         out[((size_t)b * C + c) * hw + pix] = mul ? v * m : v;
     }
+}
+
+// use_combine_h_flow branch of train_eval_foward (flowHomoAdpater.py:150-164, core/warp_utils.py:10-80), one pixel per lane:
+//   Hi = inverse(H8); the mesh projection is inverse(Hi) (H2Mesh inverts again); the rigid mesh is taken at per-pixel
+//   resolution (x_j = linspace(0, W, W)[j], spacing W/(W-1)); H_flow = mesh - (x, y); final_flow = H_flow + flow;
+//   out6 = warp(cat(image2, ones), final_flow); overlap = mean(out6[3:6]) < 0.9 (no occlusion factor).
+// image2 [B,3,H,W], H8 [B,3,3], flow [B,2,H,W] -> out6 [B,6,H,W], overlap [B,H,W], Hi (optional) [B,3,3].
+__global__ __launch_bounds__(256) void homo_flow_warp_kernel(const float* __restrict__ image2, const float* __restrict__ H8,
+                                                             const float* __restrict__ flow, float* __restrict__ out6,
+                                                             float* __restrict__ overlap, float* __restrict__ Hi, int H, int W) {
+    __shared__ float s_p[9];
+    const int j = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int b = blockIdx.z;
+    if (threadIdx.x == 0) {
+        float h[9], hi[9], p[9];
+        for (int k = 0; k < 9; ++k) h[k] = H8[9 * b + k];
+        mat3_inv(h, hi);                                 // :150, H is contiguous
+        mat3_inv_cm(hi, p);                              // warp_utils.py:24 inverts :150's column-major result
+        for (int k = 0; k < 9; ++k) s_p[k] = p[k];
+        if (Hi && blockIdx.x == 0 && blockIdx.y == 0)
+            for (int k = 0; k < 9; ++k) Hi[9 * b + k] = hi[k];
+    }
+    __syncthreads();
+    if (i >= H || j >= W) return;
+    const float x = lin_at(0.0f, (float)W, W, j), y = lin_at(0.0f, (float)H, H, i);
+    // [3x3]@[3xN] of H2Mesh (warp_utils.py:30).  torch.inverse returns a column-major 3x3, and MKL's sgemm on that operand sums
+    // x, 1, y in this order, unfused (mesh_bounds_kernel's order is the one of a row-major operand); pinned against the
+    // reference's final_flow by tests/test_branches_cpu.py.
+    float tx = s_p[0] * x; tx = tx + s_p[2]; tx = tx + s_p[1] * y;
+    float ty = s_p[3] * x; ty = ty + s_p[5]; ty = ty + s_p[4] * y;
+    float tz = s_p[6] * x; tz = tz + s_p[8]; tz = tz + s_p[7] * y;
+    const size_t hw = (size_t)H * W, pix = (size_t)i * W + j;
+    const float fx = (tx / tz - x) + flow[(size_t)b * 2 * hw + pix];
+    const float fy = (ty / tz - y) + flow[(size_t)b * 2 * hw + hw + pix];
+    const FlowTap t = flow_tap(i, j, fx, fy, H, W);
+    float* o = out6 + (size_t)b * 6 * hw + pix;
+    for (int c = 0; c < 3; ++c) o[(size_t)c * hw] = flow_tap_sample(image2 + ((size_t)b * 3 + c) * hw, t, W);
+    const float one = flow_tap_sample(nullptr, t, W);
+    for (int c = 3; c < 6; ++c) o[(size_t)c * hw] = one;
+    const float m = ((one + one) + one) / 3.0f;          // eval_finish_kernel's mean over channels 3..5
+    overlap[(size_t)b * hw + pix] = m < 0.9f ? 1.0f : 0.0f;
+}
+
+extern "C" int st_homo_flow_warp(const float* image2, const float* H8, const float* flow, float* out6, float* overlap, float* Hi,
+                                 int32_t B, int32_t H, int32_t W, void* stream) {
+    if (!image2 || !H8 || !flow || !out6 || !overlap || B <= 0 || H <= 0 || W <= 0) return ST_EINVAL;
+    dim3 grid((W + 63) / 64, (H + 3) / 4, B);
+    hipLaunchKernelGGL(homo_flow_warp_kernel, grid, dim3(256), 0, (hipStream_t)stream, image2, H8, flow, out6, overlap, Hi, H, W);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
 }
 
 extern "C" int st_flow_warp(const float* x, const float* flow, const float* mul, float* out, int32_t B, int32_t C, int32_t H,
@@ -575,6 +689,39 @@ extern "C" int st_blend(const float* homo1, const float* homo2, float* fin, cons
     if (!homo1 || !homo2 || !fin || !occ || !output2 || !mask1 || !mask2 || !blend) return ST_EINVAL;
     const size_t hw = (size_t)h * w;
     hipLaunchKernelGGL(blend_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, homo1, homo2, fin, occ, output2,
+                       mask1, mask2, blend, hw);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}
+
+// test_out mask algebra + blend without the consistency mask (flowHomoAdpater.py:347-353,355-360): no occlusion factor on fin and
+// no non_overlap_mask factor.  Same buffers as blend_kernel; fin is read only.
+__global__ void blend_plain_kernel(const float* __restrict__ homo1, const float* __restrict__ homo2, const float* __restrict__ fin,
+                                   float* __restrict__ output2, float* __restrict__ mask1o, float* __restrict__ mask2o,
+                                   unsigned char* __restrict__ blend, size_t hw) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= hw) return;
+    float m2[3], m1[3];
+    for (int c = 0; c < 3; ++c) {
+        const float mm1 = homo1[(3 + c) * hw + p], mm2 = fin[(3 + c) * hw + p];
+        const float o2 = homo2[c * hw + p] * (1.0f - mm2) + fin[c * hw + p] * mm2;            // :352
+        m2[c] = homo2[(3 + c) * hw + p] * (1.0f - mm2) + mm2 * mm2;                          // :353
+        m1[c] = mm1;
+        float bl = (homo1[c * hw + p] * mm1 + o2 * m2[c]) / (mm1 + m2[c]);                    // :357
+        bl = fminf(fmaxf(bl, 0.0f), 255.0f);                                                  // NaN -> 0 like the CPU cast
+        blend[c * hw + p] = (bl == bl) ? (unsigned char)bl : (unsigned char)0;
+        output2[c * hw + p] = o2;
+    }
+    const float a1 = fminf(fmaxf(((m1[0] + m1[1]) + m1[2]) / 3.0f, 0.0f), 1.0f);             // :361-362
+    const float a2 = fminf(fmaxf(((m2[0] + m2[1]) + m2[2]) / 3.0f, 0.0f), 1.0f);
+    for (int c = 0; c < 3; ++c) { mask1o[c * hw + p] = a1; mask2o[c * hw + p] = a2; }
+}
+
+extern "C" int st_blend_plain(const float* homo1, const float* homo2, const float* fin, float* output2, float* mask1, float* mask2,
+                              uint8_t* blend, int32_t h, int32_t w, void* stream) {
+    if (!homo1 || !homo2 || !fin || !output2 || !mask1 || !mask2 || !blend || h <= 0 || w <= 0) return ST_EINVAL;
+    const size_t hw = (size_t)h * w;
+    hipLaunchKernelGGL(blend_plain_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, homo1, homo2, fin, output2,
                        mask1, mask2, blend, hw);
     ST_CHECK_LAUNCH();
     return ST_OK;

@@ -138,13 +138,16 @@ class EvalPipeline:
             ncpu = os.cpu_count() or 1
         self.workers = decode_workers or max(2, min(4, ncpu // 2))     # 1.7 ms per 512x512 pair and thread: 4 threads feed ~2 000 pairs/s
         self.copy_stream = torch.cuda.Stream(device=device)
-        self._slots = {}                # (shape, u8) -> {slot index: _Slot}, in least-recently-used order
+        self._slots = {}                # (shape, u8, branch) -> {slot index: _Slot}, in least-recently-used order
         self._gen = None
 
     def _slot(self, k, shape, u8):
         """The slot (stream + graph) number k for this input shape; captured on first use.  The cache is bounded: a dataset of many image
-        sizes (or ragged batch tails) evicts the least recently used SHAPE -- its graphs, private pools and pinned buffers go with it."""
-        key = (shape, u8)
+        sizes (or ragged batch tails) evicts the least recently used SHAPE -- its graphs, private pools and pinned buffers go with it.
+        The model's test_eval branch is part of the key: a cfg flag flipped after a capture (only_homo, use_combine_h_flow) captures anew
+        instead of replaying the other branch's graph."""
+        branch = self.model.eval_branch() if hasattr(self.model, "eval_branch") else None
+        key = (shape, u8, branch)
         group = self._slots.pop(key, None)
         if group is None:
             group = {}

@@ -625,6 +625,19 @@ def flow_warp(x, flow, mul=None):
     return out
 
 
+def homo_flow_warp(image2, H8, flow, want_hi=True):
+    """use_combine_h_flow tail: image2 [B,3,H,W], H8 [B,3,3], flow [B,2,H,W] -> (final [B,6,H,W], overlap [B,H,W], Hi [B,3,3] or None)."""
+    B, Cc, H, W = image2.shape
+    if Cc != 3 or tuple(flow.shape) != (B, 2, H, W) or tuple(H8.shape) != (B, 3, 3):
+        raise ValueError(f"image2 [B,3,H,W], H8 [B,3,3], flow [B,2,H,W] expected: {tuple(image2.shape)} {tuple(H8.shape)} {tuple(flow.shape)}")
+    dev = image2.device
+    out = torch.empty((B, 6, H, W), device=dev, dtype=torch.float32)
+    overlap = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+    hi = torch.empty((B, 3, 3), device=dev, dtype=torch.float32) if want_hi else None
+    check(lib.st_homo_flow_warp(_pc(image2), _pc(H8), _pc(flow), _p(out), _p(overlap), _p(hi), B, H, W, _stream()), "st_homo_flow_warp")
+    return out, overlap, hi
+
+
 def resize_bilinear(x, oh, ow, align_corners, div=None):
     B, Cc, H, W = x.shape
     out = torch.empty((B, Cc, oh, ow), device=x.device, dtype=torch.float32)
@@ -674,6 +687,18 @@ def blend(homo1, homo2, fin, occ):
     m2 = torch.empty((1, 3, h, w), device=dev)
     bl = torch.empty((1, 3, h, w), device=dev, dtype=torch.uint8)
     check(lib.st_blend(_pc(homo1), _pc(homo2), _pc(fin), _pc(occ), _p(o2), _p(m1), _p(m2), _p(bl), h, w, _stream()), "st_blend")
+    return o2, m1, m2, bl
+
+
+def blend_plain(homo1, homo2, fin):
+    """test_out blend without the consistency mask: (output2, mask1, mask2, blend) as ``blend``, fin left as it is."""
+    _, _, h, w = homo1.shape
+    dev = homo1.device
+    o2 = torch.empty((1, 3, h, w), device=dev)
+    m1 = torch.empty((1, 3, h, w), device=dev)
+    m2 = torch.empty((1, 3, h, w), device=dev)
+    bl = torch.empty((1, 3, h, w), device=dev, dtype=torch.uint8)
+    check(lib.st_blend_plain(_pc(homo1), _pc(homo2), _pc(fin), _p(o2), _p(m1), _p(m2), _p(bl), h, w, _stream()), "st_blend_plain")
     return o2, m1, m2, bl
 
 
