@@ -71,7 +71,7 @@ typedef struct st_gemm_desc {
                               (encoder.py:359-369 evaluated for (f2, f1)) and costs a second store instead of a second product */
     int32_t ld_ct;
     int32_t reserved2;     /* must be 0 */
-    int32_t split3;        /* 0: a / w are fp32 (everything above).  1: EXACT-SPLIT operands on the bf16 matrix cores (csrc/gemm_split3.h):
+    int32_t split3;        /* 0: a / w are fp32 (everything above).  1: EXACT-SPLIT operands on the bf16 matrix cores (csrc/gemm_split3.h, launched from csrc/gemm_split3.hip):
                               a, w (and a2) point to THREE bf16 planes hi, mid, lo with x == hi + mid + lo exactly (st_split3_pack or a
                               producing kernel's epilogue), each blocked by 32-channel chunks: plane = [C / 32][rows][32] bf16, the planes
                               a_plane_stride / w_plane_stride ELEMENTS apart; a_rows = rows per chunk of the A planes (all pixels B*H*W of the
@@ -196,7 +196,7 @@ typedef struct st_mlp_desc {
 } st_mlp_desc;
 int st_mlp128(const st_mlp_desc* desc, void* stream);
 int st_abi_mlp_desc_size(void);
-/* st_mlp128 on the exact-split contraction (round 6, csrc/mlp_split3.h): every fp32 product of the three GEMMs as six bf16 MFMA
+/* st_mlp128 on the exact-split contraction (round 6, csrc/mlp_split3.h in csrc/gemm_rows.hip): every fp32 product of the three GEMMs as six bf16 MFMA
  * products of operand planes (hi / mid / lo), fp32 accumulation; same operator, same `desc`; accuracy against fp64 that of the fp32 MFMA
  * chain or better (tests/test_split3_gpu.py); a non-finite activation gives NaN in its row.  The weights are packed ONCE into an image
  * (one 49-KiB LDS stage per step of the kernel's walk: [wp chunk]* then [w1 chunk | w2 slice | b1 chunk]*):

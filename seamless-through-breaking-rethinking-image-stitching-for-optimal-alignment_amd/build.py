@@ -12,7 +12,7 @@ OUT = os.path.join(HERE, "libstitch_gfx950.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # geom.hip pins every fp32 rounding (bit-exact sample indices), inpaint.hip the Telea arrival times, tps_other.hip the fp64 remap
 # maps, transref.hip the inpainter's pre / post steps: no fma contraction there
-SOURCES = {"gemm.hip": [], "nn.hip": [], "flowops.hip": [], "geom.hip": ["-ffp-contract=off"],
+SOURCES = {"gemm.hip": [], "gemm_split3.hip": [], "gemm_rows.hip": [], "nn.hip": [], "flowops.hip": [], "geom.hip": ["-ffp-contract=off"],
            "metrics.hip": ["-ffp-contract=off"], "operators.hip": [], "composition.hip": ["-ffp-contract=off"], "tps_pipeline.hip": ["-ffp-contract=off"], "patchembed.hip": [],
            "inpaint.hip": ["-ffp-contract=off"], "tps_other.hip": ["-ffp-contract=off"],
            "transref.hip": ["-ffp-contract=off"]}
@@ -22,11 +22,19 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-re
 # back to back (the split3 kernels, csrc/gemm_split3.h), a wave's v_pk_*_f32 results come back wrong in lanes 48-63 -- 80 % of the
 # launches of the bilinear-resize kernel beside a split3 GEMM had corrupted 16-lane runs (DMA-only variant of the aggressor: none;
 # MFMA-only: the same; the fp32-MFMA kernels as aggressor: none; torch's own elementwise kernels as victims: none).  The compiler's
-# hazard tables cannot see another wave, so the instructions are simply not generated (scalar v_mul / v_add / v_fma instead: same
-# IEEE results, and beside an MFMA stream the packed forms were the slower choice anyway -- MI355X_MICROARCH.md, packed f32 VALU).
+# hazard tables cannot see another wave, so the instructions are simply not generated (scalar v_mul / v_add / v_fma instead).  NOT the same
+# bits everywhere: under the default -ffp-contract a v_pk_mul_f32 + v_pk_add_f32 pair can come back as ONE scalar v_fma_f32, i.e. one rounding
+# instead of two (the sources that pin their roundings carry -ffp-contract=off above).  Beside an MFMA stream the packed
+# forms were the slower choice anyway -- MI355X_MICROARCH.md, packed f32 VALU.
 COMMON += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 if os.environ.get("ST_EXACT_TRANSCENDENTALS", "0") == "1":       # diagnostic build (csrc/common.h): not the shipped arithmetic
     COMMON.append("-DST_EXACT_TRANSCENDENTALS")
+
+
+def compile_cmd(src, out, extra=()):
+    """The command that compiles one of SOURCES (a file name in csrc/) to `out`: the library's flags, then `extra`, which says what to emit
+    (build(): -c; tools/isa_waits.py: -S --cuda-device-only)."""
+    return [HIPCC] + COMMON + SOURCES[src] + list(extra) + [os.path.join(CSRC, src), "-o", out]
 
 
 def _stale(target, deps):
@@ -37,15 +45,15 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=False):
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_split3.h"), os.path.join(CSRC, "mlp_split3.h"), os.path.join(CSRC, "tps_solve.h"), os.path.join(HERE, "..", "include", "stitch_gfx950.h")]
+    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_split3.h"), os.path.join(CSRC, "mlp_split3.h"), os.path.join(CSRC, "tps_solve.h"), os.path.join(HERE, "..", "include", "stitch_gfx950.h")]
     objs, jobs = [], []
     os.makedirs(os.path.join(CSRC, "_obj"), exist_ok=True)
-    for src, extra in SOURCES.items():
+    for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, "_obj", src.replace(".hip", ".o"))
         objs.append(o)
         if force or _stale(o, [s] + hdrs):
-            jobs.append([HIPCC] + COMMON + extra + ["-c", s, "-o", o])
+            jobs.append(compile_cmd(src, o, ["-c"]))
     if jobs:
         def run(cmd):
             if verbose:

@@ -1,4 +1,5 @@
-// Exact-split fp32 contraction on the bf16 matrix cores ("split3"), included by gemm.hip (it shares the epilogue).
+// Exact-split fp32 contraction on the bf16 matrix cores ("split3"): the kernels.  Included by gemm_split3.hip alone, which launches them; the
+// epilogue they share with the fp32 kernels of gemm.hip comes from gemm_common.h.
 //
 //   x = hi + mid + lo EXACTLY, three bf16 (8 + 8 + 8 significand bits cover fp32's 24; st_split3 below), so
 //   a . b = hi.hi + hi.mid + mid.hi + mid.mid + hi.lo + lo.hi  (+ three dropped terms <= 2^-23 |a||b| together):
@@ -20,7 +21,7 @@
 // Matches: /root/reference/core/FlowFormer/PerCostFormer3/gru.py:44-59,246-254 (SepConvGRU, motion encoder convs),
 // gma.py:102-115 (aggregate), encoder.py:359-369 (all-pairs correlation).
 #pragma once
-
+#include "gemm_common.h"
 
 // fp32 [rows, ldx] (C columns, C % 32 == 0) -> three blocked planes.  One thread = 8 channels of one row.
 __global__ __launch_bounds__(256) void split3_pack_kernel(const float* __restrict__ x, __bf16* __restrict__ planes, long long rows, int C,

@@ -2,7 +2,7 @@
 // The C = 128 block tail (st_mlp128: [projection + residual ->] LayerNorm -> fc1 + GELU -> fc2 + residual(s); twins.py:622-623, 785-790)
 // on the exact-split contraction of csrc/gemm_split3.h: every fp32 product of the three GEMMs is the sum of six
 // v_mfma_f32_32x32x16_bf16 products of the operands' bf16 planes (hi / mid / lo, x == hi + mid + lo), accumulated in fp32.
-// Included by gemm.hip behind rowmlp128_kernel, whose structure it keeps:
+// Included by gemm_rows.hip alone, behind rowmlp128_kernel, whose structure it keeps (loaders and vector types: gemm_common.h):
 //   * a wave owns a 32-row block; the block's rows live in REGISTERS in the MFMA operand layout -- lane (li, lh) holds row li's
 //     features 8 m + 4 lh + t (m = 0..15, t = 0..3) -- and every product is the TRANSPOSED one (weight fragment first), whose 32 x 32
 //     accumulator tile is again that layout: nothing crosses LDS between the layers;
@@ -28,13 +28,15 @@
 // gives NaN in its row (the fp32 kernel gives inf or NaN there).
 // K order inside a 16-k MFMA step: lane half lh holds k = 16 ks + 8 qq + 4 lh + t for element e = 4 qq + t of its 8 -- the order in
 // which the accumulator layout hands the values over; the packed weights follow it.
+#pragma once
+#include "gemm_common.h"
+
 #define MS3_W1_B 24576            // 3 planes x 32 rows x 256 B
 #define MS3_W2_B 24576            // 3 planes x 128 rows x 64 B
 #define MS3_BIAS_B 1024           // 32 floats (128 B) padded to one DMA piece
 #define MS3_STAGE_B (MS3_W1_B + MS3_W2_B + MS3_BIAS_B)
 #define MS3_PIECES (MS3_STAGE_B / 1024)
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 

@@ -1,6 +1,6 @@
 // Operator-level entry points: one C symbol per reference operator of the FlowFormer / stitching path
 // (SURVEY.md 8b minimum symbol set).  Host-side composition only: each function enqueues the library's own
-// kernels (gemm.hip, nn.hip, flowops.hip, geom.hip) on the caller's stream, works in caller-provided scratch,
+// kernels (gemm.hip, gemm_split3.hip, gemm_rows.hip, nn.hip, flowops.hip, geom.hip) on the caller's stream, works in caller-provided scratch,
 // allocates nothing and keeps no state.
 #include "common.h"
 #include "../../include/stitch_gfx950.h"

@@ -17,11 +17,7 @@
 //       stream through a 4-stage LDS ring by buffer_load ... lds, one workgroup barrier per step.  k order, MFMA pairing and the K-block
 //       fold after steps 8 and 16 are those of conv_gemm_dma_kernel on the (6x3 pixel-pair) view the unfused path runs: bit-identical s2.
 // Maps other than 64x64 take the unfused path (operators.hip).
-#include "common.h"
-#include "../../include/stitch_gfx950.h"
-#include <string.h>
-
-bool st_internal_observe(const st_gemm_desc* od, void* stream, int phase, int plan_kernel);      // csrc/gemm.hip
+#include "gemm_common.h"      // st_observe / st_plan_set: this launch reports itself as one of the implicit-GEMM family
 
 typedef float pe_f32x16 __attribute__((ext_vector_type(16)));
 typedef float pe_f32x4 __attribute__((ext_vector_type(4)));
@@ -245,10 +241,11 @@ static int patch_conv12_impl(const float* cost_maps, const float* c0_w36x16, con
     od.a = cost_maps; od.w = c2_w32x576; od.c = s2; od.bias = c2_b;
     od.M = M * 256; od.N = 32; od.K = 576; od.H = 64; od.W = 64; od.Cin = 1; od.ldx = 1; od.ldw = 576; od.ldc = 32;
     od.kh = od.kw = 6; od.sh = od.sw = 2; od.ph = od.pw = 2; od.Ho = od.Wo = 16; od.batch = 1; od.alpha = 1.f; od.act = ST_ACT_RELU;
-    st_internal_observe(&od, stream, 0, 7);
+    st_observe(&od, stream, 0);
     hipLaunchKernelGGL(patch_c0c2_kernel, dim3(G), dim3(256), PE_LDS_BYTES, (hipStream_t)stream, cost_maps, c0_w36x16, c0_b, c2_w32x576, c2_b, s2, M,
                        (__bf16*)s2_planes, (long long)s2_pstride);
-    st_internal_observe(&od, stream, 1, 7);
+    st_plan_set(7, 0, 1, 1);
+    st_observe(&od, stream, 1);
     ST_CHECK_LAUNCH();
     return ST_OK;
 }

@@ -1,18 +1,20 @@
 """Per-kernel ISA summary of the package's HIP sources (no GPU needed): VGPRs, spills, vector-memory loads, and how many of those
 loads are followed by a full `s_waitcnt vmcnt(0)` before the next load -- a run of load / wait / load / wait is a chain of dependent
 memory round trips (hipcc emits it for conditional loads: `cond ? *p : 0`), which a latency-bound kernel cannot afford.
+Compiles with the library's own command (build.py's compile_cmd: the shipped flags of that source), so the figures are those of the shipped code.
 usage: python tools/isa_waits.py [file.hip ...]"""
-import os, re, subprocess, sys, tempfile
+import importlib.util, os, re, subprocess, sys, tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, "..", "seamless-through-breaking-rethinking-image-stitching-for-optimal-alignment_amd", "csrc")
-FLAGS = {"geom.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"], "composition.hip": ["-ffp-contract=off"], "tps_pipeline.hip": ["-ffp-contract=off"], "inpaint.hip": ["-ffp-contract=off"]}
+_spec = importlib.util.spec_from_file_location("_stitch_build", os.path.join(HERE, "..", "seamless-through-breaking-rethinking-image-stitching-for-optimal-alignment_amd", "build.py"))
+BUILD = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(BUILD)
+CSRC = BUILD.CSRC
 
 def summarize(path):
     name = os.path.basename(path)
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", path, "-o", out] + FLAGS.get(name, []),
-                              stderr=subprocess.DEVNULL)
+        subprocess.check_call(BUILD.compile_cmd(name, out, ["-S", "--cuda-device-only"]), stderr=subprocess.DEVNULL)
         text = open(out).read()
     meta = {}
     for m in re.finditer(r"\.name:\s+(\S+)\n(.*?)\.wavefront_size", text, re.S):
@@ -42,8 +44,8 @@ def summarize(path):
     return rows
 
 if __name__ == "__main__":
-    files = sys.argv[1:] or sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    files = sys.argv[1:] or sorted(BUILD.SOURCES)
     print(f"{'file':18} {'kernel':70} vgpr spill scratch loads vmcnt0 load->vmcnt0")
     for f in files:
-        for r in summarize(f if os.path.isabs(f) else os.path.join(CSRC, f)):
+        for r in summarize(f):
             print(f"{r[0]:18} {r[1]:70} {r[2]:4} {r[3]:5} {r[4]:7} {r[5]:5} {r[6]:6} {r[7]:6}")
