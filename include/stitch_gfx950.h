@@ -299,6 +299,16 @@ int st_latent_pool(const float* scores, int32_t ld_s, const float* tokens, int32
 
 /* ---- FlowFormer decoder gathers --------------------------------------------------------------- */
 int st_coords_grid(float* out, int32_t B, int32_t H, int32_t W, void* stream);          /* decoder.py:22-29 */
+/* Warm start (decoder.py:270-272): out rows [B*H*W, 2] = float(grid) + init, init NCHW [B,2,H,W] in low-resolution pixels.     */
+int st_coords_grid_init(float* out, const float* init, int32_t B, int32_t H, int32_t W, void* stream);
+/* Forward splat of a low-resolution flow, the next frame's flow_init (core/utils/utils.py:32-60 on the device, no host read-back).
+ * src: the flow NCHW [B,2,H,W] (src_is_coords_rows = 0) or the decoder's coords1 rows [B*H*W, 2], from which the pixel grid is
+ * subtracted (1); out NCHW [B,2,H,W], not aliasing src.  Source (i, j) lands at (j + dx, i + dy) in fp64 and is valid iff
+ * 0 < px < W and 0 < py < H (a NaN is invalid); every pixel takes the flow of the valid source that landed nearest to it (fp64
+ * squared distance; equal distances: the lowest source index, row-major); no valid source in a batch element: zeros.
+ * H*W <= 65536, B <= 65535.                                                                                         */
+int st_flow_forward_interpolate(const float* src, int32_t src_is_coords_rows, float* out, int32_t B, int32_t H, int32_t W,
+                                void* stream);
 int st_flow_from_coords(const float* coords1, float* flow4, int32_t ld4, float* dst2, int32_t ld2, int32_t B,
                         int32_t H, int32_t W, void* stream);
 /* BasicMotionEncoder flow branch, first layer, fused with the flow computation (gru.py:251, decoder.py:321):

@@ -11,6 +11,8 @@ from .adapter import FlowHomoAdpater, preprocess_occlusion_mask  # noqa: E402,F4
 from .config import CfgNode, load_inference_config, load_model_config  # noqa: E402,F401
 from .flowformer import FlowFormer, build_flowformer  # noqa: E402,F401
 from .homography import UDIS2Network  # noqa: E402,F401
+from . import sequence  # noqa: E402,F401
+from .sequence import SequenceStitcher  # noqa: E402,F401
 from . import composition  # noqa: E402,F401
 from . import tps_pipeline  # noqa: E402,F401
 from . import mix_methods  # noqa: E402,F401

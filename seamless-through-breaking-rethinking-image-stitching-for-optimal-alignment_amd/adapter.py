@@ -104,17 +104,34 @@ class FlowHomoAdpater(nn.Module):
         off = self.homo_backbone.offsets_from_images(input1_tensor, input2_tensor, 1.0, 127.5, 1.0)
         return off.reshape(-1, 4, 2)
 
-    def predict_flow(self, input1_tensor, input2_tensor):
-        """flow 1->2 at full resolution, eval: list of one tensor (flowHomoAdpater.py:63-70)."""
-        return [self.flow_backbone.flow_rows(input1_tensor, input2_tensor)[0]]
+    def predict_flow(self, input1_tensor, input2_tensor, iters=None, flow_init=None):
+        """flow 1->2 at full resolution, eval: list of one tensor (flowHomoAdpater.py:63-70).  iters / flow_init: FlowFormer.flow_rows'."""
+        return [self.flow_backbone.flow_rows(input1_tensor, input2_tensor, iters=iters, flow_init=flow_init)[0]]
 
-    def predict_flow_pair(self, input1_tensor, input2_tensor):
-        """(flow 1->2, flow 2->1) from one batched FlowFormer evaluation (see FlowFormer.flow_rows_pair)."""
+    def predict_flow_pair(self, input1_tensor, input2_tensor, iters=None, flow_init=None):
+        """(flow 1->2, flow 2->1) from one batched FlowFormer evaluation (see FlowFormer.flow_rows_pair, also for iters / flow_init)."""
         B = input1_tensor.shape[0]
-        both = self.flow_backbone.flow_rows_pair(input1_tensor, input2_tensor)[0]
+        both = self.flow_backbone.flow_rows_pair(input1_tensor, input2_tensor, iters=iters, flow_init=flow_init)[0]
         return both[:B], both[B:]
 
+    def _flows(self, input1_tensor, input2_tensor, pair, warm):
+        """The flow pass of a branch: (flow 1->2, flow 2->1 or None).  ``warm`` (a ``sequence.SequenceStitcher``'s state, or None): the
+        refinement starts from its buffer and the splat of this call's final low-res flow (``ops.forward_interpolate`` on coords1's
+        rows) replaces it, both on the current stream: no host synchronisation, the same launch sequence for every frame."""
+        if warm is None:
+            return self.predict_flow_pair(input1_tensor, input2_tensor) if pair else (self.predict_flow(input1_tensor, input2_tensor)[0], None)
+        B, _, h, w = input1_tensor.shape
+        fb = self.flow_backbone
+        state = warm.buffer((2 * B if pair else B, 2, h // 8, w // 8), input1_tensor.device)
+        up, coords1, dims = (fb.flow_rows_pair if pair else fb.flow_rows)(input1_tensor, input2_tensor, iters=warm.iters, flow_init=state)
+        ops.forward_interpolate(coords1, out=state, coords_rows=dims)
+        return (up[:B], up[B:]) if pair else (up, None)
+
     def forward(self, input1_tensor, input2_tensor, type="train", pad_mode="constant", preprocess_callback=None):
+        return self._forward(input1_tensor, input2_tensor, type, pad_mode, preprocess_callback, None)
+
+    def _forward(self, input1_tensor, input2_tensor, type, pad_mode, preprocess_callback, warm):
+        """``forward``; ``warm``: see ``_flows`` (None on the reference surface)."""
         # The reference's callers go through nn.DataParallel and hand over whatever the loader produced, CPU tensors included (out.py:197,
         # evaluate.py:43): the inputs move to the module's device, as DataParallel's scatter does.  The COMPUTE has no CPU path: a module
         # that itself sits on the CPU still raises.
@@ -126,12 +143,12 @@ class FlowHomoAdpater(nn.Module):
         with torch.no_grad():
             if type == "test_out":
                 return self.test_out_forward(input1_tensor, input2_tensor, pad_mode=pad_mode,
-                                             preprocess_callback=preprocess_callback)
+                                             preprocess_callback=preprocess_callback, warm=warm)
             if type == "test_eval":
                 if self.training:
                     raise NotImplementedError("inference-only drop-in: call .eval() first (the training branch of "
                                               "train_eval_foward, flowHomoAdpater.py:83-191, is not implemented)")
-                return self.train_eval_foward(input1_tensor, input2_tensor)
+                return self.train_eval_foward(input1_tensor, input2_tensor, warm=warm)
             if type == "train":
                 # the reference returns every refinement prediction with gradients here; this path is no_grad with
                 # frozen parameters, so training through it would silently learn nothing
@@ -170,7 +187,7 @@ class FlowHomoAdpater(nn.Module):
         return "fb" if _flag(self.cfg, "use_fb_consistency_mask") else "plain"
 
     # ------------------------------------------------------------------ eval @ fixed size (:83-191)
-    def train_eval_foward(self, input1_tensor, input2_tensor):
+    def train_eval_foward(self, input1_tensor, input2_tensor, warm=None):
         branch = self.eval_branch()
         dev = input1_tensor.device
         B, _, img_h, img_w = input1_tensor.shape
@@ -188,15 +205,12 @@ class FlowHomoAdpater(nn.Module):
                         flow_predictions=None, H=H)
         warp2 = output_H[:, 0:3].contiguous()
         if branch == "combine":
-            flow = self.predict_flow(input1_tensor, warp2)[0]                                          # :148
+            flow = self._flows(input1_tensor, warp2, False, warm)[0]                                   # :148
             final, overlap, Hi = ops.homo_flow_warp(input2_tensor, H, flow)                            # :150-164
             return dict(output_H=output_H, output_H_inv=output_H_inv, final_warp_output=final, overlap=overlap,
                         flow_predictions=[flow], H=Hi)                                                 # H reassigned at :150
         fb = _flag(self.cfg, "use_fb_consistency_mask")              # missing key = False, as hasattr(...) and ... (:176)
-        if fb:
-            flow_ij, flow_ji = self.predict_flow_pair(input1_tensor, warp2)                            # :167 and :178, one batch
-        else:
-            flow_ij = self.predict_flow(input1_tensor, warp2)[0]                                       # :167
+        flow_ij, flow_ji = self._flows(input1_tensor, warp2, fb, warm)                                 # :167 (and :178 in the same batch)
         final = ops.flow_warp(output_H, flow_ij)                                                       # :170
         out = dict()
         if fb:
@@ -211,11 +225,11 @@ class FlowHomoAdpater(nn.Module):
         return out
 
     # ------------------------------------------------------------------ stitching @ native size (:197-377)
-    def test_out_forward(self, input1_tensor, input2_tensor, pad_mode="constant", preprocess_callback=None):
-        nets = self._test_out_nets(input1_tensor, input2_tensor)
+    def test_out_forward(self, input1_tensor, input2_tensor, pad_mode="constant", preprocess_callback=None, warm=None):
+        nets = self._test_out_nets(input1_tensor, input2_tensor, warm=warm)
         return self._test_out_canvas(input1_tensor, input2_tensor, nets)
 
-    def _test_out_nets(self, input1_tensor, input2_tensor):
+    def _test_out_nets(self, input1_tensor, input2_tensor, warm=None):
         """First part of test_out_forward (:204-266): both networks at 512x512, native-resolution DLT and the mesh bounds.
         No host synchronisation and a fixed launch sequence for a given input shape, so it can be replayed from a hipGraph
         (``GraphedTestOut``); everything it returns is a device tensor.  Without the consistency mask only the forward flow
@@ -236,10 +250,7 @@ class FlowHomoAdpater(nn.Module):
         out_H = ops.homo_warp(b512, th.view(B, 9), (512, 512), n_ones=3)                               # :230
         warp2_512 = out_H[:, 0:3].contiguous()
         warp_mask_512 = ops.mean_threshold(out_H[:, 3:6].contiguous(), 0.5)                            # :233-234
-        if fb:
-            flow512, back512 = self.predict_flow_pair(a512, warp2_512)                                 # :236 and :326, one batch
-        else:
-            flow512, back512 = self.predict_flow(a512, warp2_512)[0], None                             # :236
+        flow512, back512 = self._flows(a512, warp2_512, fb, warm)                                      # :236 (and :326 in the same batch)
         residual = ops.resize_bilinear(flow512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))  # :241
         back = None
         if fb:

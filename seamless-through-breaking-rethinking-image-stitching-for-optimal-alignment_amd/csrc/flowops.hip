@@ -21,6 +21,24 @@ extern "C" int st_coords_grid(float* out, int32_t B, int32_t H, int32_t W, void*
     return ST_OK;
 }
 
+// warm start: coords1 = coords0 + flow_init (decoder.py:270-272), the reference's fp32 addition; init NCHW [B,2,H,W], low-res pixels
+__global__ void coords_grid_init_kernel(float* __restrict__ out, const float* __restrict__ init, int B, int H, int W) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)B * H * W) return;
+    const size_t N = (size_t)H * W, b = idx / N;
+    const int r = idx % N;
+    out[idx * 2] = (float)(r % W) + init[b * 2 * N + r];
+    out[idx * 2 + 1] = (float)(r / W) + init[(b * 2 + 1) * N + r];
+}
+
+extern "C" int st_coords_grid_init(float* out, const float* init, int32_t B, int32_t H, int32_t W, void* stream) {
+    if (!out || !init || B < 1 || H < 1 || W < 1) return ST_EINVAL;
+    const size_t total = (size_t)B * H * W;
+    hipLaunchKernelGGL(coords_grid_init_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, init, B, H, W);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}
+
 // flow = coords1 - coords0 (decoder.py:321) written to a zero-padded [N, ld4] buffer (conv input)
 // and, optionally, into two columns of a wider activation buffer (gru.py:254 cat([out, flow])).
 __global__ void flow_from_coords_kernel(const float* __restrict__ coords1, float* __restrict__ flow4, int ld4,

@@ -656,10 +656,11 @@ class FlowFormer(ParamTree):
                 trace.update(net_p=_planes_copy(S["hxA_p"]))
         return dict(S=S, inp=inp, gru_tab=gru_tab, attn=attn, qk=qk)
 
-    def _decoder(self, mem, mem_short, ctx, cost_maps, B, H1, W1, iters, trace=None):
+    def _decoder(self, mem, mem_short, ctx, cost_maps, B, H1, W1, iters, trace=None, flow_init=None):
         """MemoryDecoder.forward eval branch (decoder.py:262-344).  trace (a list whose last entry is the encoder's record): the prologue goes
         into that record's "prologue", then one record per iteration (coords1, net and corr after it, plus _update_block's sub-stages); the
-        last one also holds the mask head and the upsampled flow."""
+        last one also holds the mask head and the upsampled flow.  flow_init ([B,2,H1,W1], low-res pixels): the refinement starts from
+        grid + flow_init (decoder.py:270-272) instead of the grid; None is the cold start (st_coords_grid)."""
         D = self._pk["dec"]
         dev = ctx.device
         N = H1 * W1
@@ -679,7 +680,7 @@ class FlowFormer(ParamTree):
         if trace is not None:
             trace[-1]["prologue"]["kv"] = kv.clone()
         coords1 = _new(R, 2, dev)
-        ops.coords_grid(coords1, B, H1, W1)
+        ops.coords_grid(coords1, B, H1, W1, init=flow_init)
         for it in range(iters):
             ops.cost_lookup9x9(cost_maps, coords1, S["corr"], R, H1, W1)                              # decoder.py:291
             # flow_token_encoder + cost-memory cross attention + FFN: one fused launch (decoder.py:305-312)
@@ -698,8 +699,9 @@ class FlowFormer(ParamTree):
         return flow_up, coords1
 
     # ================================================================== forward
-    def flow_rows(self, image1, image2, iters=None, trace=None):
-        """images NCHW 0..255 -> (flow_up [B,2,H,W], coords1 rows [B*N,2], (B,H1,W1))."""
+    def flow_rows(self, image1, image2, iters=None, trace=None, flow_init=None):
+        """images NCHW 0..255 -> (flow_up [B,2,H,W], coords1 rows [B*N,2], (B,H1,W1)).  flow_init [B,2,H/8,W/8] (low-res pixels): warm
+        start of the refinement, as the reference's flow_init."""
         if not image1.is_cuda:
             raise RuntimeError("FlowFormer runs on the MI355X HIP kernels only: move the module and inputs to cuda")
         pk = self._pk or self.pack()
@@ -721,10 +723,10 @@ class FlowFormer(ParamTree):
         mem, short = self._cost_encoder(cost_maps, ctx, B, H1, W1, trace=tr and tr["encoder"])
         if trace is not None:
             trace.append(dict(context=ctx, feats=feats, cost_maps=cost_maps, mem=mem, short=short, **tr))
-        flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, B, H1, W1, iters, trace)
+        flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, B, H1, W1, iters, trace, flow_init=flow_init)
         return flow_up, coords1, (B, H1, W1)
 
-    def flow_rows_pair(self, image_a, image_b, iters=None, trace=None):
+    def flow_rows_pair(self, image_a, image_b, iters=None, trace=None, flow_init=None):
         """Both directions at once: returns flow_up [2B,2,H,W] = [flow a->b ; flow b->a].
 
         The stitching path always needs the forward AND the backward flow of the same image pair
@@ -734,7 +736,9 @@ class FlowFormer(ParamTree):
         rows (M = 8192 instead of 4096 per launch), and the launch count per pair halves.
 
         trace: as flow_rows' (a list that gets the encoder's record, with the per-block Twins / cost-encoder / decoder-prologue copies, then
-        one record per refinement iteration); the hooks only clone tensors, so the launch sequence is the same with and without it."""
+        one record per refinement iteration); the hooks only clone tensors, so the launch sequence is the same with and without it.
+
+        flow_init [2B,2,H/8,W/8] (low-res pixels): the warm start of both passes, a->b first, then b->a (the batch order above)."""
         if not image_a.is_cuda:
             raise RuntimeError("FlowFormer runs on the MI355X HIP kernels only: move the module and inputs to cuda")
         pk = self._pk or self.pack()
@@ -757,14 +761,15 @@ class FlowFormer(ParamTree):
         mem, short = self._cost_encoder(cost_maps, ctx, 2 * B, H1, W1, trace=tr and tr["encoder"])
         if trace is not None:
             trace.append(dict(context=ctx, feats=feats, cost_maps=cost_maps, mem=mem, short=short, **tr))
-        flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, 2 * B, H1, W1, iters, trace)
+        flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, 2 * B, H1, W1, iters, trace, flow_init=flow_init)
         return flow_up, coords1, (2 * B, H1, W1)
 
     def forward(self, image1, image2, mask=None, output=None, flow_init=None):
-        """Reference surface (transformer.py:47-65, eval): returns (flow_up, flow_lowres)."""
+        """Reference surface (transformer.py:47-65, eval): returns (flow_up, flow_lowres).  flow_init [B,2,H/8,W/8] in low-resolution
+        pixels: the refinement's start (decoder.py:270-272); ``ops.forward_interpolate`` makes one from the previous flow_lowres."""
         if flow_init is not None:
-            raise NotImplementedError("flow_init (warm start) is not on the stitching path")
-        flow_up, coords1, (B, H1, W1) = self.flow_rows(image1, image2)
+            flow_init = flow_init.to(image1.device, torch.float32).contiguous()
+        flow_up, coords1, (B, H1, W1) = self.flow_rows(image1, image2, flow_init=flow_init)
         flow4 = _new(B * H1 * W1, 4, flow_up.device)
         ops.flow_from_coords(coords1, flow4, None, B, H1, W1)
         low = flow4[:, :2].reshape(B, H1, W1, 2).permute(0, 3, 1, 2).contiguous()       # layout only (unused by the adapter)

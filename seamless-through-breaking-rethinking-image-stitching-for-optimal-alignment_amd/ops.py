@@ -430,8 +430,35 @@ def prep_image(src, dst, ldo, mul, div, sub):
     return dst
 
 
-def coords_grid(out, B, H, W):
-    check(lib.st_coords_grid(_p(out), B, H, W, _stream()), "st_coords_grid")
+def coords_grid(out, B, H, W, init=None):
+    """rows [B*H*W, 2] = the pixel grid; with ``init`` (NCHW [B,2,H,W] fp32, low-res pixels) grid + init, the decoder's warm start."""
+    if init is None:
+        check(lib.st_coords_grid(_p(out), B, H, W, _stream()), "st_coords_grid")
+        return
+    if tuple(init.shape) != (B, 2, H, W) or init.dtype != torch.float32 or not init.is_contiguous() or init.device != out.device:
+        raise ValueError(f"flow_init must be a contiguous float32 [{B}, 2, {H}, {W}] tensor on {out.device}")
+    check(lib.st_coords_grid_init(_p(out), _p(init), B, H, W, _stream()), "st_coords_grid_init")
+
+
+def forward_interpolate(flow, out=None, *, coords_rows=None):
+    """The next frame's flow_init from this frame's low-resolution flow (core/utils/utils.py:32-60 as one kernel; contract in
+    include/stitch_gfx950.h).  ``flow``: NCHW [B,2,H1,W1]; or, with ``coords_rows=(B, H1, W1)``, the decoder's coords1 rows
+    [B*H1*W1, 2] (the grid is subtracted in the kernel).  Returns ``out`` (NCHW [B,2,H1,W1], allocated when None)."""
+    if coords_rows is None:
+        B, two, H, W = flow.shape
+        ok = two == 2
+    else:
+        B, H, W = coords_rows
+        ok = tuple(flow.shape) == (B * H * W, 2)
+    if not ok or flow.dtype != torch.float32 or not flow.is_contiguous() or not flow.is_cuda:
+        raise ValueError("forward_interpolate takes a contiguous float32 cuda tensor [B,2,H1,W1], or coords1 rows [B*H1*W1,2]")
+    if out is None:
+        out = torch.empty((B, 2, H, W), device=flow.device)
+    elif tuple(out.shape) != (B, 2, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != flow.device:
+        raise ValueError(f"out must be a contiguous float32 [{B}, 2, {H}, {W}] tensor on {flow.device}")
+    check(lib.st_flow_forward_interpolate(_p(flow), 0 if coords_rows is None else 1, _p(out), B, H, W, _stream()),
+          "st_flow_forward_interpolate")
+    return out
     return out
 
 
