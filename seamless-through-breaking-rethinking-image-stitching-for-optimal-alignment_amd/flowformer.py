@@ -40,7 +40,7 @@ from .homography import pack_conv
 # pair) except the HBM-bound aggregate, PatchEmbed's third convolution and ffn_with_coord + LayerNorm, the q | k | v projections and the
 # block tails run on the bf16 matrix cores with EXACTLY split operands (csrc/gemm_split3.h, csrc/mlp_split3.h: x = hi + mid + lo in three
 # bf16, six products, fp32 accumulate -- error against fp64 0.83x the fp32 MFMA chain's, 1.5-1.76x its speed, profiles/r6_split3_probe.json).
-# Every operand travels as blocked bf16 planes written by the epilogue of the kernel that produced it.  ST_SPLIT3=0 = the fp32-MFMA kernels of rounds 1-5: the all-fp32 reference
+# Every operand travels as blocked bf16 planes written by the epilogue of the kernel that produced it.  ST_SPLIT3=0 = the fp32-MFMA kernels: the all-fp32 reference
 # that bench.py reports as value_exact_fp32.
 SPLIT3 = os.environ.get("ST_SPLIT3", "1") != "0"
 
@@ -52,6 +52,50 @@ def _new(rows, cols, dev, zero=False):
 def _planes_copy(p):
     """a copy of a plane image (the trace hooks: the live one is overwritten by the next iteration)"""
     return ops.Planes(p.rows, p.C, None, t=p.t.clone(), c0=p.c0, ncols=p.ncols)
+
+
+def _keep(trace, **named):
+    """The trace hook, one call per point: nothing without a trace; otherwise the record ``trace`` (a dict) gets copies taken NOW -- tensors
+    cloned, plane images through _planes_copy, dicts of either element-wise.  A list value extends the list kept under that key."""
+    if trace is None:
+        return
+
+    def copy(v):
+        if isinstance(v, dict):
+            return {k: copy(x) for k, x in v.items()}
+        if isinstance(v, ops.Planes):
+            return _planes_copy(v)
+        return v.clone() if torch.is_tensor(v) else v
+    for k, v in named.items():
+        if isinstance(v, list):
+            trace.setdefault(k, []).extend(copy(x) for x in v)
+        else:
+            trace[k] = copy(v)
+
+
+def _record(trace):
+    """a new record at the end of the trace list (None without a trace)"""
+    if trace is None:
+        return None
+    trace.append({})
+    return trace[-1]
+
+
+# The decoder's choice between the exact-split contractions and the fp32-MFMA ones, once per kind of operand.  S is _update_state's dict:
+# S["s3"] says which pass this is; D is the packed decoder.
+def _act(S, name, c0, c1):
+    """columns [c0, c1) of the activation S[name] as a contraction reads them: of its plane image, or of the fp32 tensor"""
+    return S[name + "_p"].cols(c0, c1) if S["s3"] else S[name][:, c0:c1]
+
+
+def _emit(S, name, c0, c1, **kw):
+    """the keyword arguments with which a launch also writes that slice of S[name]'s planes (exact-split pass only)"""
+    return dict(out_planes=S[name + "_p"].cols(c0, c1), **kw) if S["s3"] else {}
+
+
+def _wt(D, S, name):
+    """a contraction's weights: the split3_pack image, or the fp32 matrix of the (w, bias) pair"""
+    return D["s3"][name] if S["s3"] else D[name][0]
 
 
 class FlowFormer(ParamTree):
@@ -111,23 +155,23 @@ class FlowFormer(ParamTree):
                 b0, b1 = prefix + f"blocks.{s}.0.", prefix + f"blocks.{s}.1."
                 C = p[b0 + "norm1.weight"].shape[0]
                 qkv_w, qkv_b = lin(b0 + "attn.qkv")
-                t[f"l{s}"] = dict(n1=lin(b0 + "norm1"), qkv=(qkv_w, qkv_b), proj=lin(b0 + "attn.proj"), n2=lin(b0 + "norm2"),
-                                  fc1=lin(b0 + "mlp.fc1"), fc2=lin(b0 + "mlp.fc2"),
-                                  # a zero-padded token's q/k/v is the bias (twins.py:606-611)
-                                  pads=tuple(qkv_b[i * C:(i + 1) * C].expand(49, C).contiguous() for i in range(3)))
+                L = t[f"l{s}"] = dict(n1=lin(b0 + "norm1"), qkv=(qkv_w, qkv_b), proj=lin(b0 + "attn.proj"), n2=lin(b0 + "norm2"),
+                                      fc1=lin(b0 + "mlp.fc1"), fc2=lin(b0 + "mlp.fc2"),
+                                      # a zero-padded token's q/k/v is the bias (twins.py:606-611)
+                                      pads=tuple(qkv_b[i * C:(i + 1) * C].expand(49, C).contiguous() for i in range(3)))
                 if C == 128:
-                    t[f"l{s}"]["qkv_ln"] = ops.fold_layernorm(*t[f"l{s}"]["n1"], qkv_w, qkv_b)
-                    t[f"l{s}"]["qkv_s3"] = lin_image(t[f"l{s}"]["qkv_ln"])
-                    t[f"l{s}"]["fc1_ln"] = ops.fold_layernorm(*t[f"l{s}"]["n2"], *t[f"l{s}"]["fc1"])
-                    t[f"l{s}"]["mlp_s3"] = mlp_image(t[f"l{s}"]["fc1_ln"], t[f"l{s}"]["fc2"], t[f"l{s}"]["proj"])
+                    L["qkv_ln"] = ops.fold_layernorm(*L["n1"], qkv_w, qkv_b)
+                    L["qkv_s3"] = lin_image(L["qkv_ln"])
+                    L["fc1_ln"] = ops.fold_layernorm(*L["n2"], *L["fc1"])
+                    L["mlp_s3"] = mlp_image(L["fc1_ln"], L["fc2"], L["proj"])
                 w9 = p[prefix + f"pos_block.{s}.proj.0.weight"].reshape(C, 9).t().contiguous()
                 t[f"peg{s}"] = (w9, p[prefix + f"pos_block.{s}.proj.0.bias"].contiguous())
-                t[f"g{s}"] = dict(n1=lin(b1 + "norm1"), q=lin(b1 + "attn.q"), kv=lin(b1 + "attn.kv"), sr=conv(b1 + "attn.sr"),
-                                  srn=lin(b1 + "attn.norm"), proj=lin(b1 + "attn.proj"), n2=lin(b1 + "norm2"),
-                                  fc1=lin(b1 + "mlp.fc1"), fc2=lin(b1 + "mlp.fc2"))
+                G = t[f"g{s}"] = dict(n1=lin(b1 + "norm1"), q=lin(b1 + "attn.q"), kv=lin(b1 + "attn.kv"), sr=conv(b1 + "attn.sr"),
+                                      srn=lin(b1 + "attn.norm"), proj=lin(b1 + "attn.proj"), n2=lin(b1 + "norm2"),
+                                      fc1=lin(b1 + "mlp.fc1"), fc2=lin(b1 + "mlp.fc2"))
                 if C == 128:
-                    t[f"g{s}"]["fc1_ln"] = ops.fold_layernorm(*t[f"g{s}"]["n2"], *t[f"g{s}"]["fc1"])
-                    t[f"g{s}"]["mlp_s3"] = mlp_image(t[f"g{s}"]["fc1_ln"], t[f"g{s}"]["fc2"], t[f"g{s}"]["proj"])
+                    G["fc1_ln"] = ops.fold_layernorm(*G["n2"], *G["fc1"])
+                    G["mlp_s3"] = mlp_image(G["fc1_ln"], G["fc2"], G["proj"])
             return t
 
         pk["fnet"] = twins("memory_encoder.feat_encoder.svt.")
@@ -184,7 +228,7 @@ class FlowFormer(ParamTree):
             v = c + f"vertical_encoder_layers.{i}."
             lb, gb = v + "local_block.", v + "global_block."
             sk_w = p[gb + "attn.sr_key.weight"]           # [128, 192, 4, 4]: channels = [x(128) | ctx(64)]
-            vert.append(dict(
+            Vd = dict(
                 ln1=lin(lb + "norm1"), lctx=lin(lb + "attn.context_proj"), lq=lin(lb + "attn.q"), lk=lin(lb + "attn.k"),
                 lv=lin(lb + "attn.v"), lproj=lin(lb + "attn.proj"), ln2=lin(lb + "norm2"), lfc1=lin(lb + "mlp.fc1"),
                 lfc2=lin(lb + "mlp.fc2"),
@@ -192,21 +236,21 @@ class FlowFormer(ParamTree):
                 gv=lin(gb + "attn.v"), gproj=lin(gb + "attn.proj"), gn2=lin(gb + "norm2"), gfc1=lin(gb + "mlp.fc1"),
                 gfc2=lin(gb + "mlp.fc2"), gsrn=lin(gb + "attn.norm"),
                 gskx=pack_conv(sk_w[:, :128].contiguous()), gskc=pack_conv(sk_w[:, 128:].contiguous()),
-                gskb=p[gb + "attn.sr_key.bias"].contiguous(), gsv=conv(gb + "attn.sr_value")))
-            vert[-1]["lqkv"] = torch.cat([vert[-1]["lq"][0][:, :128], vert[-1]["lk"][0][:, :128], vert[-1]["lv"][0]], 0).contiguous()
-            vert[-1]["gskv"] = torch.cat([vert[-1]["gskx"], vert[-1]["gsv"][0]], 0).contiguous()   # sr_key (x part) | sr_value
-            Vd = vert[-1]
+                gskb=p[gb + "attn.sr_key.bias"].contiguous(), gsv=conv(gb + "attn.sr_value"))
+            vert.append(Vd)
+            Vd["lqkv"] = torch.cat([Vd["lq"][0][:, :128], Vd["lk"][0][:, :128], Vd["lv"][0]], 0).contiguous()
+            Vd["gskv"] = torch.cat([Vd["gskx"], Vd["gsv"][0]], 0).contiguous()   # sr_key (x part) | sr_value
             # per-pixel pre-activation tables in ONE product each: [q | k | v-bias] of the local block (the v columns have zero
             # weights: they carry v's bias), [sr_key over the context channels | sr_value's bias] of the global block
             z128 = torch.zeros_like(Vd["lq"][0])
             Vd["ltab"] = (torch.cat([Vd["lq"][0], Vd["lk"][0], z128], 0).contiguous(), torch.cat([Vd["lq"][1], Vd["lk"][1], Vd["lv"][1]]).contiguous())
             Vd["gtab"] = (torch.cat([Vd["gskc"], torch.zeros_like(Vd["gskc"])], 0).contiguous(), torch.cat([Vd["gskb"], Vd["gsv"][1]]).contiguous())
-            vert[-1]["lqkv_ln"] = ops.fold_layernorm(*vert[-1]["ln1"], vert[-1]["lqkv"])
-            vert[-1]["lqkv_s3"] = lin_image(vert[-1]["lqkv_ln"])
-            vert[-1]["lfc1_ln"] = ops.fold_layernorm(*vert[-1]["ln2"], *vert[-1]["lfc1"])
-            vert[-1]["gfc1_ln"] = ops.fold_layernorm(*vert[-1]["gn2"], *vert[-1]["gfc1"])
-            vert[-1]["lmlp_s3"] = mlp_image(vert[-1]["lfc1_ln"], vert[-1]["lfc2"], vert[-1]["lproj"])
-            vert[-1]["gmlp_s3"] = mlp_image(vert[-1]["gfc1_ln"], vert[-1]["gfc2"], vert[-1]["gproj"])
+            Vd["lqkv_ln"] = ops.fold_layernorm(*Vd["ln1"], Vd["lqkv"])
+            Vd["lqkv_s3"] = lin_image(Vd["lqkv_ln"])
+            Vd["lfc1_ln"] = ops.fold_layernorm(*Vd["ln2"], *Vd["lfc1"])
+            Vd["gfc1_ln"] = ops.fold_layernorm(*Vd["gn2"], *Vd["gfc1"])
+            Vd["lmlp_s3"] = mlp_image(Vd["lfc1_ln"], Vd["lfc2"], Vd["lproj"])
+            Vd["gmlp_s3"] = mlp_image(Vd["gfc1_ln"], Vd["gfc2"], Vd["gproj"])
         pk["vert"] = vert
         m = "memory_decoder."
         Q = HP["query_latent_dim"]
@@ -260,28 +304,26 @@ class FlowFormer(ParamTree):
 
     # ================================================================== shared blocks
     @staticmethod
-    def _mlp(x, n2, fc1, fc2, eps, out=None, fc1_ln=None, extra_res=None, proj=None, image=None):
-        """x + fc2(GELU(fc1(LN(x)))) [+ extra_res] (timm Mlp inside Block, twins.py:785-790).  proj = (att, (w, b), res): x is the Block's
-        attention branch x = att @ w^T + b + res (twins.py:622-623 / 676-677), computed by the same launch when the rows are 128 wide."""
-        if proj is not None:
-            att, (pw, pb), pres = proj
-            dev = att.device
-            if (fc1_ln is not None and att.shape[1] == 128 and pw.is_contiguous()
-                    and fc2[0].is_contiguous() and fc1_ln[0].is_contiguous() and pw.data_ptr() % 16 == 0 and pb.data_ptr() % 16 == 0):
-                o = _new(att.shape[0], 128, dev) if out is None else out
-                return ops.mlp128(att, o, fc1_ln[0], fc1_ln[1], fc2[0], fc2[1], ln_eps=eps, res=extra_res, proj=(pw, pb, pres), image=image)
-            x = _new(att.shape[0], att.shape[1], dev)
-            ops.conv_gemm(att, pw, x, bias=pb, aux0=pres)
-        dev = x.device
-        if fc1_ln is not None and x.shape[1] == 128 and fc2[0].is_contiguous() and fc1_ln[0].is_contiguous():
-            o = _new(x.shape[0], 128, dev) if out is None else out         # (projection weights the fused launch cannot read 16 B at a time)
+    def _mlp(att, proj, res, n2, fc1, fc2, eps, fc1_ln=None, image=None, extra_res=None):
+        """A Block after its attention: the output projection + residual x = att @ w^T + b + res, proj = (w, b) (twins.py:622-623 / 676-677),
+        then x + fc2(GELU(fc1(LN(x)))) [+ extra_res] (timm Mlp inside Block, twins.py:785-790) -- one launch when the rows are 128 wide."""
+        pw, pb = proj
+        dev = att.device
+        rows128 = fc1_ln is not None and att.shape[1] == 128 and fc2[0].is_contiguous() and fc1_ln[0].is_contiguous()
+        if rows128 and pw.is_contiguous() and pw.data_ptr() % 16 == 0 and pb.data_ptr() % 16 == 0:
+            o = _new(att.shape[0], 128, dev)
+            return ops.mlp128(att, o, fc1_ln[0], fc1_ln[1], fc2[0], fc2[1], ln_eps=eps, res=extra_res, proj=(pw, pb, res), image=image)
+        x = _new(att.shape[0], att.shape[1], dev)
+        ops.conv_gemm(att, pw, x, bias=pb, aux0=res)
+        if rows128:
+            o = _new(x.shape[0], 128, dev)                                 # (projection weights the fused launch cannot read 16 B at a time)
             return ops.mlp128(x, o, fc1_ln[0], fc1_ln[1], fc2[0], fc2[1], ln_eps=eps, res=extra_res)
         # C = 256 (Twins stage 2): LayerNorm, fc1 + GELU, fc2 + residual(s) as three launches
         h = _new(x.shape[0], fc1[0].shape[0], dev)
         y = _new(x.shape[0], x.shape[1], dev)
         ops.layernorm(x, n2[0], n2[1], y, eps)
         ops.conv_gemm(y, fc1[0], h, bias=fc1[1], act="gelu")
-        o = _new(x.shape[0], x.shape[1], dev) if out is None else out
+        o = _new(x.shape[0], x.shape[1], dev)
         if extra_res is None:
             ops.conv_gemm(h, fc2[0], o, bias=fc2[1], aux0=x)
         else:
@@ -316,7 +358,7 @@ class FlowFormer(ParamTree):
             att = _new(N, C, dev)
             ops.window_attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], H * W * 3 * C, 3 * C, *L["pads"], att,
                                  H * W * C, C, B, H, W, hd, C // hd, 7, (C // hd) ** -0.5)
-            x2 = self._mlp(None, L["n2"], L["fc1"], L["fc2"], 1e-6, fc1_ln=L.get("fc1_ln"), proj=(att, L["proj"], x), image=L.get("mlp_s3"))
+            x2 = self._mlp(att, L["proj"], x, L["n2"], L["fc1"], L["fc2"], 1e-6, fc1_ln=L.get("fc1_ln"), image=L.get("mlp_s3"))
             # ---- PEG (twins.py:793-808)
             x3 = _new(N, C, dev)
             ops.dwconv3x3_residual(x2, t[f"peg{s}"][0], t[f"peg{s}"][1], x3, B, H, W, C)
@@ -335,11 +377,10 @@ class FlowFormer(ParamTree):
             ops.conv_gemm(xsn, Gk["kv"][0], kv, bias=Gk["kv"][1])
             ops.attention_kvlds(q, (H * W * C, C), kv[:, :C], (Nk * 2 * C, 2 * C), kv[:, C:], (Nk * 2 * C, 2 * C), att,
                                 (H * W * C, C), B, hd, H * W, Nk, C // hd, (C // hd) ** -0.5)
-            if trace is not None:
-                trace.append(dict(H=H, W=W, pe=x.clone(), lsa=x2.clone(), peg=x3.clone()))
-            x = self._mlp(None, Gk["n2"], Gk["fc1"], Gk["fc2"], 1e-6, fc1_ln=Gk.get("fc1_ln"), proj=(att, Gk["proj"], x3), image=Gk.get("mlp_s3"))
-            if trace is not None:
-                trace[-1]["gsa"] = x.clone()
+            rec = _record(trace)
+            _keep(rec, H=H, W=W, pe=x, lsa=x2, peg=x3)
+            x = self._mlp(att, Gk["proj"], x3, Gk["n2"], Gk["fc1"], Gk["fc2"], 1e-6, fc1_ln=Gk.get("fc1_ln"), image=Gk.get("mlp_s3"))
+            _keep(rec, gsa=x)
         return x, H, W
 
     # ------------------------------------------------------------------ cost-volume encoder
@@ -376,39 +417,44 @@ class FlowFormer(ParamTree):
         ops.patch_embed(cost_maps, pe["embed11"], pe["f0"][0].stride(0), self._const[key], s1, s2, s3, s4, f, M, H2, W2)
         return f, P
 
-    def _latent_layer(self, L, x, M, first, tokens=None, P=0):
-        """crossattentionlayer.py:37-56 (first=True: latents x patch tokens) / encoder.py:156-172."""
-        dev = x.device if x is not None else tokens.device
+    def _latent_input(self, L, tokens, M, P):
+        """the input layer: the latents attend to the P patch tokens of each of the M cost maps (crossattentionlayer.py:37-56)
+        -> rows [M*8, 128]."""
+        dev = tokens.device
         lat = self._pk["latents"]
         nl = lat.shape[0]
-        if first:
-            att = _new(M * nl, 128, dev)
-            if nl == 8 and P % 2 == 0 and P <= 64:
-                # scores against the raw tokens with the folded queries, per-pixel softmax + token pooling, then the value
-                # projection per head on the pooled tokens: the [M*P, 256] K|V tensor is never built
-                S = _new(M * P, nl * 8, dev)
-                ops.conv_gemm(tokens, L["qfold"], S)
-                z = _new(M * nl * 8, 128, dev)
-                ops.latent_pool(S, tokens, z, M, P)
-                ops.conv_gemm(z.view(M * nl, 8 * 128)[:, :128], L["wv_heads"][:16], att[:, :16], batch=8, bsa=128, bsw=16 * 128, bsc=16)
-                proj_b = L["proj_b_fold"]
-            else:
-                qn = _new(nl, 128, dev)
-                ops.layernorm(lat, L["n1"][0], L["n1"][1], qn, 1e-5)
-                q = _new(nl, 128, dev)
-                ops.conv_gemm(qn, L["q"][0], q, bias=L["q"][1])
-                kv = _new(M * P, 256, dev)
-                ops.conv_gemm(tokens, L["kv"][0], kv, bias=L["kv"][1])
-                ops.attention_small(q, (0, 128), kv[:, :128], (P * 256, 256), kv[:, 128:], (P * 256, 256), att, (nl * 128, 128),
-                                    M, 8, nl, P, 16, 16 ** -0.5)
-                proj_b = L["proj"][1]
-            x1 = _new(M * nl, 128, dev)
-            ops.conv_gemm(att, L["proj"][0], x1, bias=proj_b, aux0=lat, row_mod=nl)
-            # LayerNorm -> ffn.0 + GELU -> ffn.3 + residual, one launch
-            o = _new(M * nl, 128, dev)
-            if L.get("mlp_s3_plain") is not None:
-                return ops.mlp128(x1, o, L["f0_ln"][0], L["f0_ln"][1], L["f3"][0], L["f3"][1], ln_eps=1e-5, image=L["mlp_s3_plain"])
-            return ops.linear_chain128(x1, o, [dict(w=L["f0_ln"][0], bias=L["f0_ln"][1], act="gelu", ln_eps=1e-5), dict(w=L["f3"][0], bias=L["f3"][1], res=0)])
+        att = _new(M * nl, 128, dev)
+        if nl == 8 and P % 2 == 0 and P <= 64:
+            # scores against the raw tokens with the folded queries, per-pixel softmax + token pooling, then the value
+            # projection per head on the pooled tokens: the [M*P, 256] K|V tensor is never built
+            S = _new(M * P, nl * 8, dev)
+            ops.conv_gemm(tokens, L["qfold"], S)
+            z = _new(M * nl * 8, 128, dev)
+            ops.latent_pool(S, tokens, z, M, P)
+            ops.conv_gemm(z.view(M * nl, 8 * 128)[:, :128], L["wv_heads"][:16], att[:, :16], batch=8, bsa=128, bsw=16 * 128, bsc=16)
+            proj_b = L["proj_b_fold"]
+        else:
+            qn = _new(nl, 128, dev)
+            ops.layernorm(lat, L["n1"][0], L["n1"][1], qn, 1e-5)
+            q = _new(nl, 128, dev)
+            ops.conv_gemm(qn, L["q"][0], q, bias=L["q"][1])
+            kv = _new(M * P, 256, dev)
+            ops.conv_gemm(tokens, L["kv"][0], kv, bias=L["kv"][1])
+            ops.attention_small(q, (0, 128), kv[:, :128], (P * 256, 256), kv[:, 128:], (P * 256, 256), att, (nl * 128, 128),
+                                M, 8, nl, P, 16, 16 ** -0.5)
+            proj_b = L["proj"][1]
+        x1 = _new(M * nl, 128, dev)
+        ops.conv_gemm(att, L["proj"][0], x1, bias=proj_b, aux0=lat, row_mod=nl)
+        # LayerNorm -> ffn.0 + GELU -> ffn.3 + residual, one launch
+        o = _new(M * nl, 128, dev)
+        if L.get("mlp_s3_plain") is not None:
+            return ops.mlp128(x1, o, L["f0_ln"][0], L["f0_ln"][1], L["f3"][0], L["f3"][1], ln_eps=1e-5, image=L["mlp_s3_plain"])
+        return ops.linear_chain128(x1, o, [dict(w=L["f0_ln"][0], bias=L["f0_ln"][1], act="gelu", ln_eps=1e-5), dict(w=L["f3"][0], bias=L["f3"][1], res=0)])
+
+    def _latent_self(self, L, x, M):
+        """a self-attention layer over the 8 latents of each of the M cost maps (encoder.py:156-172); x rows [M*8, 128]."""
+        dev = x.device
+        nl = self._pk["latents"].shape[0]
         qkv = _new(M * nl, 384, dev)
         if L.get("qkv_s3") is not None:
             ops.rowlin128_split3(x, qkv, L["qkv_s3"], ln_eps=1e-5)
@@ -463,7 +509,7 @@ class FlowFormer(ParamTree):
             sl = slice(b * N * nl, (b + 1) * N * nl)
             ops.window_attention(q[sl], k[sl], v[sl], 3 * C, nl * 3 * C, qp, kp, vp, att[sl], C, nl * C, nl, H1, W1, 8, 16, 7,
                                  16 ** -0.5)
-        x2 = self._mlp(None, V["ln2"], V["lfc1"], V["lfc2"], 1e-5, fc1_ln=V["lfc1_ln"], proj=(att, V["lproj"], x), image=V.get("lmlp_s3"))
+        x2 = self._mlp(att, V["lproj"], x, V["ln2"], V["lfc1"], V["lfc2"], 1e-5, fc1_ln=V["lfc1_ln"], image=V.get("lmlp_s3"))
         # ---------------- global block
         ops.layernorm(x2, V["gn1"][0], V["gn1"][1], y, 1e-5)
         z = _new(B * N, Cq, dev)
@@ -503,7 +549,7 @@ class FlowFormer(ParamTree):
             kb = kv[b * Nk:]
             ops.attention_kvlds(q[sl], (C, nl * C), kb[:, :C], (B * Nk * 2 * C, 2 * C), kb[:, C:], (B * Nk * 2 * C, 2 * C),
                                 att[sl], (C, nl * C), nl, 8, N, Nk, 16, 16 ** -0.5)
-        return self._mlp(None, V["gn2"], V["gfc1"], V["gfc2"], 1e-5, fc1_ln=V["gfc1_ln"], extra_res=extra_res, proj=(att, V["gproj"], x2), image=V.get("gmlp_s3"))
+        return self._mlp(att, V["gproj"], x2, V["gn2"], V["gfc1"], V["gfc2"], 1e-5, fc1_ln=V["gfc1_ln"], image=V.get("gmlp_s3"), extra_res=extra_res)
 
     def _cost_encoder(self, cost_maps, ctx, B, H1, W1, trace=None):
         """CostPerceiverEncoder.forward (encoder.py:258-287) -> cost memory rows [B*N*8, 128].  trace (a dict): the PatchEmbed tokens, the input
@@ -511,21 +557,18 @@ class FlowFormer(ParamTree):
         pk = self._pk
         M = B * H1 * W1
         tokens, P = self._patch_embed(cost_maps, M, H1, W1)
-        x = self._latent_layer(pk["xin"], None, M, True, tokens, P)
-        if trace is not None:
-            trace.update(tokens=tokens.clone(), latent_in=x.clone(), self=[], vert=[])
+        x = self._latent_input(pk["xin"], tokens, M, P)
+        _keep(trace, tokens=tokens, latent_in=x, self=[], vert=[])
         short = x
         nl = pk["latents"].shape[0]
         for i in range(HP["encoder_depth"]):
-            x = self._latent_layer(pk["self"][i], x, M, False)
-            if trace is not None:
-                trace["self"].append(x.clone())
+            x = self._latent_self(pk["self"][i], x, M)
+            _keep(trace, self=[x])
             # cost_encoder_res (encoder.py:281-282) adds the short-cut to the output of the last layer: a second residual operand
             # in that layer's final GEMM epilogue (no add pass, one k/v projection in the decoder)
             x = self._vertical(pk["vert"][i], x, ctx, B, H1, W1, nl, extra_res=short if i == HP["encoder_depth"] - 1 else None)
-            if trace is not None:
-                trace["vert"].append(x.clone())
-        return x, None
+            _keep(trace, vert=[x])
+        return x
 
     # ------------------------------------------------------------------ decoder
     def _gru_tables(self, inp, B, H1, W1):
@@ -561,74 +604,51 @@ class FlowFormer(ParamTree):
         plane image once the iteration is done)."""
         D = self._pk["dec"]
         N = H1 * W1
-        hxA, hxB, corr = S["hxA"], S["hxB"], S["corr"]
+        s3 = S["s3"]
+        hxA = S["hxA"]
+        net, motion, flow, agg = hxA[:, :128], hxA[:, 128:254], hxA[:, 254:256], hxA[:, 256:]
         g3 = (B, H1, W1, 3, 3, 1, 1, 1, 1)
-        if S["s3"]:
-            W3 = D["s3"]
-            hxA_p = S["hxA_p"]
-            # convc1 (K = 160) stays on the fp32 kernel and emits cor1's planes; flow_encode emits flo1's and the flow's two channels
-            if trace is not None:
-                trace.update(coords_in=coords1.clone(), net_in=hxA[:, :128].clone())
-            ops.conv_gemm(corr, D["convc1"][0], S["cor1"], bias=D["convc1"][1], act="relu", out_planes=S["cor1_p"])
-            ops.flow_encode_split3(coords1, D["convf1"][0], D["convf1"][1], S["flo1"], hxA[:, 254:256], B, H1, W1, S["flo1_p"], (hxA_p, 254))
-            ops.conv_gemm_pair((S["cor1_p"], W3["convc2"], S["corflo"][:, :192],
-                                dict(geom=g3, bias=D["convc2"][1], act="relu", out_planes=S["corflo_p"].cols(0, 192), no_f32=True)),
-                               (S["flo1_p"], W3["convf2"], S["corflo"][:, 192:],
-                                dict(geom=g3, bias=D["convf2"][1], act="relu", out_planes=S["corflo_p"].cols(192, 256), no_f32=True)))
-            if trace is not None:
-                trace.update(cor1=S["cor1"].clone(), flo1=S["flo1"].clone(), flow=hxA[:, 254:256].clone(), corflo_p=_planes_copy(S["corflo_p"]))
-            ops.conv_gemm(S["corflo_p"], W3["conv"], hxA[:, 128:254], geom=g3, bias=D["conv"][1], act="relu", out_planes=hxA_p.cols(128, 256))
-            if trace is not None:
-                trace.update(motion=hxA[:, 128:254].clone())
-            # the aggregate reads the whole attention matrix every iteration and is HBM-bound either way (fp32: 134 MB per launch, 64.8 us in
-            # the chain; planes: 201 MB, 66.2 us): it stays on the fp32 kernel, whose epilogue emits the planes of its result
-            ops.gma_aggregate(attn, hxA[:, 128:256], D["to_v"], D["gamma"], S["vT"], hxA[:, 256:], B, N, out_planes=hxA_p.cols(256, 384))
-            if trace is not None:
-                trace.update(aggregate=hxA[:, 256:].clone())
-            ops.sepconv_gru_split3(hxA, hxA_p, S["hxB_p"], S["zbuf"], gru_tab["1"], gru_tab["2"], W3["zr1"], W3["q1"], W3["zr2"], W3["q2"], B, H1, W1)
-            if trace is not None:
-                trace.update(gru=hxA[:, :128].clone())
-            ops.conv_gemm(hxA_p.cols(0, 128), W3["fh1"], S["fh"], geom=g3, bias=D["fh1"][1], act="relu")
-            ops.conv_gemm(S["fh"], D["fh2"][0], coords1, geom=g3, bias=D["fh2"][1], epi="add", aux1=coords1)
-            if trace is not None:
-                trace.update(fh=S["fh"].clone(), coords_out=coords1.clone(), hxA=hxA.clone(),
-                             planes={k: _planes_copy(S[k]) for k in ("hxA_p", "cor1_p", "flo1_p", "corflo_p")})
-            return
-        if trace is not None:
-            trace.update(coords_in=coords1.clone(), net_in=hxA[:, :128].clone())
-        ops.conv_gemm(corr, D["convc1"][0], S["cor1"], bias=D["convc1"][1], act="relu")
-        ops.flow_encode(coords1, D["convf1"][0], D["convf1"][1], S["flo1"], hxA[:, 254:256], B, H1, W1)      # :321, gru.py:251,254
+        _keep(trace, coords_in=coords1, net_in=net)
+        # convc1 (K = 160) stays on the fp32 kernel; flow_encode also writes the flow's two channels (decoder.py:321, gru.py:251,254)
+        ops.conv_gemm(S["corr"], D["convc1"][0], S["cor1"], bias=D["convc1"][1], act="relu", **_emit(S, "cor1", 0, 256))
+        enc = (coords1, D["convf1"][0], D["convf1"][1], S["flo1"], flow, B, H1, W1)
+        if s3:
+            ops.flow_encode_split3(*enc, S["flo1_p"], (S["hxA_p"], 254))
+        else:
+            ops.flow_encode(*enc)
         # convc2 (384 tiles) and convf2 (128 tiles) are independent and ready together: one launch, two workgroups per CU, no
-        # split-K slabs (gru.py:252-253)
-        ops.conv_gemm_pair((S["cor1"], D["convc2"][0], S["corflo"][:, :192], dict(geom=g3, bias=D["convc2"][1], act="relu")),
-                           (S["flo1"], D["convf2"][0], S["corflo"][:, 192:], dict(geom=g3, bias=D["convf2"][1], act="relu")))
-        if trace is not None:
-            trace.update(cor1=S["cor1"].clone(), flo1=S["flo1"].clone(), flow=hxA[:, 254:256].clone(), corflo=S["corflo"].clone())
-        ops.conv_gemm(S["corflo"], D["conv"][0], hxA[:, 128:254], geom=g3, bias=D["conv"][1], act="relu")
-        if trace is not None:
-            trace.update(motion=hxA[:, 128:254].clone())
-        # GMA aggregate: v^T = Wv . mf^T, out = mf + gamma * attn @ v
-        ops.gma_aggregate(attn, hxA[:, 128:256], D["to_v"], D["gamma"], S["vT"], hxA[:, 256:], B, N)
-        if trace is not None:
-            trace.update(aggregate=hxA[:, 256:].clone())
+        # split-K slabs (gru.py:252-253).  On the exact-split pass corflo leaves as planes only.
+        ops.conv_gemm_pair((_act(S, "cor1", 0, 256), _wt(D, S, "convc2"), S["corflo"][:, :192],
+                            dict(geom=g3, bias=D["convc2"][1], act="relu", **_emit(S, "corflo", 0, 192, no_f32=True))),
+                           (_act(S, "flo1", 0, 128), _wt(D, S, "convf2"), S["corflo"][:, 192:],
+                            dict(geom=g3, bias=D["convf2"][1], act="relu", **_emit(S, "corflo", 192, 256, no_f32=True))))
+        corflo = _act(S, "corflo", 0, 256)
+        _keep(trace, cor1=S["cor1"], flo1=S["flo1"], flow=flow, **{"corflo_p" if s3 else "corflo": corflo})
+        ops.conv_gemm(corflo, _wt(D, S, "conv"), motion, geom=g3, bias=D["conv"][1], act="relu", **_emit(S, "hxA", 128, 256))
+        _keep(trace, motion=motion)
+        # GMA aggregate: v^T = Wv . mf^T, out = mf + gamma * attn @ v.  It reads the whole attention matrix every iteration and is HBM-bound
+        # either way (fp32: 134 MB per launch, 64.8 us in the chain; planes: 201 MB, 66.2 us): it stays on the fp32 kernel, whose epilogue
+        # emits the planes of its result
+        ops.gma_aggregate(attn, hxA[:, 128:256], D["to_v"], D["gamma"], S["vT"], agg, B, N, **_emit(S, "hxA", 256, 384))
+        _keep(trace, aggregate=agg)
         # SepConvGRU: horizontal 1x5 then vertical 5x1
-        ops.sepconv_gru(hxA, hxB, S["zbuf"], gru_tab["1"], gru_tab["2"], D["zr1"], D["q1"], D["zr2"], D["q2"], B, H1, W1)
-        if trace is not None:
-            trace.update(gru=hxA[:, :128].clone())
-        ops.conv_gemm(hxA[:, :128], D["fh1"][0], S["fh"], geom=g3, bias=D["fh1"][1], act="relu")
+        gru = (S["zbuf"], gru_tab["1"], gru_tab["2"], *((D["s3"] if s3 else D)[k] for k in ("zr1", "q1", "zr2", "q2")), B, H1, W1)
+        if s3:
+            ops.sepconv_gru_split3(hxA, S["hxA_p"], S["hxB_p"], *gru)
+        else:
+            ops.sepconv_gru(hxA, S["hxB"], *gru)
+        _keep(trace, gru=net)
+        ops.conv_gemm(_act(S, "hxA", 0, 128), _wt(D, S, "fh1"), S["fh"], geom=g3, bias=D["fh1"][1], act="relu")
         ops.conv_gemm(S["fh"], D["fh2"][0], coords1, geom=g3, bias=D["fh2"][1], epi="add", aux1=coords1)
-        if trace is not None:
-            trace.update(fh=S["fh"].clone(), coords_out=coords1.clone(), hxA=hxA.clone())
+        _keep(trace, fh=S["fh"], coords_out=coords1, hxA=hxA)
+        if s3:
+            _keep(trace, planes={k: S[k] for k in ("hxA_p", "cor1_p", "flo1_p", "corflo_p")})
 
     def _mask_head(self, S, B, H1, W1, trace=None):
         """mask = .25 * conv1x1(relu(conv3x3(net))) (gru.py:315-318,333) -> rows [R, 576]."""
         D = self._pk["dec"]
-        if S["s3"]:
-            ops.conv_gemm(S["hxA_p"].cols(0, 128), D["s3"]["m0"], S["fh"], geom=(B, H1, W1, 3, 3, 1, 1, 1, 1), bias=D["m0"][1], act="relu")
-        else:
-            ops.conv_gemm(S["hxA"][:, :128], D["m0"][0], S["fh"], geom=(B, H1, W1, 3, 3, 1, 1, 1, 1), bias=D["m0"][1], act="relu")
-        if trace is not None:
-            trace.update(mask_hidden=S["fh"].clone())
+        ops.conv_gemm(_act(S, "hxA", 0, 128), _wt(D, S, "m0"), S["fh"], geom=(B, H1, W1, 3, 3, 1, 1, 1, 1), bias=D["m0"][1], act="relu")
+        _keep(trace, mask_hidden=S["fh"])
         mask = _new(S["hxA"].shape[0], 576, S["hxA"].device)
         ops.conv_gemm(S["fh"], D["m2"][0], mask, bias=D["m2"][1], alpha=0.25)
         return mask
@@ -642,21 +662,18 @@ class FlowFormer(ParamTree):
         R = B * N
         S = self._update_state(R, B, N, dev)
         inp = _new(R, 128, dev)
-        ops.conv_gemm(ctx, D["proj_net"][0], S["hxA"][:, :128], bias=D["proj_net"][1], act="tanh",
-                      out_planes=S["hxA_p"].cols(0, 128) if S["s3"] else None)
+        ops.conv_gemm(ctx, D["proj_net"][0], S["hxA"][:, :128], bias=D["proj_net"][1], act="tanh", **_emit(S, "hxA", 0, 128))
         ops.conv_gemm(ctx, D["proj_inp"][0], inp, bias=D["proj_inp"][1], act="relu")
         gru_tab = self._gru_tables(inp, B, H1, W1)
         qk = _new(R, 256, dev)
         attn = torch.empty((B, N, N), device=dev)
         ops.gma_attention(inp, D["qk"], qk, attn, B, N)
-        if trace is not None:
-            trace.update(net=S["hxA"][:, :128].clone(), inp=inp.clone(), gru_tab={k: v.clone() for k, v in gru_tab.items()}, attn=attn.clone(),
-                         qk=qk.clone())
-            if S["s3"]:
-                trace.update(net_p=_planes_copy(S["hxA_p"]))
+        _keep(trace, net=S["hxA"][:, :128], inp=inp, gru_tab=gru_tab, attn=attn, qk=qk)
+        if S["s3"]:
+            _keep(trace, net_p=S["hxA_p"])
         return dict(S=S, inp=inp, gru_tab=gru_tab, attn=attn, qk=qk)
 
-    def _decoder(self, mem, mem_short, ctx, cost_maps, B, H1, W1, iters, trace=None, flow_init=None):
+    def _decoder(self, mem, ctx, cost_maps, B, H1, W1, iters, trace=None, flow_init=None):
         """MemoryDecoder.forward eval branch (decoder.py:262-344).  trace (a list whose last entry is the encoder's record): the prologue goes
         into that record's "prologue", then one record per iteration (coords1, net and corr after it, plus _update_block's sub-stages); the
         last one also holds the mask head and the upsampled flow.  flow_init ([B,2,H1,W1], low-res pixels): the refinement starts from
@@ -666,42 +683,34 @@ class FlowFormer(ParamTree):
         N = H1 * W1
         R = B * N
         nl = self._pk["latents"].shape[0]
-        pre = self._decoder_prologue(ctx, B, H1, W1, trace=None if trace is None else trace[-1].setdefault("prologue", {}))
+        pro = None if trace is None else trace[-1].setdefault("prologue", {})
+        pre = self._decoder_prologue(ctx, B, H1, W1, trace=pro)
         S, gru_tab, attn = pre["S"], pre["gru_tab"], pre["attn"]
-        # k, v of the cost-memory cross attention, once (decoder.py:68-70); memory = x + short_cut (linear -> two GEMMs)
-        ca = D["ca"]
+        # k, v of the cost-memory cross attention, once (decoder.py:68-70)
         kv = _new(R * nl, 128, dev)
-        if mem_short is None:
-            ops.conv_gemm(mem, ca["kv"][0], kv, bias=ca["kv"][1])
-        else:                                                  # memory given as two addends: kv(x + s) = kv(x) + kv(s)
-            kv0 = _new(R * nl, 128, dev)
-            ops.conv_gemm(mem_short, ca["kv"][0], kv0, bias=ca["kv"][1])
-            ops.conv_gemm(mem, ca["kv"][0], kv, aux0=kv0)
-        if trace is not None:
-            trace[-1]["prologue"]["kv"] = kv.clone()
+        ops.conv_gemm(mem, D["ca"]["kv"][0], kv, bias=D["ca"]["kv"][1])
+        _keep(pro, kv=kv)
         coords1 = _new(R, 2, dev)
         ops.coords_grid(coords1, B, H1, W1, init=flow_init)
         for it in range(iters):
             ops.cost_lookup9x9(cost_maps, coords1, S["corr"], R, H1, W1)                              # decoder.py:291
             # flow_token_encoder + cost-memory cross attention + FFN: one fused launch (decoder.py:305-312)
             ops.decoder_token_chain(S["corr"], coords1, kv, D["chain16"], R, nl)
-            rec = None if trace is None else {}
+            rec = _record(trace)
             self._update_block(S, coords1, attn, gru_tab, B, H1, W1, trace=rec)
-            if trace is not None:
-                rec.update(coords1=coords1.clone(), net=S["hxA"][:, :128].clone(), corr=S["corr"].clone())
-                trace.append(rec)
+            _keep(rec, coords1=coords1, net=S["hxA"][:, :128], corr=S["corr"])
         # mask head + convex upsampling, last iteration only (gru.py:315-318,333; decoder.py:214-225)
-        mask = self._mask_head(S, B, H1, W1, trace=None if trace is None else trace[-1])
+        last = None if trace is None else trace[-1]
+        mask = self._mask_head(S, B, H1, W1, trace=last)
         flow_up = torch.empty((B, 2, 8 * H1, 8 * W1), device=dev)
         ops.convex_upsample(coords1, mask, flow_up, B, H1, W1)
-        if trace is not None:
-            trace[-1].update(mask=mask.clone(), flow_up=flow_up.clone())
+        _keep(last, mask=mask, flow_up=flow_up)
         return flow_up, coords1
 
     # ================================================================== forward
-    def flow_rows(self, image1, image2, iters=None, trace=None, flow_init=None):
-        """images NCHW 0..255 -> (flow_up [B,2,H,W], coords1 rows [B*N,2], (B,H1,W1)).  flow_init [B,2,H/8,W/8] (low-res pixels): warm
-        start of the refinement, as the reference's flow_init."""
+    def _forward(self, image1, image2, iters, trace, flow_init, pair):
+        """prep -> context encoder -> feature encoder -> all-pairs volume -> cost encoder -> decoder.  pair: both directions as one batch of
+        2B (flow_rows_pair: context of both images, the volume and its transpose); otherwise image1 -> image2 at batch B (flow_rows)."""
         if not image1.is_cuda:
             raise RuntimeError("FlowFormer runs on the MI355X HIP kernels only: move the module and inputs to cuda")
         pk = self._pk or self.pack()
@@ -710,21 +719,32 @@ class FlowFormer(ParamTree):
         if H % 32 or W % 32:
             raise RuntimeError(f"input size {H}x{W} must be a multiple of 32 (reference runs both nets at 512x512)")
         dev = image1.device
+        Bd = 2 * B if pair else B                                   # the batch of the context encoder, the cost encoder and the decoder
         tr = None if trace is None else dict(cnet=[], fnet=[], encoder={})
         x = _new(2 * B * H * W, 4, dev)
         ops.prep_image(image1.contiguous(), x[:B * H * W], 4, 2.0, 255.0, 1.0)        # transformer.py:53-54
         ops.prep_image(image2.contiguous(), x[B * H * W:], 4, 2.0, 255.0, 1.0)
-        ctx, H1, W1 = self._twins(pk["cnet"], x[:B * H * W], B, H, W, trace=tr and tr["cnet"])      # context = cnet(image1)
+        # context = cnet(image1); pair: of image1 (pass 1 -> 2) then of image2 (pass 2 -> 1)
+        ctx, H1, W1 = self._twins(pk["cnet"], x if pair else x[:B * H * W], Bd, H, W, trace=tr and tr["cnet"])
         feats, _, _ = self._twins(pk["fnet"], x, 2 * B, H, W, trace=tr and tr["fnet"])             # fnet(image1), fnet(image2)
         N = H1 * W1
         feats = feats.view(2, B, N, 256)
-        cost_maps = torch.empty((B * N, N), device=dev)                              # all-pairs volume (encoder.py:359-369)
-        ops.corr_volume(feats[0], feats[1], cost_maps.view(B, N, N))
-        mem, short = self._cost_encoder(cost_maps, ctx, B, H1, W1, trace=tr and tr["encoder"])
+        cost_maps = torch.empty((Bd * N, N), device=dev)                             # all-pairs volume (encoder.py:359-369)
+        if pair:
+            # the reverse direction's volume is the transpose of the forward one: one product, two stores
+            ops.corr_volume_both(feats[0], feats[1], cost_maps[:B * N].view(B, N, N), cost_maps[B * N:].view(B, N, N))
+        else:
+            ops.corr_volume(feats[0], feats[1], cost_maps.view(B, N, N))
+        mem = self._cost_encoder(cost_maps, ctx, Bd, H1, W1, trace=tr and tr["encoder"])
         if trace is not None:
-            trace.append(dict(context=ctx, feats=feats, cost_maps=cost_maps, mem=mem, short=short, **tr))
-        flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, B, H1, W1, iters, trace, flow_init=flow_init)
-        return flow_up, coords1, (B, H1, W1)
+            trace.append(dict(context=ctx, feats=feats, cost_maps=cost_maps, mem=mem, **tr))
+        flow_up, coords1 = self._decoder(mem, ctx, cost_maps, Bd, H1, W1, iters, trace, flow_init=flow_init)
+        return flow_up, coords1, (Bd, H1, W1)
+
+    def flow_rows(self, image1, image2, iters=None, trace=None, flow_init=None):
+        """images NCHW 0..255 -> (flow_up [B,2,H,W], coords1 rows [B*N,2], (B,H1,W1)).  flow_init [B,2,H/8,W/8] (low-res pixels): warm
+        start of the refinement, as the reference's flow_init."""
+        return self._forward(image1, image2, iters, trace, flow_init, pair=False)
 
     def flow_rows_pair(self, image_a, image_b, iters=None, trace=None, flow_init=None):
         """Both directions at once: returns flow_up [2B,2,H,W] = [flow a->b ; flow b->a].
@@ -739,30 +759,7 @@ class FlowFormer(ParamTree):
         one record per refinement iteration); the hooks only clone tensors, so the launch sequence is the same with and without it.
 
         flow_init [2B,2,H/8,W/8] (low-res pixels): the warm start of both passes, a->b first, then b->a (the batch order above)."""
-        if not image_a.is_cuda:
-            raise RuntimeError("FlowFormer runs on the MI355X HIP kernels only: move the module and inputs to cuda")
-        pk = self._pk or self.pack()
-        iters = HP["decoder_depth"] if iters is None else iters
-        B, _, H, W = image_a.shape
-        if H % 32 or W % 32:
-            raise RuntimeError(f"input size {H}x{W} must be a multiple of 32 (reference runs both nets at 512x512)")
-        dev = image_a.device
-        tr = None if trace is None else dict(cnet=[], fnet=[], encoder={})
-        x = _new(2 * B * H * W, 4, dev)
-        ops.prep_image(image_a.contiguous(), x[:B * H * W], 4, 2.0, 255.0, 1.0)
-        ops.prep_image(image_b.contiguous(), x[B * H * W:], 4, 2.0, 255.0, 1.0)
-        ctx, H1, W1 = self._twins(pk["cnet"], x, 2 * B, H, W, trace=tr and tr["cnet"])          # context of a (pass a->b) then of b (pass b->a)
-        feats, _, _ = self._twins(pk["fnet"], x, 2 * B, H, W, trace=tr and tr["fnet"])
-        N = H1 * W1
-        feats = feats.view(2, B, N, 256)
-        cost_maps = torch.empty((2 * B * N, N), device=dev)
-        # the reverse direction's volume is the transpose of the forward one: one product, two stores
-        ops.corr_volume_both(feats[0], feats[1], cost_maps[:B * N].view(B, N, N), cost_maps[B * N:].view(B, N, N))
-        mem, short = self._cost_encoder(cost_maps, ctx, 2 * B, H1, W1, trace=tr and tr["encoder"])
-        if trace is not None:
-            trace.append(dict(context=ctx, feats=feats, cost_maps=cost_maps, mem=mem, short=short, **tr))
-        flow_up, coords1 = self._decoder(mem, short, ctx, cost_maps, 2 * B, H1, W1, iters, trace, flow_init=flow_init)
-        return flow_up, coords1, (2 * B, H1, W1)
+        return self._forward(image_a, image_b, iters, trace, flow_init, pair=True)
 
     def forward(self, image1, image2, mask=None, output=None, flow_init=None):
         """Reference surface (transformer.py:47-65, eval): returns (flow_up, flow_lowres).  flow_init [B,2,H/8,W/8] in low-resolution

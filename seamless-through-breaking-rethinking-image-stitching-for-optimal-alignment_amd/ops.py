@@ -459,7 +459,6 @@ def forward_interpolate(flow, out=None, *, coords_rows=None):
     check(lib.st_flow_forward_interpolate(_p(flow), 0 if coords_rows is None else 1, _p(out), B, H, W, _stream()),
           "st_flow_forward_interpolate")
     return out
-    return out
 
 
 def flow_from_coords(coords1, flow4, dst2, B, H, W):
@@ -601,13 +600,6 @@ def sepconv_gru(hxA, hxB, zbuf, tab1, tab2, w_zr1, w_q1, w_zr2, w_q2, B, H, W):
     check(lib.st_sepconv_gru(_p(hxA), _p(hxB), _ld(hxA), _pc(zbuf), _p(tab1), _p(tab2), _ld(tab1), _pc(w_zr1), _pc(w_q1),
                              _pc(w_zr2), _pc(w_q2), B, H, W, *_ws(hxA.device), _stream()), "st_sepconv_gru")
     return hxA
-
-
-def grid_sample_blend(x, flow, mul, out):
-    B, Cc, H, W = x.shape
-    check(lib.st_grid_sample_blend(_pc(x), _pc(flow), _pc(mul) if mul is not None else None, _pc(out), B, Cc, H, W,
-                                   _stream()), "st_grid_sample_blend")
-    return out
 
 
 def convex_upsample(coords1, mask, out, B, H, W):

@@ -84,9 +84,9 @@ def test_cost_encoder_blocks(model, golden_ops, seeded_sd):
     tok, P = fb._patch_embed(cm.reshape(8, -1).cuda().contiguous(), 8, 64, 64)
     assert P == 64
     check("pe_out_abs", (tok.cpu().view(8, 64, 128) - T(g["pe_out"])).abs().max(), 1e-5)      # measured 3.04e-06
-    x = fb._latent_layer(fb._pk["xin"], None, 6, True, T(g["xattn_tokens"]).reshape(-1, 128).cuda().contiguous(), 64)
+    x = fb._latent_input(fb._pk["xin"], T(g["xattn_tokens"]).reshape(-1, 128).cuda().contiguous(), 6, 64)
     check("xattn_out_abs", (x.cpu().view(6, 8, 128) - T(g["xattn_out"])).abs().max(), 5e-6)      # measured 1.43e-06
-    y = fb._latent_layer(fb._pk["self"][1], T(g["sattn_in"]).reshape(-1, 128).cuda().contiguous(), 6, False)
+    y = fb._latent_self(fb._pk["self"][1], T(g["sattn_in"]).reshape(-1, 128).cuda().contiguous(), 6)
     check("sattn_out_abs", (y.cpu().view(6, 8, 128) - T(g["sattn_out"])).abs().max(), 6e-6)      # measured 1.79e-06
     vx, vctx = T(g["vert_x"]), T(g["vert_ctx"])            # [8 latents, 192 px, 128], [1,256,12,16]
     xr = vx.permute(1, 0, 2).reshape(-1, 128).cuda().contiguous()      # rows (n, l)
