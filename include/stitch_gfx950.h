@@ -254,7 +254,10 @@ int st_sine_pe(float* out, int32_t ld, int32_t rows, int32_t dim, const float* c
                void* stream);
 /* Multi-head softmax attention, element (b, t, h, e) at base + b*bs + t*ts + h*D + e (floats).
  *   _small : one thread per query, K/V from L2 (attention.py:9-68; 8 latents / 1x8 decoder query)
- *   _kvlds : K/V slab (Nk <= 256) staged in LDS (GSA: twins.py:336-392,633-680)                     */
+ *   _kvlds : K/V slab staged in LDS (GSA: twins.py:336-392,633-680); matrix cores for Nk % 16 == 0,
+ *            Nk <= 256, otherwise a VALU kernel while 2*Nk*D floats fit in 160 KiB
+ * D = 8 (small only), 16 or 32.  Rows move as 16-byte vectors: every base pointer 16-byte aligned and
+ * every stride a multiple of 4 floats, else ST_EINVAL (also for _window below and its pad tables). */
 int st_attention_small(const float* q, int64_t q_bs, int64_t q_ts, const float* k, int64_t k_bs, int64_t k_ts,
                        const float* v, int64_t v_bs, int64_t v_ts, float* out, int64_t o_bs, int64_t o_ts,
                        int32_t B, int32_t heads, int32_t Nq, int32_t Nk, int32_t D, float scale, void* stream);

@@ -270,6 +270,10 @@ extern "C" int st_sine_pe(float* out, int32_t ld, int32_t rows, int32_t dim, con
     return ST_OK;
 }
 
+// The attention kernels below read and write q / k / v / out rows as float4: every base pointer must be 16-byte aligned and every
+// batch / token stride a multiple of 4 floats (heads * D is one already: D is 8, 16 or 32).  Checked on the host, before any launch.
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // ---------------------------------------------------------------------------------------------
 // Small multi-head attention: one thread per (batch, head, query), keys/values read straight
 // from L2 (lanes of one (batch, head) share the same K/V addresses -> broadcast).
@@ -292,7 +296,11 @@ __global__ __launch_bounds__(256) void attention_small_kernel(const float* __res
 #pragma unroll
     for (int e = 0; e < D; e += 4) {
         const float4 t = *reinterpret_cast<const float4*>(qp + e);
-        qr[e] = t.x; qr[e + 1] = t.y; qr[e + 2] = t.z; qr[e + 3] = t.w;
+        // scale goes into q, as in the kvlds kernels: both passes below then run the SAME fma chain and the row maximum is one of the
+        // scores the second pass exponentiates.  With `s * scale` taken after the chain the compiler contracted the second pass to
+        // fma(s, scale, -mx) against a maximum of rounded products, so the top key's weight was exp(rounding residual) instead of 1
+        // whenever scale is not a power of two (D = 8, 32): Nk = 1 did not return the V row.  Same bits as before for D = 16.
+        qr[e] = t.x * scale; qr[e + 1] = t.y * scale; qr[e + 2] = t.z * scale; qr[e + 3] = t.w * scale;
     }
     const float* kb = k + b * k_bs + h * D;
     const float* vb = v + b * v_bs + h * D;
@@ -305,7 +313,7 @@ __global__ __launch_bounds__(256) void attention_small_kernel(const float* __res
             const float4 t = *reinterpret_cast<const float4*>(kp + e);
             s = fmaf(qr[e], t.x, s); s = fmaf(qr[e + 1], t.y, s); s = fmaf(qr[e + 2], t.z, s); s = fmaf(qr[e + 3], t.w, s);
         }
-        mx = fmaxf(mx, s * scale);
+        mx = fmaxf(mx, s);
     }
 #pragma unroll
     for (int e = 0; e < D; ++e) acc[e] = 0.f;
@@ -318,7 +326,7 @@ __global__ __launch_bounds__(256) void attention_small_kernel(const float* __res
             const float4 t = *reinterpret_cast<const float4*>(kp + e);
             s = fmaf(qr[e], t.x, s); s = fmaf(qr[e + 1], t.y, s); s = fmaf(qr[e + 2], t.z, s); s = fmaf(qr[e + 3], t.w, s);
         }
-        const float p = __expf(s * scale - mx);
+        const float p = __expf(s - mx);
         sum += p;
         const float* vp = vb + j * v_ts;
 #pragma unroll
@@ -339,6 +347,7 @@ extern "C" int st_attention_small(const float* q, int64_t q_bs, int64_t q_ts, co
                                   const float* v, int64_t v_bs, int64_t v_ts, float* out, int64_t o_bs, int64_t o_ts,
                                   int32_t B, int32_t heads, int32_t Nq, int32_t Nk, int32_t D, float scale, void* stream) {
     if (!q || !k || !v || !out || B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0) return ST_EINVAL;
+    if (!al16(q) || !al16(k) || !al16(v) || !al16(out) || ((q_bs | q_ts | k_bs | k_ts | v_bs | v_ts | o_bs | o_ts) & 3)) return ST_EINVAL;
     const long total = (long)B * heads * Nq;
     dim3 grid((total + 255) / 256), block(256);
     hipStream_t s = (hipStream_t)stream;
@@ -636,8 +645,10 @@ extern "C" int st_attention_kvlds(const float* q, int64_t q_bs, int64_t q_ts, co
                                   const float* v, int64_t v_bs, int64_t v_ts, float* out, int64_t o_bs, int64_t o_ts,
                                   int32_t B, int32_t heads, int32_t Nq, int32_t Nk, int32_t D, float scale, void* stream) {
     if (!q || !k || !v || !out || B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0) return ST_EINVAL;
+    // both kernels: the VALU one used to be handed the strides the MFMA one cannot take, and read them with the same float4 loads
+    if (!al16(q) || !al16(k) || !al16(v) || !al16(out) || ((q_bs | q_ts | k_bs | k_ts | v_bs | v_ts | o_bs | o_ts) & 3)) return ST_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if ((D == 16 || D == 32) && Nk % 16 == 0 && Nk <= 256 && !((q_ts | k_ts | v_ts | o_ts | q_bs | k_bs | v_bs | o_bs) & 3)) {
+    if ((D == 16 || D == 32) && Nk % 16 == 0 && Nk <= 256) {
         const int tpw = Nq >= 8192 ? 4 : 2;                       // 16-query tiles per wave (K/V staging amortised over 128..256 queries)
         const size_t ldsm = (size_t)2 * Nk * (D + 4) * sizeof(float);
         dim3 gridm((Nq + 64 * tpw - 1) / (64 * tpw), heads, B);
@@ -799,6 +810,9 @@ extern "C" int st_window_attention(const float* q, const float* k, const float* 
                                    const float* kpad, const float* vpad, float* out, int64_t o_bs, int64_t o_ts, int32_t B,
                                    int32_t H, int32_t W, int32_t heads, int32_t D, int32_t ws, float scale, void* stream) {
     if (!q || !k || !v || !qpad || !kpad || !vpad || !out || ws * ws > 64 || ws <= 0) return ST_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0 || heads <= 0) return ST_EINVAL;
+    if (!al16(q) || !al16(k) || !al16(v) || !al16(qpad) || !al16(kpad) || !al16(vpad) || !al16(out) || ((bs | ts | o_bs | o_ts) & 3))
+        return ST_EINVAL;
     const int nwh = (H + ws - 1) / ws, nww = (W + ws - 1) / ws;
     dim3 grid(nwh * nww, (heads + 3) / 4, B), block(256);
     const size_t lds = (size_t)4 * 2 * 64 * (D + 4) * sizeof(float);
@@ -885,7 +899,7 @@ __global__ __launch_bounds__(256) void ccl_softargmax_kernel(const float* __rest
 }
 
 extern "C" int st_ccl_softargmax(const float* G, float* out, int32_t ldo, int32_t B, int32_t h, int32_t w, void* stream) {
-    if (!G || !out || h * w > 1024 || ldo < 2) return ST_EINVAL;
+    if (!G || !out || B <= 0 || h <= 0 || w <= 0 || h > 1024 || w > 1024 || h * w > 1024 || ldo < 2) return ST_EINVAL;
     hipLaunchKernelGGL(ccl_softargmax_kernel, dim3(h * w, B), dim3(256), 0, (hipStream_t)stream, G, out, ldo, h, w);
     ST_CHECK_LAUNCH();
     return ST_OK;
