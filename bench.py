@@ -1,6 +1,10 @@
 """Headline benchmark: stitched image-pairs/s at 512x512 (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload 512|1024] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload 512|1024] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds the model, captures the hipGraphs, warms up,
+times the K steps, writes the last step's outputs if ``--dump-outputs`` is given and prints the JSON line.  Every other
+measurement and check of the benchmark (listed at the end) runs only with ``--full``.
 
 N > 1: if the process was not started by ``torch.distributed.run`` it starts
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`` itself (as a child: this parent
@@ -9,13 +13,16 @@ never touches the GPU) and relays rank 0's JSON line; under the driver's own tor
 A step = one pass of the hot path over one synthetic pair:
   --workload 512  (default, BASELINE.json configs[1]): ``FlowHomoAdpater.forward(type="test_eval")`` on a 512x512 pair,
                   batch 1 (1 homography pass, 2 FlowFormer++ passes, warp / occlusion / blend), hipGraph replay, 3 pairs in
-                  flight on 3 HIP streams; the single-stream figure is reported beside it (``value_1_in_flight``)
+                  flight on 3 HIP streams; ``--full`` reports the single-stream figure beside it (``value_1_in_flight``)
   --workload 1024 (configs[3]): ``forward(type="test_out")`` on 1024x1024 pairs, 4 distinct pairs per GPU in turn, batch 1
                   (the canvas is per pair and read back to the host mid-way, so this path is eager, one stream)
 Pairs are independent: ranks shard them with no data-path collective (weak scaling: every rank runs K steps); one RCCL
 all-gather moves the per-pair PSNR at the end.  Inputs and random-init weights are resident in HBM before the timed region.
 
-Besides the contract fields the JSON line carries
+With ``--full`` the JSON line carries, besides the fields of a plain run,
+  value_1_in_flight -- the same graphs with one pair in flight (latency-bound figure)
+  value_exact_fp32  -- the same command on the all-fp32 kernels (``ST_SPLIT3=0``), run as a plain child process
+  harness       -- the product evaluation harness end to end on JPEG pairs on disk (``--harness``, workload 512)
   roofline      -- the dominant kernel family (fp32-MFMA implicit GEMM): algorithmic FLOPs of its launches in one step /
                    their summed HIP-event durations vs the 157.3 TFLOP/s fp32 matrix peak; measured on an instrumented step
                    after the timed region (events on the stream the kernels are launched on); ``traffic`` = HBM bytes per
@@ -48,15 +55,18 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", choices=("512", "1024"), default="512")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-corr-roofline", action="store_true", help="skip the stand-alone corr-volume timing (PMC passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures and checks: one pair in flight, the product "
+                         "harness, the instrumented roofline step, the all-fp32 child run, the corr-volume roofline, the CPU baseline and parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle timing and the parity figures")
+    ap.add_argument("--no-corr-roofline", action="store_true", help="with --full: skip the stand-alone corr-volume timing (PMC passes)")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python instead of replaying the hipGraph")
     ap.add_argument("--streams", type=int, default=3, help="independent forwards in flight per GPU (one hipGraph + HIP stream each)")
     ap.add_argument("--batch", type=int, default=1, help="pairs per forward: 1 = BASELINE configs[1] (default), 8 = configs[2]")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend of the ranks (nccl = RCCL; gloo for CPU rehearsal of the launcher)")
     ap.add_argument("--dry-run", action="store_true", help="launcher/collective plumbing only: no GPU, no model (tests/test_dist_cpu.py)")
     ap.add_argument("--harness", choices=("none", "eval"), default="eval",
-                    help="eval (default, workload 512): also time the PRODUCT harness end to end -- stitch_amd.evaluate.validate_with_model over "
+                    help="with --full; eval (default, workload 512): also time the PRODUCT harness end to end -- stitch_amd.evaluate.validate_with_model over "
                          "--harness-pairs synthetic 512x512 JPEG pairs written to a temp dir (JPEG decode + H2D + forward + metric + final "
                          "copy inside the clock) -> harness_pairs_per_s beside value")
     ap.add_argument("--harness-pairs", type=int, default=240)
@@ -81,7 +91,7 @@ def launcher_command(args, port):
            "--harness-pairs", str(args.harness_pairs), "--harness-batch", str(args.harness_batch)]
     if args.dump_outputs:
         fwd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
-    for flag, on in (("--no-cpu-baseline", args.no_cpu_baseline), ("--no-corr-roofline", args.no_corr_roofline),
+    for flag, on in (("--full", args.full), ("--no-cpu-baseline", args.no_cpu_baseline), ("--no-corr-roofline", args.no_corr_roofline),
                      ("--eager", args.eager), ("--dry-run", args.dry_run), ("--share-gpu", args.share_gpu)):
         if on:
             fwd.append(flag)
@@ -532,6 +542,43 @@ def worker(args):
         dumped = {"dir": os.path.abspath(args.dump_outputs), "arrays": dump_outputs(args.dump_outputs, dict(o, **{mname: m}))}
         log(f"wrote the last timed step's outputs to {dumped['dir']}")
     per_rank_pairs_s = [args.steps * nb / t for t in rank_times]
+
+    from stitch_amd import flowformer
+    split3_on = flowformer.SPLIT3          # the switch that puts the contractions named in `dtype` on the split3 kernels (read at import)
+    out = None
+    if rank == 0:
+        wl = ("synthetic 1024x1024 pairs, 4 per GPU, batch=1, FlowHomoAdpater.forward(type=test_out)" if big else
+              f"UDIS-D-shaped 512x512 pairs, batch={nb}, FlowHomoAdpater.forward(type=test_eval)")
+        out = {
+            "metric": "stitched image-pairs/s at 512x512" if not big else "stitched image-pairs/s at 1024x1024",
+            "value": world * args.steps * nb / dt, "unit": "pairs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": ("f32 (decoder contractions, PatchEmbed's third conv and the C = 128 block tails: exact 3xbf16 split of both operands, 6 products on the bf16 matrix cores, fp32 accumulate -- error vs fp64 "
+                      "0.83x the fp32 MFMA chain's; everything else fp32)") if split3_on else "f32",
+            "data": "synthetic", "full": args.full,
+            "effective_warmup_steps": nstreams + settle + max(args.warmup, nstreams),
+            "config": {"workload": wl, "pairs_per_step_per_gpu": nb,
+                       "launch": "eager" if args.eager else ("hipGraph replay of the network part + eager canvas part" if big else "hipGraph replay"),
+                       "pairs_in_flight": nstreams * nb,
+                       "parallelism": f"pairs sharded over {world} GPU(s), no data-path collective, one all_gather of per-pair metrics"
+                                      + (" [REHEARSAL: all ranks share cuda:0]" if args.share_gpu else "")},
+            "settle_steps": settle,
+            "per_rank_pairs_per_s": {"min": min(per_rank_pairs_s), "max": max(per_rank_pairs_s), "ranks": len(per_rank_pairs_s)},
+            "dump_outputs": dumped,
+        }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
+
+    # ------------------------------------------------------------------------------------------ --full only from here on
     dt1 = None
     if nstreams > 1:
         dt1 = timed(max(10, args.steps // 2), n_in_flight=1)       # same graphs, one pair in flight (latency-bound figure)
@@ -546,16 +593,17 @@ def worker(args):
         inst = instrumented_step((lambda: model(a, b, type="test_out")) if big else (lambda: model(a, b, type="test_eval")))
         flops, gemm_ms, launches, abytes = inst["flops"], inst["ms"], inst["launches"], inst["alg_bytes"]
         tf = flops / gemm_ms / 1e9
-        split3_on = inst["split3_launches"] > 0
+        if split3_on != (inst["split3_launches"] > 0):
+            raise SystemExit(f"bench.py: `dtype` was written for ST_SPLIT3 {'on' if split3_on else 'off'}, but the instrumented step saw "
+                             f"{inst['split3_launches']} split3 launches")
         s3_tf = inst["split3_flops"] / inst["split3_ms"] / 1e9 if split3_on else None
         f32_ms = gemm_ms - inst["split3_ms"]
         value_exact = None
-        if split3_on and world == 1 and not big and nb == 1 and not args.eager and os.environ.get("ST_BENCH_CHILD") != "1":
-            # the same command on the fp32-MFMA kernels of rounds 1-5 (ST_SPLIT3=0), in a child process (the switch is read at import)
+        if split3_on and world == 1 and not big and nb == 1 and not args.eager:
+            # the same steps on the fp32-MFMA kernels of rounds 1-5 (ST_SPLIT3=0), as a plain run in a child process (the switch is read at import)
             log("child run with ST_SPLIT3=0 (value_exact_fp32)")
-            env = dict(os.environ, ST_SPLIT3="0", ST_BENCH_CHILD="1")
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", str(args.warmup), "--streams", str(args.streams),
-                   "--harness", "none", "--no-cpu-baseline", "--no-corr-roofline"]
+            env = dict(os.environ, ST_SPLIT3="0")
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", str(args.warmup), "--streams", str(args.streams)]
             try:
                 cp = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, timeout=400)
                 for ln in cp.stdout.splitlines():
@@ -580,28 +628,12 @@ def worker(args):
                 prof = json.load(open(ppath))
                 psrc = dict(provenance(ppath), how=prof.get("source"))
                 break
-        wl = ("synthetic 1024x1024 pairs, 4 per GPU, batch=1, FlowHomoAdpater.forward(type=test_out)" if big else
-              f"UDIS-D-shaped 512x512 pairs, batch={nb}, FlowHomoAdpater.forward(type=test_eval)")
-        out = {
-            "metric": "stitched image-pairs/s at 512x512" if not big else "stitched image-pairs/s at 1024x1024",
-            "value": world * args.steps * nb / dt, "unit": "pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": ("f32 (decoder contractions, PatchEmbed's third conv and the C = 128 block tails: exact 3xbf16 split of both operands, 6 products on the bf16 matrix cores, fp32 accumulate -- error vs fp64 "
-                      "0.83x the fp32 MFMA chain's; everything else fp32)") if split3_on else "f32",
-            "value_exact_fp32": value_exact, "data": "synthetic",
-            "effective_warmup_steps": nstreams + settle + max(args.warmup, nstreams),
-            "config": {"workload": wl, "pairs_per_step_per_gpu": nb,
-                       "launch": "eager" if args.eager else ("hipGraph replay of the network part + eager canvas part" if big else "hipGraph replay"),
-                       "pairs_in_flight": nstreams * nb,
-                       "parallelism": f"pairs sharded over {world} GPU(s), no data-path collective, one all_gather of per-pair metrics"
-                                      + (" [REHEARSAL: all ranks share cuda:0]" if args.share_gpu else "")},
-            "settle_steps": settle,
+        out.update({
+            "value_exact_fp32": value_exact,
             "harness_pairs_per_s": None if harness is None else harness["pairs_per_s"],
             "harness_batched_pairs_per_s": None if harness is None or not harness.get("batched") else harness["batched"]["pairs_per_s"],
             "harness": harness,
             "value_1_in_flight": None if dt1 is None else world * max(10, args.steps // 2) * nb / dt1,
-            "per_rank_pairs_per_s": {"min": min(per_rank_pairs_s), "max": max(per_rank_pairs_s), "ranks": len(per_rank_pairs_s)},
             "roofline": {"bound": "mfma", "kernel": "GEMM family: conv_gemm_split3_kernel / _kpar_kernel / _pair_kernel / _persist_kernel + rowmlp128_split3_kernel (decoder contractions, PatchEmbed c4, block tails: exact 3xbf16 split on the bf16 matrix cores) + the fp32-MFMA kernels conv_gemm_dma_kernel + rowstream_gemm_kernel + rowmlp128_kernel + rowchain128_kernel + conv_gemm_kernel + skinny / narrow variants + split-K reducers (every st_conv_gemm / st_mlp128 / st_linear_chain128 launch of one step)",
                          "achieved": tf, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / FP32_MFMA_PEAK_TFLOPS,
                          "frac_note": "fp32-EQUIVALENT FLOPs (2 M N K per launch) of the whole family over its kernel time against the fp32-MFMA peak: the split3 launches execute 6 bf16 products per fp32 product on the 16x faster bf16 pipe, so this fraction is not bounded by 1 for them -- `split3` and `fp32_mfma` below price each part against its own pipe",
@@ -630,15 +662,11 @@ def worker(args):
                          "stale_profile_warning": None if (tsrc is None or tsrc.get("launches_per_step_in_file") in (None, launches)) else
                          f"the committed PMC pass saw {tsrc['launches_per_step_in_file']} launches per step, this run {launches}: `traffic` is from an older build"},
             "corr_volume": None if args.no_corr_roofline else corr_roofline(ops),
-            "dump_outputs": dumped,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             log("cpu baseline + parity")
             out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity(model, ops)
-        print(json.dumps(out), flush=True)
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 def main(argv=None):

@@ -72,6 +72,17 @@ def test_bench_launcher_starts_n_ranks():
     assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["gathered_ranks"] == [0, 1]
 
 
+def test_bench_full_is_opt_in_and_reaches_the_ranks():
+    """A plain `bench.py` run times the steps and nothing else: `--full` (everything else the benchmark measures) is off unless
+    asked for, and the launcher hands it on to the ranks it starts."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert "--full" not in bench.launcher_command(bench.parse_args(["--gpus", "2"]), 29545)
+    args = bench.parse_args(["--gpus", "2", "--full"])
+    assert args.full is True and "--full" in bench.launcher_command(args, 29545)
+
+
 def test_out_py_shards_its_pair_list(tmp_path):
     """`torchrun --nproc-per-node 2 out.py ...` (configs[4] names 8 GPUs): every rank takes pairs rank, rank + N, ... of
     demo.txt; rehearsed with --dry-run (no model, no GPU).  The shards are disjoint and cover the list."""

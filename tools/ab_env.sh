@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 V=$1; shift
 for val in "$@"; do
   echo "== $V=$val"
-  for i in 1 2; do env $V=$val python bench.py --steps 80 --warmup 10 --no-cpu-baseline --no-corr-roofline 2>/dev/null | python -c "
+  for i in 1 2; do env $V=$val python bench.py --full --steps 80 --warmup 10 --no-cpu-baseline --no-corr-roofline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 # bench twice + rocprofv3 kernel summary of the same command (run on the GPU box from the repo root): bash tools/prof_bench.sh TAG [NLINES]
 export TMPDIR=/tmp
 T=${1:-x}; N=${2:-28}
-for i in 1 2; do python bench.py --steps 80 --warmup 10 --no-cpu-baseline --no-corr-roofline 2>/dev/null | python -c "
+for i in 1 2; do python bench.py --full --steps 80 --warmup 10 --no-cpu-baseline --no-corr-roofline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
