@@ -301,7 +301,10 @@ int st_latent_pool(const float* scores, int32_t ld_s, const float* tokens, int32
                    int32_t P, void* stream);
 
 /* ---- FlowFormer decoder gathers --------------------------------------------------------------- */
-int st_coords_grid(float* out, int32_t B, int32_t H, int32_t W, void* stream);          /* decoder.py:22-29 */
+/* Argument rule of this group and of the geometric and metric groups below: every size (B, H, W, C, planes, Nq, n, h, w) must be
+ * positive and every row stride must cover the columns written, else ST_EINVAL and nothing is launched; the further preconditions of
+ * an entry stand next to its prototype. */
+int st_coords_grid(float* out, int32_t B, int32_t H, int32_t W, void* stream);          /* decoder.py:22-29; B, H, W >= 1 */
 /* Warm start (decoder.py:270-272): out rows [B*H*W, 2] = float(grid) + init, init NCHW [B,2,H,W] in low-resolution pixels.     */
 int st_coords_grid_init(float* out, const float* init, int32_t B, int32_t H, int32_t W, void* stream);
 /* Forward splat of a low-resolution flow, the next frame's flow_init (core/utils/utils.py:32-60 on the device, no host read-back).
@@ -312,22 +315,27 @@ int st_coords_grid_init(float* out, const float* init, int32_t B, int32_t H, int
  * H*W <= 65536, B <= 65535.                                                                                         */
 int st_flow_forward_interpolate(const float* src, int32_t src_is_coords_rows, float* out, int32_t B, int32_t H, int32_t W,
                                 void* stream);
+/* flow = coords1 - grid (decoder.py:321) into flow4 [B*H*W, ld4] (columns 0..1, zeros up to ld4) and / or columns 0..1 of dst2 rows of
+ * stride ld2; either may be NULL.  B, H, W >= 1; ld4 >= 2 where flow4 is given, ld2 >= 2 where dst2 is given.                  */
 int st_flow_from_coords(const float* coords1, float* flow4, int32_t ld4, float* dst2, int32_t ld2, int32_t B,
                         int32_t H, int32_t W, void* stream);
 /* BasicMotionEncoder flow branch, first layer, fused with the flow computation (gru.py:251, decoder.py:321):
  * out [B*H*W, ldo] (first Co columns) = relu(Conv2d(2, Co, 7, padding=3)(coords1 - coords0)); w98 [49 taps][2][Co]
  * (tap-major: w98[(ky*7+kx)*2 + c][co] = weight[co][c][ky][kx]); flow2 (optional) receives the flow itself in
- * columns 0..1 of rows of stride ld2 (gru.py:254 cat([out, flow])).  Co % 4 == 0.                                 */
+ * columns 0..1 of rows of stride ld2 (gru.py:254 cat([out, flow])).  B, H, W >= 1; Co >= 4, Co % 4 == 0; ldo >= Co; ld2 >= 2 where
+ * flow2 is given; w98 16-byte and coords1 8-byte aligned (its rows are read as float2).                             */
 int st_flow_encode(const float* coords1, const float* w98, const float* bias, float* out, int32_t ldo, float* flow2,
                    int32_t ld2, int32_t B, int32_t H, int32_t W, int32_t Co, void* stream);                             /* decoder.py:321   */
 /* The same, ALSO leaving both results as blocked bf16 planes (st_gemm_desc.split3 operand format, planes `*_pstride` elements apart,
  * `*_prows` rows per 32-channel chunk): out_planes [3][Co/32][out_prows][32]; channels flow_col, flow_col + 1 (flow_col even) of flow_planes
- * (may be NULL).  Co % 32 == 0.  Replaces gru.py:251,254 for a split3 consumer of gru.py:252-253 / 44-59.                          */
+ * (may be NULL).  Co % 32 == 0, otherwise st_flow_encode's preconditions.  Replaces gru.py:251,254 for a split3 consumer of gru.py:252-253 / 44-59. */
 int st_flow_encode_split3(const float* coords1, const float* w98, const float* bias, float* out, int32_t ldo, float* flow2,
                           int32_t ld2, int32_t B, int32_t H, int32_t W, int32_t Co, void* out_planes, int64_t out_pstride,
                           int64_t out_prows, void* flow_planes, int64_t flow_pstride, int64_t flow_prows, int32_t flow_col,
                           void* stream);
-/* encode_flow_token + bilinear_sampler (decoder.py:242-260, core/utils/utils.py:62-76).              */
+/* encode_flow_token + bilinear_sampler (decoder.py:242-260, core/utils/utils.py:62-76): maps [Nq, H2*W2], coords [Nq, 2], out [Nq, ldo],
+ * channel i*(2r+1)+j sampled at (x + i - r, y + j - r).  Nq >= 1; 0 <= r <= 64; ldo >= (2r+1)^2; H2, W2 >= 2 (the sampler divides by
+ * W2 - 1 and H2 - 1, as the reference's does); H2*W2 < 2^31.                                          */
 int st_cost_lookup(const float* maps, const float* coords, float* out, int32_t ldo, int32_t Nq, int32_t H2,
                    int32_t W2, int32_t r, void* stream);
 /* One fused launch for the row-local token chain of a refinement iteration: flow_token_encoder
@@ -337,7 +345,7 @@ int st_cost_lookup(const float* maps, const float* coords, float* out, int32_t l
  * weights16 (host array of 16 device pointers): w0[64,84] b0 w2[64,64] b2 n1w n1b wq bq wp bp n2w n2b wf0 bf0 wf3 bf3. */
 int st_decoder_token_chain(float* corr, int32_t ld_corr, const float* coords1, const float* kv,
                            const float* const* weights16, int32_t rows, int32_t ntok, void* stream);
-/* upsample_flow (decoder.py:214-225): mask [B*H*W, ldm>=576] -> out NCHW [B,2,8H,8W].              */
+/* upsample_flow (decoder.py:214-225): mask [B*H*W, ldm>=576] -> out NCHW [B,2,8H,8W].  B, H, W >= 1; coords1 8-byte aligned. */
 int st_convex_upsample(const float* coords1, const float* mask, int32_t ldm, float* out, int32_t B, int32_t H,
                        int32_t W, void* stream);
 
@@ -351,41 +359,49 @@ int st_dlt4(const float* src4x2, const float* motion, float* H, int32_t B, float
 int st_mat3_sandwich(const float* L, const float* X, const float* R, float* out, int32_t B, int32_t invert,
                      void* stream);
 /* torch_homo_transform.transformer (core/udis_utils/torch_homo_transform.py:5-151); the last n_ones
- * output channels are the warp of an all-ones image; idx (optional) [B,oh,ow,4] = x0,x1,y0,y1.      */
+ * output channels are the warp of an all-ones image; idx (optional) [B,oh,ow,4] = x0,x1,y0,y1.
+ * B, H, W, oh, ow >= 1; C, n_ones >= 0 and, where out is given, C + n_ones >= 1; out or idx given.  */
 int st_homo_warp(const float* U, const float* theta, float* out, int32_t* idx, int32_t B, int32_t C,
                  int32_t n_ones, int32_t H, int32_t W, int32_t oh, int32_t ow, void* stream);
-/* get_rigid_mesh + H2Mesh + min/max (core/warp_utils.py:10-34, flowHomoAdpater.py:254-266).          */
+/* get_rigid_mesh + H2Mesh + min/max (core/warp_utils.py:10-34, flowHomoAdpater.py:254-266).  B >= 1; gw, gh >= 0. */
 int st_mesh_bounds(const float* H, float* out4, int32_t B, float width, float height, int32_t gw, int32_t gh,
                    void* stream);
-/* warp() = grid_sample(bilinear, zeros, align_corners=True) at pix+flow (core/warp_utils.py:54-80). */
+/* warp() = grid_sample(bilinear, zeros, align_corners=True) at pix+flow (core/warp_utils.py:54-80); a sample whose coordinate is not
+ * finite is 0.  mul (optional) [B,1,H,W].  B, C, H, W >= 1.                                         */
 int st_flow_warp(const float* x, const float* flow, const float* mul, float* out, int32_t B, int32_t C,
                  int32_t H, int32_t W, void* stream);
 /* use_combine_h_flow branch of train_eval_foward (flowHomoAdpater.py:150-164): Hi = inverse(H8) (optional output [B,3,3]), mesh of
  * the per-pixel rigid grid through inverse(Hi) (warp_utils.py:10-34), final_flow = mesh - grid + flow, out6 = warp(cat(image2,
- * ones), final_flow) [B,6,H,W], overlap = mean(out6[:,3:6]) < 0.9 [B,H,W].  image2 [B,3,H,W], H8 [B,3,3], flow [B,2,H,W]. */
+ * ones), final_flow) [B,6,H,W], overlap = mean(out6[:,3:6]) < 0.9 [B,H,W].  image2 [B,3,H,W], H8 [B,3,3], flow [B,2,H,W].  B, H, W >= 1. */
 int st_homo_flow_warp(const float* image2, const float* H8, const float* flow, float* out6, float* overlap, float* Hi,
                       int32_t B, int32_t H, int32_t W, void* stream);
 /* F.interpolate bilinear: resize_flow (warp_utils.py:38-46) / Resize((512,512)) (flowHomoAdpater.py:14);
- * align_corners == 2: scale_factor form of out.py:281 (half-pixel centres, source step (div0, div1) = 1/scale). */
+ * align_corners == 2: scale_factor form of out.py:281 (half-pixel centres, source step (div0, div1) = 1/scale).
+ * ndiv == 2 (align_corners 0 / 1): plane p is divided by (p % 2 ? div1 : div0) afterwards.  planes, H, W, oh, ow >= 1; align_corners in
+ * {0, 1, 2}; ndiv in {0, 2}, the divisors non-zero when ndiv == 2; align_corners == 2: div0, div1 > 0 and the last output row / column
+ * starts inside the source, div0 * (oh - 0.5) - 0.5 < H and div1 * (ow - 0.5) - 0.5 < W (i.e. oh <= H * scale: the lower tap index (int)sy is not clamped). */
 int st_resize_bilinear(const float* x, float* out, int32_t planes, int32_t H, int32_t W, int32_t oh, int32_t ow,
                        int32_t align_corners, float div0, float div1, int32_t ndiv, void* stream);
-/* compute_range_map (core/warp_utils.py:114-175), deterministic fixed-point splat.                  */
+/* compute_range_map (core/warp_utils.py:114-175), deterministic fixed-point splat; scratch: B*H*W uint64.  B, H, W >= 1. */
 int st_range_map(const float* flow, void* scratch_u64, float* out, int32_t B, int32_t H, int32_t W, void* stream);
+/* 1 - (1 - clamp(range, 0, 1)), thresholded at >= 0.5 when threshold != 0 (warp_utils.py:212-220, flowHomoAdpater.py:181).  n >= 1. */
 int st_occlusion_from_range(const float* range, float* out, int64_t n, int32_t threshold, void* stream);
-/* preprocess_occlusion_mask (flowHomoAdpater.py:18-35); scratch: 2*N*H*W bytes.                     */
+/* preprocess_occlusion_mask (flowHomoAdpater.py:18-35); scratch: 2*N*H*W bytes.  N, H, W >= 1; ksz >= 1 and odd. */
 int st_morph_open(const float* mask, float* out, void* scratch_u8x2, int32_t N, int32_t H, int32_t W,
                   int32_t ksz, void* stream);
+/* flowHomoAdpater.py:171-183: overlap = mean(final6[:,3:6]) < 0.9, final6 *= occ in place.  B, H, W >= 1. */
 int st_eval_finish(float* final6, const float* occ, float* overlap, int32_t B, int32_t H, int32_t W, void* stream);
 int st_blend(const float* homo1, const float* homo2, float* fin, const float* occ, float* output2, float* mask1,
-             float* mask2, uint8_t* blend, int32_t h, int32_t w, void* stream);          /* :339-360 */
+             float* mask2, uint8_t* blend, int32_t h, int32_t w, void* stream);          /* :339-360; h, w >= 1 */
 /* test_out without the consistency mask (flowHomoAdpater.py:349-360): st_blend's outputs, fin read only, no occlusion and no
- * non_overlap_mask factor. */
+ * non_overlap_mask factor.  h, w >= 1. */
 int st_blend_plain(const float* homo1, const float* homo2, const float* fin, float* output2, float* mask1, float* mask2,
                    uint8_t* blend, int32_t h, int32_t w, void* stream);
 int st_mean_threshold(const float* x, float* out, int32_t B, int32_t C, int32_t H, int32_t W, float thr,
-                      void* stream);                                                      /* :233-234 */
+                      void* stream);                                                      /* :233-234; B, C, H, W >= 1 */
 /* UDIS2 TPS transformer (core/udis_utils/torch_tps_transform.py:7-190): fp64 solve -> T [B,2,N+3],
- * then grid + 4-tap gather.  work_f64: B*(N+3)*(N+5) doubles.                                       */
+ * then grid + 4-tap gather.  work_f64: B*(N+3)*(N+5) doubles.  B >= 1, 1 <= N <= 4000; with out or idx: H, W, oh, ow >= 1, and with
+ * out: U given and C >= 1 (checked before the solve is launched).                                    */
 int st_tps_solve_grid(const float* U, const float* source, const float* target, void* work_f64, float* T,
                       float* out, int32_t* idx, int32_t B, int32_t C, int32_t H, int32_t W, int32_t N,
                       int32_t oh, int32_t ow, void* stream);
@@ -394,10 +410,11 @@ int st_tps_solve_grid(const float* U, const float* source, const float* target, 
 /* Masked PSNR / SSIM per image exactly as evaluate.py:53-65 feeds skimage 0.19.3 (uint8 truncation, mask =
  * uint8(channel-mean mask), 7x7 uniform SSIM, K1=.01 K2=.03, sample covariance, 3-px crop, channel mean).
  * image1 [B,3,H,W]; warped: B images of 3 planes, batch stride in floats (e.g. 6*H*W for final_warp_output);
- * maskmean [B,H,W]; partial_f64: 2*B*ceil(3HW/256) doubles of scratch; out [B,2] fp64 = (psnr, ssim). */
+ * maskmean [B,H,W]; partial_f64: 2*B*ceil(3HW/256) doubles of scratch; out [B,2] fp64 = (psnr, ssim).  B >= 1; H, W >= 7 (one
+ * SSIM window); 0 <= warped_batch_stride < 2^31. */
 int st_masked_psnr_ssim(const float* image1, const float* warped, int64_t warped_batch_stride, const float* maskmean,
                         void* partial_f64, double* out_psnr_ssim, int32_t B, int32_t H, int32_t W, void* stream);
-/* mean over C planes of x[b] (evaluate.py:45). */
+/* mean over C planes of x[b] (evaluate.py:45).  B, C, H, W >= 1. */
 int st_channel_mean(const float* x, int64_t batch_stride, float* out, int32_t B, int32_t C, int32_t H, int32_t W,
                     void* stream);
 

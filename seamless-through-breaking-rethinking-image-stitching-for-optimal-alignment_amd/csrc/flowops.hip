@@ -14,7 +14,7 @@ __global__ void coords_grid_kernel(float* __restrict__ out, int B, int H, int W)
 }
 
 extern "C" int st_coords_grid(float* out, int32_t B, int32_t H, int32_t W, void* stream) {
-    if (!out) return ST_EINVAL;
+    if (!out || B <= 0 || H <= 0 || W <= 0) return ST_EINVAL;
     const size_t total = (size_t)B * H * W;
     hipLaunchKernelGGL(coords_grid_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, B, H, W);
     ST_CHECK_LAUNCH();
@@ -57,7 +57,7 @@ __global__ void flow_from_coords_kernel(const float* __restrict__ coords1, float
 
 extern "C" int st_flow_from_coords(const float* coords1, float* flow4, int32_t ld4, float* dst2, int32_t ld2, int32_t B,
                                    int32_t H, int32_t W, void* stream) {
-    if (!coords1) return ST_EINVAL;
+    if (!coords1 || B <= 0 || H <= 0 || W <= 0 || (flow4 && ld4 < 2) || (dst2 && ld2 < 2)) return ST_EINVAL;
     const size_t total = (size_t)B * H * W;
     hipLaunchKernelGGL(flow_from_coords_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, coords1, flow4,
                        ld4, dst2, ld2, B, H, W);
@@ -178,6 +178,7 @@ __global__ __launch_bounds__(512) void flow_encode_kernel(const float* __restric
 extern "C" int st_flow_encode(const float* coords1, const float* w98, const float* bias, float* out, int32_t ldo, float* flow2,
                               int32_t ld2, int32_t B, int32_t H, int32_t W, int32_t Co, void* stream) {
     if (!coords1 || !w98 || !bias || !out || B <= 0 || H <= 0 || W <= 0 || Co <= 0 || (Co & 3) || ((uintptr_t)w98 & 15)) return ST_EINVAL;
+    if (ldo < Co || (flow2 && ld2 < 2) || ((uintptr_t)coords1 & 7)) return ST_EINVAL;      // coords1 rows are read as float2
     dim3 grid(((H + 3) / 4) * ((W + 7) / 8), (Co + 127) / 128, B);
     hipLaunchKernelGGL(flow_encode_kernel, grid, dim3(512), 0, (hipStream_t)stream, coords1, w98, bias, out, ldo, flow2, ld2, H, W, Co,
                        (__bf16*)nullptr, 0LL, 0LL, (__bf16*)nullptr, 0LL, 0LL, 0);
@@ -192,6 +193,7 @@ extern "C" int st_flow_encode_split3(const float* coords1, const float* w98, con
                                      int64_t out_prows, void* flow_planes, int64_t flow_pstride, int64_t flow_prows, int32_t flow_col,
                                      void* stream) {
     if (!coords1 || !w98 || !bias || !out || B <= 0 || H <= 0 || W <= 0 || Co <= 0 || (Co & 31) || ((uintptr_t)w98 & 15)) return ST_EINVAL;
+    if (ldo < Co || (flow2 && ld2 < 2) || ((uintptr_t)coords1 & 7)) return ST_EINVAL;
     if (!out_planes || out_pstride <= 0 || out_prows < (int64_t)B * H * W) return ST_EINVAL;
     if (flow_planes && (!flow2 || flow_pstride <= 0 || flow_prows < (int64_t)B * H * W || flow_col < 0 || (flow_col & 1))) return ST_EINVAL;
     dim3 grid(((H + 3) / 4) * ((W + 7) / 8), (Co + 127) / 128, B);
@@ -242,7 +244,8 @@ __global__ __launch_bounds__(256) void cost_lookup_kernel(const float* __restric
 
 extern "C" int st_cost_lookup(const float* maps, const float* coords, float* out, int32_t ldo, int32_t Nq, int32_t H2,
                               int32_t W2, int32_t r, void* stream) {
-    if (!maps || !coords || !out || Nq <= 0 || r < 0 || ldo < (2 * r + 1) * (2 * r + 1)) return ST_EINVAL;
+    if (!maps || !coords || !out || Nq <= 0 || r < 0 || r > 64 || ldo < (2 * r + 1) * (2 * r + 1)) return ST_EINVAL;
+    if (H2 < 2 || W2 < 2 || (int64_t)H2 * W2 > 0x7fffffff) return ST_EINVAL;      // W2 - 1, H2 - 1 divide (the reference's bilinear_sampler too)
     const size_t total = (size_t)Nq * (2 * r + 1) * (2 * r + 1);
     hipLaunchKernelGGL(cost_lookup_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, maps, coords, out,
                        ldo, Nq, H2, W2, r);
@@ -289,7 +292,7 @@ __global__ __launch_bounds__(256) void convex_upsample_kernel(const float* __res
 
 extern "C" int st_convex_upsample(const float* coords1, const float* mask, int32_t ldm, float* out, int32_t B, int32_t H,
                                   int32_t W, void* stream) {
-    if (!coords1 || !mask || !out || ldm < 576) return ST_EINVAL;
+    if (!coords1 || !mask || !out || ldm < 576 || B <= 0 || H <= 0 || W <= 0 || ((uintptr_t)coords1 & 7)) return ST_EINVAL;
     const size_t total = (size_t)B * H * W * 64;
     hipLaunchKernelGGL(convex_upsample_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, coords1, mask,
                        ldm, out, B, H, W);

@@ -88,6 +88,7 @@ __global__ __launch_bounds__(256) void homo_warp_kernel(const float* __restrict_
 extern "C" int st_homo_warp(const float* U, const float* theta, float* out, int32_t* idx, int32_t B, int32_t C,
                             int32_t n_ones, int32_t H, int32_t W, int32_t oh, int32_t ow, void* stream) {
     if (!theta || (!out && !idx) || (C > 0 && !U) || B <= 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0) return ST_EINVAL;
+    if (C < 0 || n_ones < 0 || (out && C + n_ones <= 0)) return ST_EINVAL;
     dim3 grid((ow + 63) / 64, (oh + 3) / 4, B);
     hipLaunchKernelGGL(homo_warp_kernel, grid, dim3(256), 0, (hipStream_t)stream, U, theta, out, idx, C, n_ones, H, W, oh, ow);
     ST_CHECK_LAUNCH();
@@ -473,7 +474,7 @@ extern "C" int st_homo_flow_warp(const float* image2, const float* H8, const flo
 
 extern "C" int st_flow_warp(const float* x, const float* flow, const float* mul, float* out, int32_t B, int32_t C, int32_t H,
                             int32_t W, void* stream) {
-    if (!x || !flow || !out || B <= 0 || C <= 0) return ST_EINVAL;
+    if (!x || !flow || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0) return ST_EINVAL;
     dim3 grid((W + 63) / 64, (H + 3) / 4, B);
     hipLaunchKernelGGL(flow_warp_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, flow, mul, out, C, H, W);
     ST_CHECK_LAUNCH();
@@ -516,6 +517,16 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
 extern "C" int st_resize_bilinear(const float* x, float* out, int32_t planes, int32_t H, int32_t W, int32_t oh, int32_t ow,
                                   int32_t align_corners, float div0, float div1, int32_t ndiv, void* stream) {
     if (!x || !out || planes <= 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0) return ST_EINVAL;
+    if (align_corners < 0 || align_corners > 2 || (ndiv != 0 && ndiv != 2)) return ST_EINVAL;
+    if (align_corners == 2) {
+        // the kernel steps the source by (div0, div1) and, like ATen, clamps only the upper tap (y1 = y0 + (y0 < H - 1)), not y0 = (int)sy
+        // itself: the last output row / column must still start inside the source (oh <= H * scale).  The same fp32 expression as the
+        // kernel's: build.py's SOURCES entry compiles this file with -ffp-contract=off, and hipcc hands the flag to the host pass and the
+        // device pass alike, so neither fuses the product and the subtraction and both round twice.
+        if (!(div0 > 0.f) || !(div1 > 0.f)) return ST_EINVAL;
+        const float sy = div0 * ((float)(oh - 1) + 0.5f) - 0.5f, sx = div1 * ((float)(ow - 1) + 0.5f) - 0.5f;
+        if (!(sy < (float)H) || !(sx < (float)W)) return ST_EINVAL;
+    } else if (ndiv == 2 && (div0 == 0.f || div1 == 0.f)) return ST_EINVAL;
     dim3 grid((ow + 63) / 64, (oh + 3) / 4, planes);
     hipLaunchKernelGGL(resize_bilinear_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, out, planes, H, W, oh, ow,
                        align_corners, div0, div1, ndiv);
@@ -560,7 +571,7 @@ __global__ void range_finish_kernel(const unsigned long long* __restrict__ acc, 
 }
 
 extern "C" int st_range_map(const float* flow, void* scratch_u64, float* out, int32_t B, int32_t H, int32_t W, void* stream) {
-    if (!flow || !scratch_u64 || !out || B <= 0) return ST_EINVAL;
+    if (!flow || !scratch_u64 || !out || B <= 0 || H <= 0 || W <= 0) return ST_EINVAL;
     const size_t n = (size_t)B * H * W;
     hipStream_t s = (hipStream_t)stream;
     // zeroed by a kernel, not hipMemsetAsync: captured into a hipGraph, the memset node did not clear the accumulator on replays
@@ -619,7 +630,7 @@ __global__ void morph_pass_kernel(const float* __restrict__ srcf, const unsigned
 
 extern "C" int st_morph_open(const float* mask, float* out, void* scratch_u8x2, int32_t N, int32_t H, int32_t W, int32_t ksz,
                              void* stream) {
-    if (!mask || !out || !scratch_u8x2 || N <= 0 || ksz <= 0 || !(ksz & 1)) return ST_EINVAL;
+    if (!mask || !out || !scratch_u8x2 || N <= 0 || H <= 0 || W <= 0 || ksz <= 0 || !(ksz & 1)) return ST_EINVAL;
     const size_t n = (size_t)N * H * W;
     unsigned char* t0 = (unsigned char*)scratch_u8x2;
     unsigned char* t1 = t0 + n;
@@ -650,7 +661,7 @@ __global__ void eval_finish_kernel(float* __restrict__ fin, const float* __restr
 }
 
 extern "C" int st_eval_finish(float* final6, const float* occ, float* overlap, int32_t B, int32_t H, int32_t W, void* stream) {
-    if (!final6 || !occ || !overlap) return ST_EINVAL;
+    if (!final6 || !occ || !overlap || B <= 0 || H <= 0 || W <= 0) return ST_EINVAL;
     const size_t n = (size_t)B * H * W;
     hipLaunchKernelGGL(eval_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, final6, occ, overlap, B, (size_t)H * W);
     ST_CHECK_LAUNCH();
@@ -686,7 +697,7 @@ __global__ void blend_kernel(const float* __restrict__ homo1, const float* __res
 
 extern "C" int st_blend(const float* homo1, const float* homo2, float* fin, const float* occ, float* output2, float* mask1,
                         float* mask2, uint8_t* blend, int32_t h, int32_t w, void* stream) {
-    if (!homo1 || !homo2 || !fin || !occ || !output2 || !mask1 || !mask2 || !blend) return ST_EINVAL;
+    if (!homo1 || !homo2 || !fin || !occ || !output2 || !mask1 || !mask2 || !blend || h <= 0 || w <= 0) return ST_EINVAL;
     const size_t hw = (size_t)h * w;
     hipLaunchKernelGGL(blend_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, homo1, homo2, fin, occ, output2,
                        mask1, mask2, blend, hw);
@@ -738,7 +749,7 @@ __global__ void mean_threshold_kernel(const float* __restrict__ x, float* __rest
 }
 
 extern "C" int st_mean_threshold(const float* x, float* out, int32_t B, int32_t C, int32_t H, int32_t W, float thr, void* stream) {
-    if (!x || !out) return ST_EINVAL;
+    if (!x || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0) return ST_EINVAL;
     const size_t n = (size_t)B * H * W;
     hipLaunchKernelGGL(mean_threshold_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, out, B, C, (size_t)H * W, thr);
     ST_CHECK_LAUNCH();
@@ -856,10 +867,10 @@ extern "C" int st_tps_solve_grid(const float* U, const float* source, const floa
                                  int32_t* idx, int32_t B, int32_t C, int32_t H, int32_t W, int32_t N, int32_t oh, int32_t ow,
                                  void* stream) {
     if (!source || !target || !work_f64 || !T || B <= 0 || N <= 0 || N > 4000) return ST_EINVAL;
+    if ((out || idx) && (H <= 0 || W <= 0 || oh <= 0 || ow <= 0 || C < 0 || (out && (!U || C <= 0)))) return ST_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(tps_solve_kernel, dim3(B), dim3(256), 0, s, source, target, (double*)work_f64, T, N);
     if (out || idx) {
-        if (!U && out) return ST_EINVAL;
         dim3 grid((ow + 63) / 64, (oh + 3) / 4, B);
         const size_t lds = (size_t)(2 * N + 2 * (N + 3)) * sizeof(float);
         hipLaunchKernelGGL(tps_warp_kernel, grid, dim3(256), lds, s, U, source, T, out, idx, C, H, W, oh, ow, N);

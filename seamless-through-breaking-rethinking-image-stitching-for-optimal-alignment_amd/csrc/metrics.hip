@@ -78,6 +78,7 @@ __global__ __launch_bounds__(256) void metrics_final_kernel(const double* __rest
 extern "C" int st_masked_psnr_ssim(const float* image1, const float* warped, int64_t warped_batch_stride, const float* maskmean,
                                    void* partial_f64, double* out_psnr_ssim, int32_t B, int32_t H, int32_t W, void* stream) {
     if (!image1 || !warped || !maskmean || !partial_f64 || !out_psnr_ssim || B <= 0 || H < 7 || W < 7) return ST_EINVAL;
+    if (warped_batch_stride < 0 || warped_batch_stride > 0x7fffffffLL) return ST_EINVAL;      // the kernel takes it as an int
     const int nblk = (int)(((size_t)3 * H * W + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(metrics_partial_kernel, dim3(nblk, B), dim3(256), 0, s, image1, warped, (int)warped_batch_stride, maskmean,
@@ -98,7 +99,7 @@ __global__ void channel_mean_kernel(const float* __restrict__ x, long bstride, f
 }
 
 extern "C" int st_channel_mean(const float* x, int64_t batch_stride, float* out, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
-    if (!x || !out || B <= 0 || C <= 0) return ST_EINVAL;
+    if (!x || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0) return ST_EINVAL;
     const size_t n = (size_t)B * H * W;
     hipLaunchKernelGGL(channel_mean_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, (long)batch_stride, out, B, C, (size_t)H * W);
     ST_CHECK_LAUNCH();
