@@ -423,6 +423,21 @@ int st_channel_mean(const float* x, int64_t batch_stride, float* out, int32_t B,
  * aligned (ST_EINVAL otherwise). */
 int st_load_rgb8(const void* src_u8_hwc, float* dst_chw, int32_t B, int32_t H, int32_t W, void* stream);
 
+/* Saver tail of out.py (out.py:260-312 `to_pillow_fn(x).save(path)`): the baseline JPEG file Pillow writes at its defaults on libjpeg-turbo
+ * (quality 75; RGB: 4:2:0; L: one component; Annex K Huffman tables; JFIF header; integer "islow" DCT), byte for byte, encoded on the device
+ * (csrc/jpeg.hip; contract in README.md, CPU restatement tests/_jpeg_ref.py).  src: uint8 [H, W, channels] interleaved, rows row_stride BYTES
+ * apart (>= W * channels, < 2^31); channels 3 (RGB) or 1 (L); 1 <= H, W <= 65535 and H * W <= 2^24.  out receives the file (SOI .. EOI),
+ * *out_nbytes (device int32) its length; nothing is read back, all launches go to `stream`.  ST_EINVAL before any launch for: a null pointer,
+ * other channels, sizes outside those limits, a row_stride below W * channels, a workspace that is not 16-byte aligned or smaller than
+ * st_jpeg_workspace_bytes, an out_capacity below st_jpeg_max_bytes -- the worst case of the code tables: header (623 bytes RGB, 328 L) +
+ * 2 * ceil(nblocks * (20 + 63 * 26) / 8) + 2, i.e. <= 20 bits of DC and <= 16 + 10 bits per AC coefficient in every block, doubled for byte
+ * stuffing, + EOI; nblocks = 6 * ceil(W / 16) * ceil(H / 16) (RGB) or ceil(W / 8) * ceil(H / 8) (L).  The workspace needs no
+ * initialisation and may be reused by the next call on the same stream.  The two size queries return 0 for a rejected shape.          */
+int st_jpeg_workspace_bytes(int32_t H, int32_t W, int32_t channels);
+int st_jpeg_max_bytes(int32_t H, int32_t W, int32_t channels);
+int st_jpeg_encode_u8(const void* src, int32_t H, int32_t W, int32_t channels, int64_t row_stride, void* out, int64_t out_capacity,
+                      int32_t* out_nbytes, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- operator-level entry points (one per reference operator; host-side composition of the kernels
  *      above on the caller's stream, caller-provided scratch, no allocation, no state) ------------------ */
 /* encode_flow_token with the reference's 9x9 window (decoder.py:242-260).                            */

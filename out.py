@@ -39,13 +39,15 @@ def get_config(argv=None):
     p.add_argument("--inf_cfg", type=str, default="all_img1_with_inpaint_g12_transRef")
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--skip_if_avg_fusion_exists", action="store_true")
+    p.add_argument("--gpu_jpeg", action="store_true",
+                   help="encode the result JPEGs on the GPU (the same files, byte for byte) instead of with Pillow on the host")
     p.add_argument("--dry-run", dest="dry_run", action="store_true",
                    help="list the pairs this rank would process (sharding rehearsal: no model, no GPU) and exit")
     args = p.parse_args(argv)
     import stitch_amd
     cfg, tps = stitch_amd.load_inference_config(args.inf_cfg, args.model_config_name)
     for k, v in vars(args).items():
-        if k == "restore_ckpt" and not v:
+        if k in ("restore_ckpt", "gpu_jpeg") and not v:         # (gpu_jpeg off: config.txt stays what it was before the switch existed)
             continue
         cfg[k] = v
     cfg.TPS_PIPELINE_CONFIG = tps
@@ -97,26 +99,63 @@ def to_pillow(t):
 class _Saver:
     """JPEG writes of out.py:260-312.  The uint8 conversion runs on the GPU (clip + truncation, as `to_pillow_fn` does on the
     host), the bytes are copied to the host in the caller's thread, the JPEG encode + file write go to ``pool`` when one is given
-    (``main``'s loop: the encoder releases the GIL, so the next pair's kernels are enqueued meanwhile)."""
+    (``main``'s loop: the encoder releases the GIL, so the next pair's kernels are enqueued meanwhile).
 
-    def __init__(self, pool=None):
-        self.pool, self.futures = pool, []
+    ``gpu_jpeg``: the same uint8 canvas is encoded on the device instead (`ops.jpeg_encode`, the file Pillow would write, byte for
+    byte) on the caller's stream; nothing is read back until ``flush`` (the end of a pair), which reads the byte counts of all
+    pending files together, copies exactly those bytes to the host in one transfer and hands the plain file writes to ``pool``."""
+
+    def __init__(self, pool=None, gpu_jpeg=False):
+        self.pool, self.futures, self.gpu_jpeg = pool, [], gpu_jpeg
+        self.pending = []
 
     def _write(self, arr, path):
         from PIL import Image
         Image.fromarray(arr).save(path)
 
+    @staticmethod
+    def _write_bytes(data, path):
+        with open(path, "wb") as f:
+            f.write(data)
+
+    def _submit(self, fn, *args):
+        if self.pool is None:
+            fn(*args)
+        else:
+            self.futures.append(self.pool.submit(fn, *args))
+
     def image(self, t, path):
-        arr = t[0].detach().clip(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
-        self.array(arr, path)
+        u8 = t[0].detach().clip(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+        self.array(u8, path)
 
     def array(self, arr, path):
-        if self.pool is None:
-            self._write(arr, path)
-        else:
-            self.futures.append(self.pool.submit(self._write, arr, path))
+        """uint8 [H,W,3] / [H,W], a device tensor or a host array"""
+        if self.gpu_jpeg:
+            import stitch_amd
+            if not torch.is_tensor(arr):
+                arr = torch.from_numpy(arr)
+            self.pending.append(stitch_amd.ops.jpeg_encode(arr.cuda()) + (path,))
+            return
+        if torch.is_tensor(arr):
+            arr = arr.cpu().numpy()
+        self._submit(self._write, arr, path)
+
+    def flush(self):
+        """gpu_jpeg: device -> host of the files queued so far, on the current stream: the counts together, then exactly those bytes
+        in one transfer; the file writes go to the pool.  (Deferring the read-back until the next pair's graph had been enqueued was
+        measured slower at depth 3, 59 against 68 pairs/s, and no faster at depth 2: README.md.)"""
+        if not self.pending:
+            return
+        files, self.pending = self.pending, []
+        counts = torch.cat([n for _, n, _ in files]).tolist()
+        data = torch.cat([buf[:c] for (buf, _, _), c in zip(files, counts)]).cpu().numpy()
+        at = 0
+        for (_, _, path), c in zip(files, counts):
+            self._submit(self._write_bytes, data[at:at + c].tobytes(), path)
+            at += c
 
     def wait(self):
+        self.flush()
         for f in self.futures:
             f.result()
         self.futures = []
@@ -137,7 +176,8 @@ def load_inpainter(name):
         return importlib.import_module("stitch_amd.mix_methods.utils.passthrough_inpainter").inpainter
 
 
-def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_model=None, inpainter=None, forward=None, saver=None):
+def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_model=None, inpainter=None, forward=None, saver=None,
+                       gpu_jpeg=False):
     """out.py:158-312: forward (`test_out`), TPS post-pipeline with the configured `mix_fn`, saves, composition.  The inpainter
     is the caller's, else the pass-through stand-in (`load_inpainter`: `transref_inpainter` needs its checkpoint, the diffusion one is
     out of scope): with the stand-in, in `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the
@@ -146,8 +186,9 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
 
     ``forward``: a callable returning the `test_out` dict of this pair whose network part is already in flight (``main``
     launches pair i + 1's hipGraph before it finishes pair i); default = load + ``warp_model(..., type="test_out")`` here.
-    ``saver``: a ``_Saver`` (JPEG encodes on a thread pool); default = write synchronously."""
-    saver = saver or _Saver()
+    ``saver``: a ``_Saver`` (JPEG encodes on a thread pool); default = write synchronously, with ``gpu_jpeg`` through the device encoder."""
+    own_saver = saver is None
+    saver = saver or _Saver(gpu_jpeg=gpu_jpeg)
     path = data_dict["DATA_PATH"]
     name = os.path.basename(os.path.normpath(path))
     result_path = os.path.join(save_root_path, name) + "/"
@@ -188,7 +229,7 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     saver.image(out["output1"], result_path + "warp1.jpg")
     saver.image(out["output2"], result_path + "warp2.jpg")                                                # out.py:265-272
     for key in ("mask1", "mask2"):
-        saver.array((out[key] > 0.5)[0, 0].to(torch.uint8).mul(255).cpu().numpy(), result_path + key + ".jpg")
+        saver.array((out[key] > 0.5)[0, 0].to(torch.uint8).mul(255), result_path + key + ".jpg")
     saver.image(out["new_blend_image"].float(), result_path + "ave_fusion.jpg")
     if composition_model is not None:
         # out.py:277-312: learned seam masks + composed image from the UDIS2 composition network
@@ -198,10 +239,13 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
         for key in ("learned_mask1", "learned_mask2"):
             saver.image(comp[key] * 255, result_path + key + ".jpg")
         out = dict(out, **comp)
+    saver.flush()
+    if own_saver:
+        saver.wait()
     return out, result_path
 
 
-def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=None, on_done=None, depth=2):
+def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=None, on_done=None, depth=2, gpu_jpeg=False):
     """The inference loop of out.py:351-357 as a software pipeline, `depth` pairs in flight.  While pair i is finished on the host
     (canvas bounds read back, canvas kernels, TPS post-pipeline with its control-point round trips, composition, device->host copies
     of the images), the network parts of pairs i + 1 .. i + depth - 1 -- both nets at 512x512, ~1 000 launches each, replayed from a
@@ -210,7 +254,9 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
     buffers (`residual_flow`, ...) are not overwritten before its post-pipeline has consumed them.  Same kernels and the same files
     as calling `inference_one_data` pair by pair (tests/test_harness_gpu.py).  Measured on 48 synthetic 512x512 pairs, 10 JPEGs written per
     pair (tools/bench_out_harness.py, profiles/r4_out_harness.json): 36.9 pairs/s pair by pair, 60.0 at depth 2 (default), 51 at depth 3 / 4
-    (a third network graph in flight only delays the canvas / TPS / composition kernels of the pair the host is waiting for)."""
+    (a third network graph in flight only delays the canvas / TPS / composition kernels of the pair the host is waiting for).
+    ``gpu_jpeg``: the ten files of a pair are encoded on the device on the pair's stream (`_Saver(gpu_jpeg=True)`) and read back, counts
+    first, at the end of the pair; the pool then only writes files."""
     from concurrent.futures import ThreadPoolExecutor
     if not todo:
         return []
@@ -238,7 +284,7 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
                 return graphs[k], graphs[k].launch(image1, image2), streams[k]
 
         inflight = [launch(j) for j in range(min(depth - 1, len(todo)))]
-        saver = _Saver(enc_pool)
+        saver = _Saver(enc_pool, gpu_jpeg=gpu_jpeg)
         for j, dd in enumerate(todo):
             if j + depth - 1 < len(todo):
                 inflight.append(launch(j + depth - 1))
@@ -309,7 +355,7 @@ def main(argv=None):
             print("[WARNING] Skip, Due to exist", dd["DATA_PATH"])
             continue
         todo.append(dd)
-    run_pairs(cfg, todo, save_root, model, composition_model, inpainter)
+    run_pairs(cfg, todo, save_root, model, composition_model, inpainter, gpu_jpeg=bool(getattr(cfg, "gpu_jpeg", False)))
     if world > 1:
         import torch.distributed as tdist
         tdist.barrier()

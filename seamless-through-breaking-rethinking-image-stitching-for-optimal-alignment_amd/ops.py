@@ -755,6 +755,40 @@ def load_rgb8(src_u8_hwc, out=None):
     return out
 
 
+def jpeg_encode(u8, workspace=None):
+    """out.py:260-312 `Image.fromarray(arr).save(path)` on the GPU: uint8 [H,W,3] (RGB) or [H,W] (L) -> (buf, nbytes), the JPEG file Pillow
+    writes at its defaults, byte for byte (csrc/jpeg.hip).  buf: uint8 device tensor of the worst-case size, nbytes: device int32 [1], the
+    file is buf[:nbytes].  Rows may be strided (a column slice of a wider canvas).  No host synchronisation; current stream.
+    `workspace`: a uint8 device tensor of at least `jpeg_workspace_bytes` to reuse (stream-ordered: same stream as its last use)."""
+    if u8.dtype != torch.uint8 or not (u8.dim() == 2 or (u8.dim() == 3 and u8.shape[2] == 3)):
+        raise ValueError(f"uint8 [H,W,3] or [H,W] expected, got {u8.dtype} {tuple(u8.shape)}")
+    H, W = u8.shape[:2]
+    ch = 3 if u8.dim() == 3 else 1
+    if (W > 1 and u8.stride(1) != ch) or (ch == 3 and u8.stride(2) != 1) or (H > 1 and u8.stride(0) < W * ch):
+        u8 = u8.contiguous()
+    row_stride = u8.stride(0) if H > 1 else W * ch
+    cap, need = lib.st_jpeg_max_bytes(H, W, ch), lib.st_jpeg_workspace_bytes(H, W, ch)
+    if cap == 0:
+        raise StitchErrorBase(f"st_jpeg_encode_u8: unsupported shape {tuple(u8.shape)} (sides 1..65535, H * W <= 2^24)")
+    if workspace is None:
+        workspace = torch.empty((need,), device=u8.device, dtype=torch.uint8)
+    buf = torch.empty((cap,), device=u8.device, dtype=torch.uint8)
+    nbytes = torch.empty((1,), device=u8.device, dtype=torch.int32)
+    check(lib.st_jpeg_encode_u8(_p(u8), H, W, ch, row_stride, _p(buf), cap, _p(nbytes), _pc(workspace), workspace.numel() * workspace.element_size(),
+                                _stream()), "st_jpeg_encode_u8")
+    return buf, nbytes
+
+
+def jpeg_workspace_bytes(H, W, channels):
+    return lib.st_jpeg_workspace_bytes(H, W, channels)
+
+
+def jpeg_bytes(buf, nbytes):
+    """The file of `jpeg_encode` on the host: reads the count, then copies exactly that many bytes."""
+    n = int(nbytes.item())
+    return buf[:n].cpu().numpy().tobytes()
+
+
 def masked_psnr_ssim(image1, final_warp_output, out=None):
     """evaluate.py:44-59 on the GPU: image1 [B,3,H,W], final_warp_output [B,6,H,W] -> fp64 [B,2] (psnr, ssim)."""
     B, _, H, W = image1.shape
