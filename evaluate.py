@@ -18,7 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def validate(cfg, val_dataset, batch_size=1):
+def validate(cfg, val_dataset, batch_size=1, gpu_decode=False):
     """evaluate.py:110-128."""
     import stitch_amd
     from stitch_amd import evaluate as sev
@@ -29,7 +29,7 @@ def validate(cfg, val_dataset, batch_size=1):
     print("[Loading ckpt from {}]".format(cfg.restore_ckpt))
     model.load_state_dict(torch.load(cfg.restore_ckpt, map_location="cpu", weights_only=True), strict=True)
     model = model.cuda().eval()
-    return sev.validate_with_model(model, val_dataset, batch_size=batch_size)[0]
+    return sev.validate_with_model(model, val_dataset, batch_size=batch_size, gpu_decode=gpu_decode)[0]
 
 
 def main(argv=None):
@@ -43,6 +43,8 @@ def main(argv=None):
                    help="pairs per forward (the reference's loader batches 12, evaluate.py:34; measured on one MI355X: 82.2 pairs/s at 1, 84.2 at 2, "
                         "84.7 at 4, 82.7 at 8 -- profiles/r5_batch_sweep.txt; per-pair results move by the batched-vs-unbatched reorder noise the "
                         "reference shows itself, tests/golden/e2e_r5_512.npz b2_vs_b1_*)")
+    p.add_argument("--gpu_decode", action="store_true",
+                   help="decode the JPEG files on the GPU (ops.jpeg_decode: Pillow's pixels bit for bit); files outside the decoder's contract keep Pillow")
     args = p.parse_args(argv)
     rank, world, local = sdist.init()
     torch.cuda.set_device(local)
@@ -50,7 +52,7 @@ def main(argv=None):
     cfg.batch_size = 1
     cfg.restore_ckpt = args.ckpt_path
     val_dataset = sev.UDISDataset(data_dir=args.data_dir, phase="testing")
-    result = validate(cfg, val_dataset, batch_size=args.batch_size)
+    result = validate(cfg, val_dataset, batch_size=args.batch_size, gpu_decode=args.gpu_decode)
     if rank == 0:
         print(result)
     return result

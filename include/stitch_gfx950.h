@@ -438,6 +438,31 @@ int st_jpeg_max_bytes(int32_t H, int32_t W, int32_t channels);
 int st_jpeg_encode_u8(const void* src, int32_t H, int32_t W, int32_t channels, int64_t row_stride, void* out, int64_t out_capacity,
                       int32_t* out_nbytes, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Loader head of evaluate.py and out.py (`PIL.Image.open(path)` on the worker threads): the uint8 [H, W, C] array Pillow returns for a baseline
+ * JPEG file on libjpeg-turbo at its defaults (Huffman baseline, integer "islow" IDCT, fancy upsampling, jdcolor.c's fixed-point YCbCr -> RGB),
+ * bit for bit, decoded on the device (csrc/jpeg_dec.hip; contract in README.md, CPU restatement tests/_jpeg_dec_ref.py).  The HOST parses the
+ * markers (ops.jpeg_probe) and fills st_jpeg_dec_params; the quantiser and Huffman tables and the scan are read on the device from the file's
+ * bytes at the offsets given there.  file_dev: the whole file, nbytes <= 2^28.  out: uint8 [H, W, ncomp] interleaved, rows row_stride BYTES apart
+ * (>= W * ncomp, < 2^31).  *status_dev (device int32) receives 0, 1 when the scan ended before the frame's blocks were decoded, 2 when it held
+ * more blocks than the frame; with a nonzero status the pixels are unspecified, every access stays in bounds (bit reads inside the scan, coefficient
+ * writes inside the frame's blocks).  Nothing is read back, all launches go to `stream`: 9 + one per 256 subsequences of 1024 scan bits.
+ * ST_EINVAL before any launch for: a null pointer; 1 <= H, W <= 65535 and H * W <= 2^24 violated; ncomp other than 1 or 3; (hs, vs) -- the luma
+ * sampling factors, chroma is 1 x 1 -- other than (1,1), or with three components (2,1), (2,2); a table index outside 0..1; an offset of a used
+ * table below 0 or closer to the end of the file than its fixed part (64 quantiser bytes, 16 code counts); a scan outside the file or empty;
+ * a row_stride below W * ncomp; a workspace that is not 16-byte aligned or smaller than st_jpeg_dec_workspace_bytes (0 for a rejected shape).
+ * The workspace needs no initialisation and may be reused by the next call on the same stream.                                             */
+typedef struct st_jpeg_dec_params {
+    int32_t H, W, ncomp, hs, vs;
+    int32_t tq[3], td[3], ta[3];                    /* component -> quantiser / DC / AC table index (0..1)                                   */
+    int32_t q_off[2], dc_off[2], ac_off[2];         /* byte offsets in the file: the 64 zigzag-ordered quantiser bytes of DQT table i; the 16
+                                                     * code counts of DHT table i (its values follow); -1: not defined                       */
+    int32_t scan_off, scan_len;                     /* the entropy-coded bytes: behind the SOS header, up to (not including) the EOI marker  */
+} st_jpeg_dec_params;
+int st_abi_jpeg_dec_params_size(void);
+int st_jpeg_dec_workspace_bytes(int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, int64_t scan_len);
+int st_jpeg_decode_u8(const void* file_dev, int64_t nbytes, const st_jpeg_dec_params* params, void* out, int64_t row_stride, int32_t* status_dev,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- operator-level entry points (one per reference operator; host-side composition of the kernels
  *      above on the caller's stream, caller-provided scratch, no allocation, no state) ------------------ */
 /* encode_flow_token with the reference's 9x9 window (decoder.py:242-260).                            */

@@ -41,13 +41,15 @@ def get_config(argv=None):
     p.add_argument("--skip_if_avg_fusion_exists", action="store_true")
     p.add_argument("--gpu_jpeg", action="store_true",
                    help="encode the result JPEGs on the GPU (the same files, byte for byte) instead of with Pillow on the host")
+    p.add_argument("--gpu_decode", action="store_true",
+                   help="decode the input JPEGs on the GPU (Pillow's pixels, bit for bit); files outside the decoder's contract keep Pillow")
     p.add_argument("--dry-run", dest="dry_run", action="store_true",
                    help="list the pairs this rank would process (sharding rehearsal: no model, no GPU) and exit")
     args = p.parse_args(argv)
     import stitch_amd
     cfg, tps = stitch_amd.load_inference_config(args.inf_cfg, args.model_config_name)
     for k, v in vars(args).items():
-        if k in ("restore_ckpt", "gpu_jpeg") and not v:         # (gpu_jpeg off: config.txt stays what it was before the switch existed)
+        if k in ("restore_ckpt", "gpu_jpeg", "gpu_decode") and not v:         # (a switch that is off: config.txt stays what it was before the switch existed)
             continue
         cfg[k] = v
     cfg.TPS_PIPELINE_CONFIG = tps
@@ -72,13 +74,58 @@ def decodeSingleData(data_path, img1_name, img2_name):
                  for name in (img1_name, img2_name))
 
 
-def uploadSingleData(arrays, resize_to_512=False):
-    """device half of out.py:137-143: uint8 HWC -> float [1,3,H,W] in 0..255 on the GPU (`st_load_rgb8`, exact), optional 512 resize."""
+class _JpegFile:
+    """an input file as `readSingleData` leaves it: its bytes and the probe the GPU decoder needs"""
+    __slots__ = ("path", "data", "info")
+
+    def __init__(self, path, data, info):
+        self.path, self.data, self.info = path, data, info
+
+
+def readSingleData(data_path, img1_name, img2_name):
+    """`decodeSingleData` with ``gpu_decode``: the worker thread only reads and probes the two files (`ops.jpeg_probe`), the pixels are
+    made on the device by `uploadSingleData`.  A pair with a file the decoder does not take (progressive, restart intervals, other sampling
+    factors, ...) goes through `decodeSingleData` unchanged, with one printed line."""
+    import stitch_amd
+    files = []
+    for name in (img1_name, img2_name):
+        path = os.path.join(data_path, name)
+        with open(path, "rb") as f:
+            data = f.read()
+        info = stitch_amd.ops.jpeg_probe(data)
+        if info is None:
+            print(f"gpu_decode: {data_path} decoded with Pillow ({name} is outside the GPU decoder's contract)", flush=True)
+            return decodeSingleData(data_path, img1_name, img2_name)
+        files.append(_JpegFile(path, data, info))
+    return tuple(files)
+
+
+def check_decode(statuses):
+    """the status words of a pair's GPU decodes (read back here): a scan that does not hold its frame's blocks raises and names the file"""
+    bad = [(path, int(st.item())) for path, st in statuses]
+    bad = [(path, v) for path, v in bad if v]
+    if bad:
+        raise RuntimeError("gpu_decode: the scan of " + ", ".join(f"{p} (status {v})" for p, v in bad) + " does not hold the frame's blocks")
+
+
+def uploadSingleData(arrays, resize_to_512=False, statuses=None):
+    """device half of out.py:137-143: uint8 HWC -> float [1,3,H,W] in 0..255 on the GPU (`st_load_rgb8`, exact), optional 512 resize.
+    A `_JpegFile` (``gpu_decode``) is decoded on the device first (`ops.jpeg_decode`; an L file tiled to three channels, as
+    `.convert("RGB")` does); its status word goes to `statuses` as (path, device int32) for `check_decode`, or is checked here."""
     import stitch_amd
     ts = []
     for arr in arrays:
-        u8 = torch.from_numpy(arr).unsqueeze(0).cuda(non_blocking=True)
-        hw = arr.shape[0] * arr.shape[1]
+        if isinstance(arr, _JpegFile):
+            px, st = stitch_amd.ops.jpeg_decode(arr.data, info=arr.info)
+            if statuses is None:
+                check_decode([(arr.path, st)])
+            else:
+                statuses.append((arr.path, st))
+            u8 = (px if arr.info.ncomp == 3 else px.expand(-1, -1, 3).contiguous()).unsqueeze(0)
+            hw = arr.info.H * arr.info.W
+        else:
+            u8 = torch.from_numpy(arr).unsqueeze(0).cuda(non_blocking=True)
+            hw = arr.shape[0] * arr.shape[1]
         t = stitch_amd.ops.load_rgb8(u8) if hw % 4 == 0 else u8.permute(0, 3, 1, 2).float().contiguous()
         ts.append(stitch_amd.ops.resize_bilinear(t, 512, 512, False) if resize_to_512 else t)
     return ts[0], ts[1]
@@ -177,7 +224,7 @@ def load_inpainter(name):
 
 
 def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_model=None, inpainter=None, forward=None, saver=None,
-                       gpu_jpeg=False):
+                       gpu_jpeg=False, gpu_decode=False):
     """out.py:158-312: forward (`test_out`), TPS post-pipeline with the configured `mix_fn`, saves, composition.  The inpainter
     is the caller's, else the pass-through stand-in (`load_inpainter`: `transref_inpainter` needs its checkpoint, the diffusion one is
     out of scope): with the stand-in, in `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the
@@ -186,8 +233,10 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
 
     ``forward``: a callable returning the `test_out` dict of this pair whose network part is already in flight (``main``
     launches pair i + 1's hipGraph before it finishes pair i); default = load + ``warp_model(..., type="test_out")`` here.
-    ``saver``: a ``_Saver`` (JPEG encodes on a thread pool); default = write synchronously, with ``gpu_jpeg`` through the device encoder."""
+    ``saver``: a ``_Saver`` (JPEG encodes on a thread pool); default = write synchronously, with ``gpu_jpeg`` through the device encoder.
+    ``gpu_decode``: the two input files are decoded on the device (`readSingleData`, `ops.jpeg_decode`) when this function loads them."""
     own_saver = saver is None
+    statuses = []
     saver = saver or _Saver(gpu_jpeg=gpu_jpeg)
     path = data_dict["DATA_PATH"]
     name = os.path.basename(os.path.normpath(path))
@@ -196,8 +245,9 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     if forward is not None:
         out = forward()
     else:
-        image1, image2 = uploadSingleData(decodeSingleData(path if path.endswith("/") else path + "/", data_dict["IMG1"], data_dict["IMG2"]),
-                                          resize_to_512=cfg.resize_to_512)
+        image1, image2 = uploadSingleData((readSingleData if gpu_decode else decodeSingleData)(path if path.endswith("/") else path + "/", data_dict["IMG1"],
+                                                                                              data_dict["IMG2"]),
+                                          resize_to_512=cfg.resize_to_512, statuses=statuses)
         if getattr(cfg, "swap_image", False):
             image1, image2 = image2, image1
         out = warp_model(image1, image2, type="test_out", pad_mode=cfg.pad_mode)
@@ -240,12 +290,13 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
             saver.image(comp[key] * 255, result_path + key + ".jpg")
         out = dict(out, **comp)
     saver.flush()
+    check_decode(statuses)
     if own_saver:
         saver.wait()
     return out, result_path
 
 
-def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=None, on_done=None, depth=2, gpu_jpeg=False):
+def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=None, on_done=None, depth=2, gpu_jpeg=False, gpu_decode=False):
     """The inference loop of out.py:351-357 as a software pipeline, `depth` pairs in flight.  While pair i is finished on the host
     (canvas bounds read back, canvas kernels, TPS post-pipeline with its control-point round trips, composition, device->host copies
     of the images), the network parts of pairs i + 1 .. i + depth - 1 -- both nets at 512x512, ~1 000 launches each, replayed from a
@@ -256,7 +307,9 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
     pair (tools/bench_out_harness.py, profiles/r4_out_harness.json): 36.9 pairs/s pair by pair, 60.0 at depth 2 (default), 51 at depth 3 / 4
     (a third network graph in flight only delays the canvas / TPS / composition kernels of the pair the host is waiting for).
     ``gpu_jpeg``: the ten files of a pair are encoded on the device on the pair's stream (`_Saver(gpu_jpeg=True)`) and read back, counts
-    first, at the end of the pair; the pool then only writes files."""
+    first, at the end of the pair; the pool then only writes files.
+    ``gpu_decode``: the decode threads only read and probe the files (`readSingleData`), the pixels are made on the pair's stream
+    (`ops.jpeg_decode`) in front of its graph launch; the status words are checked when the pair is finished."""
     from concurrent.futures import ThreadPoolExecutor
     if not todo:
         return []
@@ -267,7 +320,7 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
     with ThreadPoolExecutor(max_workers=2) as dec_pool, ThreadPoolExecutor(max_workers=4) as enc_pool:
         def decode(dd):
             p = dd["DATA_PATH"]
-            return decodeSingleData(p if p.endswith("/") else p + "/", dd["IMG1"], dd["IMG2"])
+            return (readSingleData if gpu_decode else decodeSingleData)(p if p.endswith("/") else p + "/", dd["IMG1"], dd["IMG2"])
 
         decoded = [dec_pool.submit(decode, dd) for dd in todo[:depth + 1]]
 
@@ -277,21 +330,23 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
             decoded[j] = None                  # the Future keeps both uint8 arrays alive: release it (the reference's loop holds one pair)
             if j + depth + 1 < len(todo):
                 decoded.append(dec_pool.submit(decode, todo[j + depth + 1]))
+            statuses = []
             with torch.cuda.stream(streams[k]):
-                image1, image2 = uploadSingleData(arrays, resize_to_512=cfg.resize_to_512)
+                image1, image2 = uploadSingleData(arrays, resize_to_512=cfg.resize_to_512, statuses=statuses)
                 if getattr(cfg, "swap_image", False):
                     image1, image2 = image2, image1
-                return graphs[k], graphs[k].launch(image1, image2), streams[k]
+                return graphs[k], graphs[k].launch(image1, image2), streams[k], statuses
 
         inflight = [launch(j) for j in range(min(depth - 1, len(todo)))]
         saver = _Saver(enc_pool, gpu_jpeg=gpu_jpeg)
         for j, dd in enumerate(todo):
             if j + depth - 1 < len(todo):
                 inflight.append(launch(j + depth - 1))
-            g, handle, st = inflight.pop(0)
+            g, handle, st, statuses = inflight.pop(0)
             with torch.cuda.stream(st):
                 out, rp = inference_one_data(cfg, dd, save_root, model, composition_model, inpainter,
                                              forward=lambda: g.finish(handle), saver=saver)
+                check_decode(statuses)
             # no host wait here: the graph of this slot is launched again on the SAME stream (pair j + depth), i.e. after everything
             # that reads this pair's static buffers
             print("saved", rp)
@@ -355,7 +410,8 @@ def main(argv=None):
             print("[WARNING] Skip, Due to exist", dd["DATA_PATH"])
             continue
         todo.append(dd)
-    run_pairs(cfg, todo, save_root, model, composition_model, inpainter, gpu_jpeg=bool(getattr(cfg, "gpu_jpeg", False)))
+    run_pairs(cfg, todo, save_root, model, composition_model, inpainter, gpu_jpeg=bool(getattr(cfg, "gpu_jpeg", False)),
+              gpu_decode=bool(getattr(cfg, "gpu_decode", False)))
     if world > 1:
         import torch.distributed as tdist
         tdist.barrier()

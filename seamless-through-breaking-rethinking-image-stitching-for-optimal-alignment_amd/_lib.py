@@ -62,6 +62,12 @@ class MlpDesc(C.Structure):
                 + [(n, C.c_void_p) for n in ("wp", "bp", "res0")] + [("ld_res0", C.c_int32), ("reserved1", C.c_int32)])
 
 
+class JpegDecParams(C.Structure):
+    """Mirror of ``st_jpeg_dec_params``."""
+    _fields_ = ([(n, C.c_int32) for n in ("H", "W", "ncomp", "hs", "vs")] + [(n, C.c_int32 * 3) for n in ("tq", "td", "ta")]
+                + [(n, C.c_int32 * 2) for n in ("q_off", "dc_off", "ac_off")] + [("scan_off", C.c_int32), ("scan_len", C.c_int32)])
+
+
 def declared_functions(header=HEADER):
     """{name: [ctypes argtypes]} for every ``int st_*(...)`` declaration in the header."""
     src = open(header).read()

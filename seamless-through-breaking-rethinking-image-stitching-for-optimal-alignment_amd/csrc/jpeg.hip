@@ -551,6 +551,12 @@ __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint32_t* __restr
 
 }  // namespace
 
+// jpeg_scan_kernel for csrc/jpeg_dec.hip (its chunk and block counts): in-place exclusive prefix sum of data[0 .. n), total -> *total
+hipError_t st_jpeg_scan_u32(uint32_t* data, uint32_t n, uint32_t* total, hipStream_t st) {
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, data, n, (const uint32_t*)nullptr, total);
+    return hipGetLastError();
+}
+
 extern "C" int st_jpeg_workspace_bytes(int32_t H, int32_t W, int32_t channels) {
     JGeom g;
     return make_geom(H, W, channels, g) ? (int)g.ws_bytes : 0;

@@ -12,7 +12,14 @@ whole per-pair work -- uint8 HWC -> float CHW, ``forward(type="test_eval")``, th
 rows stay in a device table until one copy at the end.  The host therefore does per pair: two decodes (off-thread), one memcpy
 into pinned memory, two async H2D copies, one graph launch and one 16-byte device copy; it never waits for the GPU inside the
 loop (the reference's loop synchronises four times per batch, evaluate.py:38-50).  ``pipelined=False`` keeps the plain
-one-pair-at-a-time loop (eager launches, ``.cpu()`` per pair): same kernels, same bits -- ``tests/test_harness_gpu.py``."""
+one-pair-at-a-time loop (eager launches, ``.cpu()`` per pair): same kernels, same bits -- ``tests/test_harness_gpu.py``.
+
+``gpu_decode=True`` (default off) moves the JPEG decode onto the device: the worker threads only read and probe the files
+(``ops.jpeg_probe``), the compressed bytes go through the slot's pinned buffer and the copy stream, and the two decodes
+(``ops.jpeg_decode``, csrc/jpeg_dec.hip: Pillow's pixels bit for bit) run on the slot's stream straight into its uint8 staging
+buffers, eagerly, before the graph replay -- their launch shapes depend on the file.  Their status words are read back with the
+metric table; a nonzero one raises and names the file.  A work item with a file the decoder does not take (progressive, grey,
+restart intervals, ..., or H * W not a multiple of 4) goes the Pillow path unchanged, with one printed line."""
 from __future__ import annotations
 
 import glob
@@ -34,6 +41,35 @@ def _decode_rgb8(path):
     if arr.ndim == 2:
         arr = np.tile(arr[..., None], (1, 1, 3))
     return np.ascontiguousarray(arr[..., :3])
+
+
+class _JpegPair:
+    """one pair as the worker thread leaves it with gpu_decode: the two files' bytes and their probes"""
+    __slots__ = ("data", "info", "paths", "shape")
+
+    def __init__(self, data, info, paths):
+        self.data, self.info, self.paths = data, info, paths
+        self.shape = (info[0].H, info[0].W, 3)
+
+
+def _read_jpeg_pair(paths):
+    """the files of a pair and their probes, or the reason why the pair keeps the Pillow path"""
+    data, info = [], []
+    for path in paths:
+        with open(path, "rb") as f:
+            d = f.read()
+        i = ops.jpeg_probe(d)
+        if i is None:
+            return None, f"{path} is outside the GPU decoder's contract"
+        if i.ncomp != 3:
+            return None, f"{path} is grey"
+        if (i.H * i.W) % 4:
+            return None, f"{path}: {i.H}x{i.W} is not a size of the uint8 path"
+        data.append(d)
+        info.append(i)
+    if (info[0].H, info[0].W) != (info[1].H, info[1].W):
+        return None, f"{paths[0]} and {paths[1]} differ in size"
+    return _JpegPair(data, info, paths), None
 
 
 class UDISDataset:
@@ -87,6 +123,9 @@ class _Slot:
         self.pin_np = [p.numpy() for p in self.pin]
         self.stage = [torch.empty(host_shape, dtype=dt, device=device) for _ in range(2)]
         self.inputs = [torch.zeros((B, 3, H, W), dtype=torch.float32, device=device) for _ in range(2)]
+        self.device = device
+        self.jpin = self.jdev = self.jws = None         # gpu_decode: pinned / device bytes of the slot's files, decoder workspace
+        self.jconsumed = torch.cuda.Event()             # slot stream: the decodes out of jdev finished (jdev reusable)
         self.metric = torch.empty((B, 2), dtype=torch.float64, device=device)
         ws = ops.new_workspace(device)                 # this graph's own split-K slabs (graphs replay concurrently)
 
@@ -105,6 +144,17 @@ class _Slot:
         with torch.cuda.graph(self.graph), ops.workspace_scope(ws):
             body()
         self._keep = ws
+
+    def jpeg_buffers(self, nbytes, ws_bytes):
+        """the slot's byte buffers and decoder workspace, grown (rarely) when a work item needs more"""
+        if self.jpin is None or self.jpin.numel() < nbytes or self.jws.numel() < ws_bytes:
+            self.stream.synchronize()                   # nothing of this slot reads the old buffers any more
+            self.h2d_done.synchronize()
+            cap = max(2 * nbytes, 1 << 20, 0 if self.jpin is None else self.jpin.numel())
+            self.jpin = torch.empty((cap,), dtype=torch.uint8).pin_memory()
+            self.jdev = torch.empty((cap,), dtype=torch.uint8, device=self.device)
+            self.jws = torch.empty((max(2 * ws_bytes, 0 if self.jws is None else self.jws.numel()),), dtype=torch.uint8, device=self.device)
+        return self.jpin, self.jdev, self.jws
 
     def unstage(self):
         """device staging -> the graph's static float inputs, on the slot's stream (core/datasets.py:383-386 on the GPU)."""
@@ -130,8 +180,9 @@ class EvalPipeline:
     MAX_OUTSTANDING = 2
     MAX_SHAPES = 4          # distinct (batch, H, W, dtype) kept captured; each costs nslots x (a forward's activations + 64 MiB workspace + pinned staging)
 
-    def __init__(self, model, device, streams=3, decode_workers=None):
+    def __init__(self, model, device, streams=3, decode_workers=None, gpu_decode=False):
         self.model, self.device, self.nslots = model, device, max(1, int(streams))
+        self.gpu_decode = bool(gpu_decode)
         try:
             ncpu = len(os.sched_getaffinity(0))
         except AttributeError:
@@ -175,9 +226,19 @@ class EvalPipeline:
             self._slots.clear()
             self._gen = gen
 
-    @staticmethod
-    def _load(dataset, idx):
-        """host side of one work item: decode (worker thread) -> list of (array pair) + whether they are uint8 HWC."""
+    def _load(self, dataset, idx):
+        """host side of one work item: decode (worker thread) -> list of (array pair) + whether they are uint8 HWC.  With gpu_decode a
+        JPEG dataset's work item is a list of `_JpegPair` (bytes and probes) instead, unless one of its files keeps the Pillow path."""
+        if self.gpu_decode and hasattr(dataset, "image_list") and hasattr(dataset, "load_u8"):
+            pairs = []
+            for i in idx:
+                pair, why = _read_jpeg_pair(dataset.image_list[i])
+                if pair is None:
+                    print(f"gpu_decode: pairs {list(idx)} decoded with Pillow ({why})", flush=True)
+                    break
+                pairs.append(pair)
+            else:
+                return pairs, True
         if hasattr(dataset, "load_u8"):
             return [dataset.load_u8(i) for i in idx], True
         items = [dataset[i] for i in idx]              # generic dataset: float [3,H,W] tensors, uploaded as they are
@@ -205,11 +266,52 @@ class EvalPipeline:
             done.record()
             slot.inflight.append(done)
 
+    def _launch_jpeg(self, slot, sub, table, row, status, srow):
+        """`_launch` with the decode on the device: bytes -> pinned -> device on the copy stream, two decodes per pair on the slot's stream"""
+        while len(slot.inflight) >= self.MAX_OUTSTANDING:
+            slot.inflight.popleft().synchronize()
+        offs, total = [], 0
+        for p in sub:
+            for d in p.data:
+                offs.append(total)
+                total += (len(d) + 15) & ~15
+        ws_bytes = max(ops.jpeg_dec_workspace_bytes(i) for p in sub for i in p.info)
+        jpin, jdev, jws = slot.jpeg_buffers(total, ws_bytes)
+        slot.h2d_done.synchronize()                    # the previous H2D out of this slot's pinned buffers (long done)
+        jnp = jpin.numpy()
+        k = 0
+        for p in sub:
+            for d in p.data:
+                jnp[offs[k]:offs[k] + len(d)] = np.frombuffer(d, np.uint8)
+                k += 1
+        with torch.cuda.stream(self.copy_stream):
+            self.copy_stream.wait_event(slot.jconsumed)        # the decodes of the slot's previous files have read them
+            jdev[:total].copy_(jpin[:total], non_blocking=True)
+            slot.h2d_done.record()
+        with torch.cuda.stream(slot.stream):
+            slot.stream.wait_event(slot.h2d_done)
+            k = 0
+            for i, p in enumerate(sub):
+                for side in range(2):
+                    ops.jpeg_decode(jdev[offs[k]:offs[k] + len(p.data[side])], info=p.info[side], out=slot.stage[side][i], workspace=jws,
+                                    status=status[srow + k:srow + k + 1])
+                    k += 1
+            slot.jconsumed.record()
+            slot.unstage()
+            slot.consumed.record()
+            slot.graph.replay()
+            table[row:row + len(sub)].copy_(slot.metric, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            slot.inflight.append(done)
+
     def run(self, dataset, groups):
         """groups: list of index lists (one forward each).  Returns a CPU fp64 [sum(len(g)), 2] table in group order."""
         self._check_weights()
         n_rows = sum(len(g) for g in groups)
         table = torch.full((max(1, n_rows), 2), float("nan"), dtype=torch.float64, device=self.device)
+        status = torch.zeros((max(1, 2 * n_rows),), dtype=torch.int32, device=self.device)       # gpu_decode: one word per file
+        status_paths = {}
         ready = torch.cuda.Event()
         ready.record()                                  # the slot streams write rows of `table`: after its fill
         depth = max(2 * self.nslots, self.workers)
@@ -222,6 +324,20 @@ class EvalPipeline:
                 if nxt < len(groups):
                     futs.append(pool.submit(self._load, dataset, groups[nxt]))
                     nxt += 1
+                compressed = bool(pairs) and isinstance(pairs[0], _JpegPair)
+                if compressed:
+                    for sub in ([pairs] if len({p.shape for p in pairs}) == 1 else [[p] for p in pairs]):
+                        H, W = sub[0].shape[:2]
+                        slot = self._slot(launch % self.nslots, (len(sub), H, W), True)
+                        launch += 1
+                        if slot not in used:
+                            slot.stream.wait_event(ready)
+                            used.add(slot)
+                        for j, p in enumerate(sub):
+                            status_paths[2 * (row + j)], status_paths[2 * (row + j) + 1] = p.paths
+                        self._launch_jpeg(slot, sub, table, row, status, 2 * row)
+                        row += len(sub)
+                    continue
                 shapes = {p[0].shape for p in pairs} | {p[1].shape for p in pairs}
                 # one forward needs one shape: a batch of mixed shapes runs pair by pair (as the plain loop does)
                 for sub in ([pairs] if len(shapes) == 1 else [[p] for p in pairs]):
@@ -242,7 +358,12 @@ class EvalPipeline:
         for slot in used:
             torch.cuda.current_stream().wait_stream(slot.stream)
             slot.inflight.clear()
-        return table[:n_rows].cpu()                    # the loop's one synchronisation
+        out = table[:n_rows].cpu()                     # the loop's one synchronisation
+        if status_paths:
+            bad = [(status_paths[j], int(v)) for j, v in enumerate(status.cpu().tolist()) if v and j in status_paths]
+            if bad:
+                raise RuntimeError("gpu_decode: the scan of " + ", ".join(f"{p} (status {v})" for p, v in bad) + " does not hold the frame's blocks")
+        return out
 
 
 def _groups(dataset, mine, batch_size):
@@ -251,8 +372,11 @@ def _groups(dataset, mine, batch_size):
 
 
 @torch.no_grad()
-def validate_with_model(model, val_dataset, batch_size=1, device=None, verbose=False, pipelined=True, streams=3, decode_workers=None):
-    """Sharded evaluate.py:23-107.  Returns (result_dict, table[n_pairs, 2] of per-pair (psnr, ssim))."""
+def validate_with_model(model, val_dataset, batch_size=1, device=None, verbose=False, pipelined=True, streams=3, decode_workers=None, gpu_decode=False):
+    """Sharded evaluate.py:23-107.  Returns (result_dict, table[n_pairs, 2] of per-pair (psnr, ssim)).  gpu_decode: decode the JPEG files on
+    the device (the pipelined loop only; module docstring)."""
+    if gpu_decode and not pipelined:
+        raise ValueError("gpu_decode belongs to the pipelined loop")
     rank, world, local = sdist.init()
     device = device or torch.device("cuda", local)
     n = len(val_dataset)
@@ -264,6 +388,7 @@ def validate_with_model(model, val_dataset, batch_size=1, device=None, verbose=F
         if pipe is None or pipe.nslots != max(1, int(streams)) or pipe.device != device:
             pipe = EvalPipeline(model, device, streams=streams, decode_workers=decode_workers)
             model._eval_pipeline = pipe
+        pipe.gpu_decode = bool(gpu_decode)
         with torch.cuda.device(device):
             vals = pipe.run(val_dataset, _groups(val_dataset, mine, batch_size)).tolist() if mine else []
         if verbose:

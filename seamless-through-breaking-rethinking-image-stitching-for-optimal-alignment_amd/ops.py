@@ -6,7 +6,8 @@ import ctypes as C
 
 import torch
 
-from ._lib import ChainDesc, GemmDesc, MlpDesc, check, lib
+from ._lib import ChainDesc, GemmDesc, JpegDecParams, MlpDesc, check, lib
+from .jpeg_probe import JpegInfo, probe as _jpeg_probe
 from ._lib import StitchError as StitchErrorBase
 
 ACT = dict(none=0, relu=1, gelu=2, sigmoid=3, tanh=4, lrelu=5)
@@ -15,6 +16,7 @@ EPI = dict(store=0, add=1, mul=2, gru=3, axpy=4, zr=5)
 assert lib.st_abi_gemm_desc_size() == C.sizeof(GemmDesc), "st_gemm_desc ABI mismatch between header and binding"
 assert lib.st_abi_chain_desc_size() == C.sizeof(ChainDesc), "st_chain_desc ABI mismatch between header and binding"
 assert lib.st_abi_mlp_desc_size() == C.sizeof(MlpDesc), "st_mlp_desc ABI mismatch between header and binding"
+assert lib.st_abi_jpeg_dec_params_size() == C.sizeof(JpegDecParams), "st_jpeg_dec_params ABI mismatch between header and binding"
 
 
 def _stream():
@@ -787,6 +789,60 @@ def jpeg_bytes(buf, nbytes):
     """The file of `jpeg_encode` on the host: reads the count, then copies exactly that many bytes."""
     n = int(nbytes.item())
     return buf[:n].cpu().numpy().tobytes()
+
+
+def jpeg_probe(data):
+    """Host-side marker parse of a JPEG file (bytes-like, or a CPU uint8 tensor): the `JpegInfo` `jpeg_decode` needs, or None when the file is
+    outside the decoder's contract (progressive, restart intervals, other sampling factors, ...: jpeg_probe.py) and keeps the Pillow path."""
+    if isinstance(data, torch.Tensor):
+        data = data.numpy().tobytes()
+    return _jpeg_probe(data)
+
+
+def jpeg_dec_workspace_bytes(info):
+    return lib.st_jpeg_dec_workspace_bytes(info.H, info.W, info.ncomp, info.hs, info.vs, info.scan_len)
+
+
+def jpeg_decode(data, info=None, out=None, workspace=None, status=None):
+    """evaluate.py / out.py `np.array(Image.open(path))` on the GPU: the file's bytes -> (uint8 [H,W,3] or [H,W,1] device tensor, status), the
+    pixels Pillow returns on libjpeg-turbo, bit for bit (csrc/jpeg_dec.hip).  `data`: bytes or a CPU uint8 tensor (uploaded on the current
+    stream; `info` defaults to `jpeg_probe(data)`), or a device uint8 tensor (`info` required).  `out`: a uint8 [H,W,C] device view to decode
+    into, rows may be strided.  status: device int32 [1] (or the given one-element int32 device view): 0, or nonzero when the scan ended
+    before the frame's blocks or ran on after them (pixels then unspecified).  No host synchronisation; current stream.
+    `workspace`: a uint8 device tensor of at least `jpeg_dec_workspace_bytes(info)` to reuse (stream-ordered)."""
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        data = torch.frombuffer(bytearray(data), dtype=torch.uint8)
+    if data.dtype != torch.uint8 or data.dim() != 1:
+        raise ValueError(f"uint8 [nbytes] expected, got {data.dtype} {tuple(data.shape)}")
+    if not data.is_cuda:
+        if info is None:
+            info = jpeg_probe(data)
+            if info is None:
+                raise StitchErrorBase("jpeg_decode: unsupported file (jpeg_probe returned None)")
+        data = data.cuda()              # a blocking copy: the host tensor may be a temporary of this call
+    if info is None:
+        raise ValueError("jpeg_decode of a device tensor needs the JpegInfo of jpeg_probe")
+    data = data.contiguous()
+    H, W, ch = info.H, info.W, info.ncomp
+    if out is None:
+        out = torch.empty((H, W, ch), device=data.device, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (H, W, ch) or (ch > 1 and out.stride(2) != 1) or (W > 1 and out.stride(1) != ch):
+        raise ValueError(f"out: uint8 [{H},{W},{ch}] with dense pixels expected, got {out.dtype} {tuple(out.shape)} strides {out.stride()}")
+    row_stride = out.stride(0) if H > 1 else W * ch
+    need = jpeg_dec_workspace_bytes(info)
+    if need == 0:
+        raise StitchErrorBase(f"st_jpeg_decode_u8: unsupported frame {H}x{W}x{ch}, sampling {info.hs}x{info.vs}")
+    if workspace is None:
+        workspace = torch.empty((need,), device=data.device, dtype=torch.uint8)
+    if status is None:
+        status = torch.empty((1,), device=data.device, dtype=torch.int32)
+    if status.dtype != torch.int32 or status.numel() != 1:
+        raise ValueError("status: one int32 element expected")
+    prm = JpegDecParams(H, W, ch, info.hs, info.vs, (C.c_int32 * 3)(*info.tq), (C.c_int32 * 3)(*info.td), (C.c_int32 * 3)(*info.ta),
+                        (C.c_int32 * 2)(*info.q_off), (C.c_int32 * 2)(*info.dc_off), (C.c_int32 * 2)(*info.ac_off), info.scan_off, info.scan_len)
+    check(lib.st_jpeg_decode_u8(_p(data), data.numel(), C.byref(prm), _p(out), row_stride, _p(status), _pc(workspace),
+                                workspace.numel() * workspace.element_size(), _stream()), "st_jpeg_decode_u8")
+    return out, status
 
 
 def masked_psnr_ssim(image1, final_warp_output, out=None):

@@ -1,0 +1,196 @@
+"""The GPU JPEG decoder (csrc/jpeg_dec.hip, `ops.jpeg_decode`) against Pillow, and what it does to the evaluation loop.
+
+    python tools/bench_jpeg_decode.py [--out profiles/jpeg_decode_bench.json] [--parent-root PATH] [--pairs 48] [--rounds 5] [--no-profile]
+
+* per file: HIP-event time of one decode of device-resident bytes (median of single calls, and back-to-back throughput with one
+  workspace) for a 512x512 4:2:0 file at quality 75 and 95, a 1024x1024 file and a 512x512 0/255 mask (L), against Pillow's decode of
+  the same bytes on one thread of this box; the launches of the synchronise stage and the rounds its fixpoint needs (CPU model);
+* per kernel: one `rocprofv3 --kernel-trace --stats` child making 200 decodes of the 512x512 quality-75 file;
+* the loop: `validate_with_model` on synthetic 512x512 JPEG pairs with `gpu_decode` off and on, each run a child process, the variants
+  alternating, median of the rounds: pairs/s, host CPU seconds per pair (`time.process_time`: all threads) and host-to-device bytes
+  per pair.  `--parent-root` adds the loop of another checkout (the commit before the switch existed, built) to the alternation.
+"""
+import argparse
+import csv
+import glob
+import io
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def files():
+    import _jpeg_ref as eref
+    from PIL import Image
+
+    def pil(u8, **kw):
+        buf = io.BytesIO()
+        Image.fromarray(u8).save(buf, format="JPEG", **kw)
+        return buf.getvalue()
+    return {"rgb_512_q75": pil(eref._smooth(512, 512, 3, 5)), "rgb_512_q95": pil(eref._smooth(512, 512, 3, 5), quality=95),
+            "rgb_1024_q75": pil(eref._smooth(1024, 1024, 3, 6)), "mask_512": pil(((eref._smooth(512, 512, 0, 7) > 127) * 255).astype(np.uint8))}
+
+
+def pillow_ms(data, n=20):
+    from PIL import Image
+    ts = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        np.array(Image.open(io.BytesIO(data)))
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def decode_times(data, n=50):
+    import torch
+    from stitch_amd import ops
+    info = ops.jpeg_probe(data)
+    dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    ws = torch.empty((ops.jpeg_dec_workspace_bytes(info),), dtype=torch.uint8, device="cuda")
+    out = torch.empty((info.H, info.W, info.ncomp), dtype=torch.uint8, device="cuda")
+    for _ in range(5):
+        ops.jpeg_decode(dev, info=info, out=out, workspace=ws)
+    torch.cuda.synchronize()
+    single = []
+    for _ in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ops.jpeg_decode(dev, info=info, out=out, workspace=ws)
+        e1.record()
+        e1.synchronize()
+        single.append(e0.elapsed_time(e1))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        ops.jpeg_decode(dev, info=info, out=out, workspace=ws)
+    e1.record()
+    e1.synchronize()
+    return float(np.median(single)), e0.elapsed_time(e1) / n
+
+
+def profile_child(n):
+    d = tempfile.mkdtemp(prefix="jpegd_prof_")
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "jpegd", "--output-format", "csv", "--",
+           sys.executable, os.path.abspath(__file__), "--inner-profile", str(n)]
+    subprocess.run(cmd, check=True, timeout=600, stdout=subprocess.DEVNULL)
+    path = (glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True) or [None])[0]
+    if path is None:
+        raise RuntimeError(f"rocprofv3 wrote no kernel_stats.csv under {d}")
+    rows = []
+    for r in csv.DictReader(open(path)):
+        if "jpeg" in r["Name"]:
+            name = re.sub(r"\(.*", "", re.sub(r"^void ", "", r["Name"]).replace("(anonymous namespace)::", ""))
+            rows.append(dict(name=name, calls_per_decode=int(r["Calls"]) / n, us_per_decode=float(r["TotalDurationNs"]) / n / 1e3))
+    return sorted(rows, key=lambda r: -r["us_per_decode"])
+
+
+def write_dataset(root, pairs):
+    from PIL import Image
+    sys.path.insert(0, ROOT)
+    from stitch_amd.data import structured_pair
+    for d in ("input1", "input2"):
+        os.makedirs(os.path.join(root, "testing", d), exist_ok=True)
+    base = [structured_pair(512, 512, seed=40 + i) for i in range(8)]
+    nbytes = 0
+    for i in range(pairs):
+        for d, t in zip(("input1", "input2"), base[i % 8]):
+            path = os.path.join(root, "testing", d, f"{i:06d}.jpg")
+            Image.fromarray(t[0].permute(1, 2, 0).numpy().astype(np.uint8)).save(path, quality=95)
+            nbytes += os.path.getsize(path)
+    return nbytes / pairs
+
+
+def inner_eval(root, data_dir, gpu_decode, rounds):
+    """child: `rounds` timed runs of the loop of the checkout at `root` (after one untimed run that captures the graphs)"""
+    sys.path.insert(0, root)
+    import torch
+    import stitch_amd
+    from stitch_amd import evaluate as ev
+    from oracle import spec
+    cfg, _ = stitch_amd.load_inference_config("all_img1_with_inpaint_g12_transRef")
+    model = stitch_amd.build_model(cfg)
+    model.load_state_dict(spec.seeded_state_dict(1234), strict=True)
+    model = model.cuda().eval()
+    ds = ev.UDISDataset(data_dir, phase="testing")
+    kw = dict(gpu_decode=True) if gpu_decode else {}
+    ev.validate_with_model(model, ds, batch_size=1, **kw)
+    out = []
+    for _ in range(rounds):
+        torch.cuda.synchronize()
+        t0, c0 = time.perf_counter(), time.process_time()
+        ev.validate_with_model(model, ds, batch_size=1, **kw)
+        torch.cuda.synchronize()
+        out.append(dict(pairs_per_s=len(ds) / (time.perf_counter() - t0), cpu_s_per_pair=(time.process_time() - c0) / len(ds)))
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def loop_bench(pairs, rounds, parent_root):
+    data_dir = tempfile.mkdtemp(prefix="jpegd_loop_") + "/"
+    file_bytes = write_dataset(data_dir, pairs)
+    variants = [("gpu_decode_off", ROOT, 0), ("gpu_decode_on", ROOT, 1)] + ([("parent", parent_root, 0)] if parent_root else [])
+    runs = {name: [] for name, _, _ in variants}
+    for _ in range(rounds):                                       # alternating: one timed run per child, the variants in turn
+        for name, root, on in variants:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--inner-eval", root, data_dir, str(on)], check=True, timeout=900,
+                               stdout=subprocess.PIPE, text=True)
+            line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1]
+            runs[name].extend(json.loads(line[7:]))
+    res = {"pairs": pairs, "rounds": rounds, "h2d_bytes_per_pair": {"gpu_decode_off": 2 * 512 * 512 * 3, "gpu_decode_on": file_bytes}}
+    for name, rs in runs.items():
+        res[name] = dict(pairs_per_s_median=float(np.median([r["pairs_per_s"] for r in rs])), pairs_per_s=[round(r["pairs_per_s"], 2) for r in rs],
+                         cpu_s_per_pair_median=float(np.median([r["cpu_s_per_pair"] for r in rs])))
+    return res
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_bench.json"))
+    p.add_argument("--parent-root", default="")
+    p.add_argument("--pairs", type=int, default=48)
+    p.add_argument("--rounds", type=int, default=5)
+    p.add_argument("--no-profile", action="store_true")
+    p.add_argument("--inner-profile", type=int, default=0)
+    p.add_argument("--inner-eval", nargs=3, default=None)
+    args = p.parse_args()
+    if args.inner_eval:
+        return inner_eval(args.inner_eval[0], args.inner_eval[1], int(args.inner_eval[2]), 1)
+    sys.path.insert(0, ROOT)
+    import torch
+    from stitch_amd import ops
+    if args.inner_profile:
+        data = files()["rgb_512_q75"]
+        info = ops.jpeg_probe(data)
+        dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+        for _ in range(args.inner_profile):
+            ops.jpeg_decode(dev, info=info)
+        torch.cuda.synchronize()
+        return None
+    import _jpeg_dec_ref as dref
+    res = {"device": torch.cuda.get_device_name(0), "per_file": {}}
+    for name, data in files().items():
+        single, b2b = decode_times(data)
+        info = ops.jpeg_probe(data)
+        model = dref.sync_model(data, 1024)
+        res["per_file"][name] = dict(file_bytes=len(data), pillow_ms=pillow_ms(data), gpu_single_ms=single, gpu_back_to_back_ms=b2b,
+                                     subsequences=len(model["states"]), sync_launches=-(-len(model["states"]) // 256), fixpoint_rounds=model["rounds"])
+        print(name, res["per_file"][name], flush=True)
+    if not args.no_profile:
+        res["kernels_rgb_512_q75"] = profile_child(200)
+    res["eval_loop"] = loop_bench(args.pairs, args.rounds, args.parent_root)
+    print(json.dumps(res["eval_loop"]), flush=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
