@@ -550,7 +550,8 @@ int st_compose_normalize(const float* x, float* out, int64_t n, void* stream);
 
 /* ---- TPS post-pipeline (the core/inference package, in-tree "kornia" back-end, no inpainter) ---------------- */
 /* preprocess (tps_pipline.py:213-244): zero-padded k x k mean of flow [B,C,H,W] (row-major window sum / k^2), optional
- * negation (residual_flow_use_forward = False), optional * valid [B,1,H,W].                                             */
+ * negation (residual_flow_use_forward = False), optional * valid [B,1,H,W].  One plane per grid layer: B*C <= 65535,
+ * ST_EINVAL beyond.                                                                                                      */
 int st_flow_boxavg(const float* flow, const float* valid, float* out, int32_t B, int32_t C, int32_t H, int32_t W,
                    int32_t k, int32_t negate, void* stream);
 /* advanced_uniform_sample_border_points (sample_point_methods.py:70-90): image [C,H,W] -> grad [H,W] =
@@ -561,7 +562,8 @@ int st_sobel_magnitude(const float* img, float* grad, int32_t C, int32_t H, int3
 int st_range_argmax(const float* grad, const int32_t* ranges, int32_t* out_flat_idx, int32_t n_ranges, int32_t H,
                     int32_t W, void* stream);
 /* get_point_pairs flow lookup (core/inference/utils.py:61-68) / border_points_mask filter (tps_pipline.py:111-128):
- * out[i, p] = planes[p, y_i, x_i] for integer points (x, y).                                                             */
+ * out[i, p] = planes[p, y_i, x_i] for integer points (x, y); a point outside the H x W image gives 0.  H, W > 0 and
+ * n*P < 2^31 - 255 (computed in 64 bits), ST_EINVAL otherwise.                                                           */
 int st_gather_points(const float* planes, const int32_t* points_xy, float* out, int32_t n, int32_t P, int32_t H,
                      int32_t W, void* stream);
 /* TPS fit f(sites_i) = values_i, f(v) = a0 + [ax ay].v + sum_j w_j U(|v - centers_j|) -> kernel_w [n,2], affine_w [3,2];
@@ -569,20 +571,24 @@ int st_gather_points(const float* planes, const int32_t* points_xy, float* out, 
  * called by warp_by_tps (tps_pipline.py:362-378, kornia_tps.py:47-112): normalised points, U = 0.5 d2 log(d2 + 1e-8);
  * mode 1 = pixel-unit r^2 log r^2 spline with centers = sites (OpenCV ThinPlateSplineShapeTransformer's formulation,
  * opencv_tps.py:8-18).  status (device int32, may be NULL): 0, or 1 when a pivot collapsed to rounding level (coincident or
- * collinear control points: the reference's torch.linalg.solve raises there) -- the weights are then meaningless.       */
+ * collinear control points: the reference's torch.linalg.solve raises there) -- the weights are then meaningless.
+ * The augmented [n+3, n+5] fp64 matrix is kept in LDS while (n+3)*(n+5)*8 <= 150 KiB, i.e. for n <= 134; from n = 135 on
+ * it lives in work_f64 (same arithmetic, same result).                                                                   */
 int st_tps2_solve(const float* sites, const float* centers, const float* values, void* work_f64, float* kernel_w,
                   float* affine_w, int32_t n, int32_t mode, int32_t* status, void* stream);
 /* warp_image_tps (kornia_tps.py:114-176): img [C,H,W] -> out [C,H,W]; centers [n,2]; grid_sample(bilinear, zeros).  mode 0 =
  * kornia (normalised mesh), 1 = pixel-unit spline sampled directly, 3 = 1 on uint8 data as the reference's OpenCV branch sees it
- * (opencv_tps.py + utils.py:10: taps truncated to 0..255 integers, result rounded half-to-even and saturated).            */
+ * (opencv_tps.py + utils.py:10: taps truncated to 0..255 integers, result rounded half-to-even and saturated).  Any other
+ * mode, H or W < 2, n < 1 or n > 3800 (16 n bytes of LDS): ST_EINVAL.                                                     */
 int st_tps2_warp(const float* img, const float* centers, const float* kernel_w, const float* affine_w, float* out,
                  int32_t C, int32_t H, int32_t W, int32_t n, float kernel_scale, float affine_scale,
                  int32_t align_corners, int32_t mode, void* stream);
 /* cv2.erode / cv2.dilate with a k x k rectangle (tps_pipline.py:143-148) = two 1-D passes of this filter (axis 0: x,
- * axis 1: y), window clipped to the image; in != out.                                                                    */
+ * axis 1: y), window clipped to the image; in != out.  One plane per grid layer: planes <= 65535, ST_EINVAL beyond.      */
 int st_minmax_filter(const float* in, float* out, int32_t planes, int32_t H, int32_t W, int32_t k, int32_t is_max,
                      int32_t axis, void* stream);
-/* tps_pipline.py:139-141: inv [h,w] = 1 - (mean_c(warped_mask [C,h,w]) >= 0.5).                                          */
+/* tps_pipline.py:139-141: inv [h,w] = 1 - (mean_c(warped_mask [C,h,w]) >= 0.5).  This entry and the elementwise ones below
+ * (st_tps_mix_blend, st_mix_stage_a, st_mix_stage_b, st_mix_mul_mask, st_blend_pair) return ST_EINVAL for h <= 0 or w <= 0. */
 int st_tps_mask_inv(const float* warped_mask, float* inv, int32_t C, int32_t h, int32_t w, void* stream);
 /* tps_pipline.py:150-176 with inv_clean = dilate(erode(inv)): tps3 *= tmask (in place), tmask [h,w], mix3 = output2 of
  * the flow/TPS mix, mixmask [h,w], blend3 uint8 [3,h,w] = clip((output1*mask1 + mix*mixmask) / (mask1 + mixmask)).      */
@@ -638,7 +644,8 @@ int st_inpaint_telea_fill(const int32_t* ring_counts_host, int32_t nrings, int32
 /* fit of the two splines f(sites_i) = delta_i (sites = c_dst, delta = c_src - c_dst, both [n,2] float32, 3 <= n <= 4096):
  * [[K, P], [P^T, 0]] theta = [delta; 0], K_ij = U(|sites_i - sites_j|), U(r) = r^2 ln(r + 1e-6), P = [1, x, y], in fp64 ->
  * kernel_w [n,2], affine_w [3,2] float32.  work_f64: (n+3)*(n+6) doubles.  status (device int32, required): 0, or 1 when a
- * pivot collapsed to rounding level (coincident or collinear sites).                                                      */
+ * pivot collapsed to rounding level (coincident or collinear sites).  LDS for n <= 134, work_f64 from n = 135 on, as for
+ * st_tps2_solve.                                                                                                          */
 int st_tps_other_solve(const float* sites, const float* delta, void* work_f64, float* kernel_w, float* affine_w, int32_t n,
                        int32_t* status, void* stream);
 /* remap maps [h,w] float32 of the fitted splines (centers = sites [n,2], 1 <= n <= 4096): on the numpy.linspace(0, 1) float32

@@ -46,6 +46,7 @@ __global__ __launch_bounds__(256) void flow_boxavg_kernel(const float* __restric
 extern "C" int st_flow_boxavg(const float* flow, const float* valid, float* out, int32_t B, int32_t C, int32_t H, int32_t W,
                               int32_t k, int32_t negate, void* stream) {
     if (!flow || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || k < 1 || !(k & 1)) return ST_EINVAL;
+    if ((int64_t)B * C > 65535) return ST_EINVAL;                         // one plane per gridDim.z
     dim3 grid((W + 63) / 64, (H + 3) / 4, B * C);
     hipLaunchKernelGGL(flow_boxavg_kernel, grid, dim3(256), 0, (hipStream_t)stream, flow, valid, out, B * C, C, H, W, k, negate);
     ST_CHECK_LAUNCH();
@@ -138,8 +139,10 @@ __global__ void gather_points_kernel(const float* __restrict__ planes, const int
 
 extern "C" int st_gather_points(const float* planes, const int32_t* points_xy, float* out, int32_t n, int32_t P, int32_t H,
                                 int32_t W, void* stream) {
-    if (!planes || !points_xy || !out || n <= 0 || P <= 0) return ST_EINVAL;
-    hipLaunchKernelGGL(gather_points_kernel, dim3((n * P + 255) / 256), dim3(256), 0, (hipStream_t)stream, planes, points_xy, out,
+    if (!planes || !points_xy || !out || n <= 0 || P <= 0 || H <= 0 || W <= 0) return ST_EINVAL;
+    const int64_t total = (int64_t)n * P;                                  // the kernel indexes n * P in int
+    if (total > 0x7fffffff - 255) return ST_EINVAL;
+    hipLaunchKernelGGL(gather_points_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, planes, points_xy, out,
                        n, P, H, W);
     ST_CHECK_LAUNCH();
     return ST_OK;
@@ -253,6 +256,7 @@ extern "C" int st_tps2_warp(const float* img, const float* centers, const float*
                             int32_t C, int32_t H, int32_t W, int32_t n, float kernel_scale, float affine_scale,
                             int32_t align_corners, int32_t mode, void* stream) {
     if (!img || !centers || !kernel_w || !affine_w || !out || C <= 0 || H < 2 || W < 2 || n < 1 || n > 3800) return ST_EINVAL;
+    if (mode != 0 && mode != 1 && mode != 3) return ST_EINVAL;             // 2 would be "kornia units, quantised": nothing defines it
     const size_t lds = (size_t)4 * n * sizeof(float);
     hipLaunchKernelGGL(tps2_warp_kernel, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), lds, (hipStream_t)stream, img, centers,
                        kernel_w, affine_w, out, C, H, W, n, kernel_scale, affine_scale, align_corners, mode);
@@ -281,7 +285,7 @@ __global__ __launch_bounds__(256) void minmax_filter_kernel(const float* __restr
 
 extern "C" int st_minmax_filter(const float* in, float* out, int32_t planes, int32_t H, int32_t W, int32_t k, int32_t is_max,
                                 int32_t axis, void* stream) {
-    if (!in || !out || in == out || planes <= 0 || H <= 0 || W <= 0 || k < 1 || !(k & 1)) return ST_EINVAL;
+    if (!in || !out || in == out || planes <= 0 || planes > 65535 || H <= 0 || W <= 0 || k < 1 || !(k & 1)) return ST_EINVAL;   // one plane per gridDim.z
     dim3 grid((W + 63) / 64, (H + 3) / 4, planes);
     hipLaunchKernelGGL(minmax_filter_kernel, grid, dim3(256), 0, (hipStream_t)stream, in, out, H, W, k, is_max, axis);
     ST_CHECK_LAUNCH();
@@ -330,7 +334,7 @@ __global__ void tps_mix_blend_kernel(float* __restrict__ tps, const float* __res
 }
 
 extern "C" int st_tps_mask_inv(const float* warped_mask, float* inv, int32_t C, int32_t h, int32_t w, void* stream) {
-    if (!warped_mask || !inv || C <= 0) return ST_EINVAL;
+    if (!warped_mask || !inv || C <= 0 || h <= 0 || w <= 0) return ST_EINVAL;
     const size_t hw = (size_t)h * w;
     hipLaunchKernelGGL(tps_mask_inv_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, warped_mask, inv, C, hw);
     ST_CHECK_LAUNCH();
@@ -340,7 +344,8 @@ extern "C" int st_tps_mask_inv(const float* warped_mask, float* inv, int32_t C, 
 extern "C" int st_tps_mix_blend(float* tps3, const float* inv_clean, const float* final_warp3, const float* output1_3,
                                 const float* mask1_3, float* tmask, float* mix3, float* mixmask, uint8_t* blend3, int32_t h,
                                 int32_t w, void* stream) {
-    if (!tps3 || !inv_clean || !final_warp3 || !output1_3 || !mask1_3 || !tmask || !mix3 || !mixmask || !blend3) return ST_EINVAL;
+    if (!tps3 || !inv_clean || !final_warp3 || !output1_3 || !mask1_3 || !tmask || !mix3 || !mixmask || !blend3 || h <= 0 || w <= 0)
+        return ST_EINVAL;
     const size_t hw = (size_t)h * w;
     hipLaunchKernelGGL(tps_mix_blend_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, tps3, inv_clean, final_warp3,
                        output1_3, mask1_3, tmask, mix3, mixmask, blend3, hw);
@@ -436,7 +441,8 @@ __global__ void mix_stage_a_kernel(const float* __restrict__ fw, const float* __
 
 extern "C" int st_mix_stage_a(const float* final_warp3, const float* occ, const float* mask1_3, const float* tps3, const float* tmask,
                               float* tfw3, float* tfwm3, float* iam0, int32_t h, int32_t w, int32_t method, void* stream) {
-    if (!final_warp3 || !occ || !mask1_3 || !tps3 || !tmask || !tfw3 || !tfwm3 || !iam0 || method < 0 || method > 1) return ST_EINVAL;
+    if (!final_warp3 || !occ || !mask1_3 || !tps3 || !tmask || !tfw3 || !tfwm3 || !iam0 || method < 0 || method > 1 || h <= 0 || w <= 0)
+        return ST_EINVAL;
     const size_t hw = (size_t)h * w;
     hipLaunchKernelGGL(mix_stage_a_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, final_warp3, occ, mask1_3, tps3, tmask,
                        tfw3, tfwm3, iam0, hw, method);
@@ -461,7 +467,7 @@ __global__ void mix_stage_b_kernel(const float* __restrict__ iam, const float* _
 
 extern "C" int st_mix_stage_b(const float* iam, const float* dil, const float* mask1_3, const float* tfw3, const float* output1_3,
                               float* only_img1_3, float* other0, int32_t h, int32_t w, void* stream) {
-    if (!iam || !dil || !mask1_3 || !tfw3 || !output1_3 || !only_img1_3 || !other0) return ST_EINVAL;
+    if (!iam || !dil || !mask1_3 || !tfw3 || !output1_3 || !only_img1_3 || !other0 || h <= 0 || w <= 0) return ST_EINVAL;
     const size_t hw = (size_t)h * w;
     hipLaunchKernelGGL(mix_stage_b_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, iam, dil, mask1_3, tfw3, output1_3,
                        only_img1_3, other0, hw);
@@ -484,7 +490,7 @@ __global__ void mix_mul_mask_kernel(const float* __restrict__ img, const float* 
 
 extern "C" int st_mix_mul_mask(const float* img3, const float* mask, float* out3, int32_t h, int32_t w, int32_t invert, int32_t clip,
                                void* stream) {
-    if (!img3 || !out3) return ST_EINVAL;
+    if (!img3 || !out3 || h <= 0 || w <= 0) return ST_EINVAL;
     const size_t hw = (size_t)h * w;
     hipLaunchKernelGGL(mix_mul_mask_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, img3, mask, out3, hw, invert, clip,
                        mask ? 1 : 0);
@@ -508,7 +514,8 @@ __global__ void blend_pair_kernel(const float* __restrict__ o1, const float* __r
 
 extern "C" int st_blend_pair(const float* output1_3, const float* mask1_3, const float* output2_3, const float* mask2, int32_t mask2_planes,
                              uint8_t* blend3, int32_t h, int32_t w, void* stream) {
-    if (!output1_3 || !mask1_3 || !output2_3 || !mask2 || !blend3 || (mask2_planes != 1 && mask2_planes != 3)) return ST_EINVAL;
+    if (!output1_3 || !mask1_3 || !output2_3 || !mask2 || !blend3 || (mask2_planes != 1 && mask2_planes != 3) || h <= 0 || w <= 0)
+        return ST_EINVAL;
     const size_t hw = (size_t)h * w;
     hipLaunchKernelGGL(blend_pair_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, output1_3, mask1_3, output2_3, mask2,
                        mask2_planes, blend3, hw);

@@ -14,14 +14,15 @@ __device__ __forceinline__ void tps_gauss_jordan(UFn ufn, const float* __restric
                                                  const float* __restrict__ rhs, double* __restrict__ work_g, float* __restrict__ kw,
                                                  float* __restrict__ aw, int n, int use_lds, int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) double tps2_lds[];
-    double* __restrict__ work = use_lds ? tps2_lds : work_g;       // n <= ~130: the augmented matrix lives in LDS (91 pivot steps
-                                                                   // of global round trips cost 1.9 ms; in LDS 0.2 ms)
+    double* __restrict__ work = use_lds ? tps2_lds : work_g;       // n <= 134 ((n+3)(n+5) doubles <= 150 KiB, the callers' test): the
+                                                                   // augmented matrix lives in LDS (91 pivot steps of global round
+                                                                   // trips cost 1.9 ms; in LDS 0.2 ms); from n = 135 on in work_g
     const int n3 = n + 3, ld = n + 5;
     __shared__ int s_piv;
     __shared__ double s_pmin, s_pmax;             // smallest / largest pivot magnitude: singular-system detection
     __shared__ double s_best[4];
     __shared__ int s_idx[4];
-    __shared__ double s_fac_lds[144];             // per-row elimination factors: LDS mode has n + 3 <= 140
+    __shared__ double s_fac_lds[144];             // per-row elimination factors: LDS mode has n + 3 <= 137
     double* __restrict__ s_fac = use_lds ? s_fac_lds : work_g + (size_t)n3 * ld;   // otherwise behind the matrix ((n+3)*(n+6) scratch)
     for (int e = threadIdx.x; e < n3 * ld; e += 256) {
         const int r = e / ld, c = e % ld;
