@@ -203,7 +203,8 @@ int st_abi_mlp_desc_size(void);
  *   st_mlp128_split3_image_bytes(hidden, with_proj, &bytes)  size of the image
  *   st_mlp128_split3_pack(w1, b1, w2, wp, bp, hidden, image, image_bytes, stream)   wp / bp NULL = no projection
  *   st_mlp128_split3(desc, image, image_bytes, stream)   desc->w1 / b1 / w2 / bp are not read; desc->wp != NULL <=> the image holds a projection.
- * plan4[0] = 9; reported to the observer like st_mlp128 with split3 = 1.                                                            */
+ * res may alias out, with the projection as well (x stays in registers; a lane reads its residual values right before it writes the same
+ * addresses); st_mlp128 allows that alias without the projection only.  plan4[0] = 9; reported to the observer like st_mlp128 with split3 = 1. */
 int st_mlp128_split3_image_bytes(int32_t hidden, int32_t with_proj, int64_t* bytes);
 int st_mlp128_split3_pack(const float* w1, const float* b1, const float* w2, const float* wp, const float* bp, int32_t hidden, void* image,
                           int64_t image_bytes, void* stream);
@@ -493,7 +494,9 @@ int st_patch_embed_split3(const float* cost_maps, const float* const* weights, i
  *   out[R, 128] = LayerNorm_affine( ReLU( x[R, 64] . w1^T + tab[r mod P] ) . w2^T + b2 )
  * w1 = ffn_with_coord.0's first 64 input columns [128, ld1], tab [P, 128] = its position half + bias (st_patch_embed's pe_bias), w2 [128, 128];
  * both weight matrices are packed once into a 144-KiB image that the kernel holds in LDS (st_pe_tail_split3_image_bytes / _pack).  st_patch_embed_split3
- * takes the image as tail_image (NULL = the three separate launches, s4 [M P, 128] scratch required).  plan4[0] = 11, reported as R x 192 x 128.        */
+ * takes the image as tail_image (NULL = the three separate launches, s4 [M P, 128] scratch required).  plan4[0] = 11, reported as R x 192 x 128.
+ * A non-finite value of x stays in its row but does not show in it: the hidden layer of such a row is NaN, the ReLU is v_max_f32, which returns 0
+ * for a NaN (as st_conv_gemm's), and the row leaves as LayerNorm_affine(b2).                                                                          */
 int st_pe_tail_split3_image_bytes(int64_t* bytes);
 int st_pe_tail_split3_pack(const float* w1, int32_t ld1, const float* w2, void* image, int64_t image_bytes, void* stream);
 int st_pe_tail_split3(const float* x, const float* tab, int32_t P, const void* image, int64_t image_bytes, const float* b2, const float* gamma,
