@@ -665,30 +665,37 @@ int st_remap_cubic_u8(const float* src, int32_t planes, int32_t src_h, int32_t s
 
 /* ---- TransRef inpainter (core/inference/mix_methods/utils/transref_inpainter.py, TransRef/models/*.py; csrc/transref.hip) -------- */
 /* softmax(scale Q K^T) V per head, flash style on the fp32 matrix cores: q [Nq, ldq], k [Nk, ldk], v [Nk, ldv], out [Nq, ldo] row-major,
- * head h in columns [h D, (h + 1) D).  D in {32, 64, 80, 128, 160, 256}, any Nq, Nk >= 1.  q and k 16-byte aligned, ldq and ldk
- * multiples of 4.                                                                                                                 */
+ * head h in columns [h D, (h + 1) D).  D in {32, 64, 80, 128, 160, 256}, heads, Nq, Nk >= 1 (any Nq, Nk: ragged tiles are masked).
+ * q and k 16-byte aligned, ldq and ldk multiples of 4 (float4 loads; h D is a multiple of 8 for every admitted D); v and out need
+ * 4-byte alignment only and any ldv, ldo; every ld >= heads D.  out must not overlap q, k or v.  Anything else: ST_EINVAL, no launch. */
 int st_tr_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out, int64_t ldo,
                     int32_t heads, int32_t Nq, int32_t Nk, int32_t D, float scale, void* stream);
 /* mmcv DeformConv2d 3x3 / pad 1 / one deformable group, sampling part: x channels-last [H W, ldx], off [H W, ldoff] (channel 2k = dy,
- * 2k + 1 = dx of tap k = 3 ky + kx) -> cols [H W, 9 C] ((ky, kx, c) order, for a plain-matrix st_conv_gemm).                       */
+ * 2k + 1 = dx of tap k = 3 ky + kx) -> cols [H W, 9 C] dense ((ky, kx, c) order, for a plain-matrix st_conv_gemm).  H, W, C >= 1,
+ * ldx >= C, ldoff >= 18.  The sample point is the fp32 sum (oy - 1 + ky) + dy; outside (-1, H) x (-1, W), any magnitude, it gives 0. */
 int st_tr_deform_im2col(const float* x, int64_t ldx, const float* off, int64_t ldoff, float* cols, int32_t H, int32_t W, int32_t C,
                         void* stream);
-/* stride-2 transposed convolution, last step: phases [4, H W, C] (phase 2 py + px) -> out [(2H)(2W), ldo] (+ res, row stride ldr).  */
+/* stride-2 transposed convolution, last step: phases [4, H W, C] dense (phase 2 py + px) -> out [(2H)(2W), ldo] (+ res, row stride ldr,
+ * one fp32 add; res may be null).  H, W, C >= 1, ldo >= C, ldr >= C when res is given.                                             */
 int st_tr_phase_interleave(const float* phases, float* out, int64_t ldo, const float* res, int64_t ldr, int32_t H, int32_t W, int32_t C,
                            void* stream);
-/* out = GELU(erf)(depthwise 3x3 pad 1 conv of x + bias): x / out channels-last [H W, ld], w9c [9, C] (tap-major).                    */
+/* out = GELU(erf)(depthwise 3x3 pad 1 conv of x + bias): x / out channels-last [H W, ld], w9c [9, C] (tap-major) and bias [C] dense.
+ * H, W, C >= 1, ldx >= C, ldo >= C; out must not overlap x.                                                                        */
 int st_tr_dwconv3x3_gelu(const float* x, int64_t ldx, const float* w9c, const float* bias, float* out, int64_t ldo, int32_t H, int32_t W,
                          int32_t C, void* stream);
-/* out = a + b over [rows, C] row-major views.                                                                                      */
+/* out = a + b over [rows, C] row-major views: rows, C >= 1, every ld >= C.  out may be a or b (same view); no other overlap.            */
 int st_tr_add(const float* a, int64_t lda, const float* b, int64_t ldb, float* out, int64_t ldo, int64_t rows, int32_t C, void* stream);
-/* wrapper, steps 1-2: img3 / ctl3 [3, hw] -> out6 [6, hw] = ((trunc-clamp-u8(x) / 255) - 0.5) / 0.5.                              */
+/* wrapper, steps 1-2: img3 / ctl3 [3, hw] -> out6 [6, hw] = ((trunc-clamp-u8(x) / 255) - 0.5) / 0.5, each operation rounded to fp32 as
+ * torch's CPU does (no contraction); all dense, hw >= 1.                                                                           */
 int st_tr_prep(const float* img3, const float* ctl3, float* out6, int64_t hw, void* stream);
-/* steps 4-6: rs6 [6, n] (resized out6), mask [n] (resized mask plane 0) -> x6 [n, 6] (hole fill, 1 - byte mask), ref3 [n, 3],
- * detail3 [3, n].                                                                                                                 */
+/* steps 4-6: rs6 [6, n] (resized out6), mask [n] (resized mask plane 0) -> x6 [n, 6], ref3 [n, 3], detail3 [3, n], all dense, n >= 1.
+ * byte = (int)mask & 255 (mask.byte()); where it is nonzero the image channels hold the fill colour; the three mask channels hold
+ * 1 - byte as TransRef.set_input builds them (1 / 0 for a 0 / 1 mask, -254 for 255).                                              */
 int st_tr_pack(const float* rs6, const float* mask, float* x6, float* ref3, float* detail3, int64_t n, void* stream);
-/* step 7: fake3 [3, n] = out3 [n, 3] * mask + detail3 * (1 - mask), mask [mask_planes (1 or 3), n].                               */
+/* step 7: fake3 [3, n] = out3 [n, 3] * mask + detail3 * (1 - mask), one fp32 rounding per operation; mask [mask_planes, n], mask_planes
+ * 1 (broadcast) or 3, any other count is ST_EINVAL; all dense, n >= 1.                                                             */
 int st_tr_blend(const float* out3, const float* detail3, const float* mask, int32_t mask_planes, float* fake3, int64_t n, void* stream);
-/* step 8: uint8 (x * 127.5 + 127.5).round() clamped to 0..255.                                                                   */
+/* step 8: uint8 (x * 127.5 + 127.5).round() (halves to even) clamped to 0..255; dense, n >= 1.                                        */
 int st_tr_to_u8(const float* x, uint8_t* out, int64_t n, void* stream);
 
 #ifdef __cplusplus

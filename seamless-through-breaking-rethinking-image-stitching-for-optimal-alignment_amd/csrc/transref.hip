@@ -281,13 +281,14 @@ __global__ __launch_bounds__(256) void tr_pack_kernel(const float* __restrict__ 
                                                       float* __restrict__ ref3, float* __restrict__ detail3, int64_t n) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
-    const bool hole = (((int)mask[p]) & 255) != 0;
+    const int byte = ((int)mask[p]) & 255;
+    const bool hole = byte != 0;
     const float fill[3] = {(float)(2.0 * 123.0 / 255.0 - 1.0), (float)(2.0 * 104.0 / 255.0 - 1.0), (float)(2.0 * 117.0 / 255.0 - 1.0)};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float d = hole ? fill[c] : rs6[c * n + p];
         x6[p * 6 + c] = d;
-        x6[p * 6 + 3 + c] = hole ? 0.f : 1.f;
+        x6[p * 6 + 3 + c] = 1.f - (float)byte;
         detail3[c * n + p] = d;
         ref3[p * 3 + c] = rs6[(3 + c) * n + p];
     }
