@@ -439,6 +439,33 @@ int st_jpeg_max_bytes(int32_t H, int32_t W, int32_t channels);
 int st_jpeg_encode_u8(const void* src, int32_t H, int32_t W, int32_t channels, int64_t row_stride, void* out, int64_t out_capacity,
                       int32_t* out_nbytes, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The same encoder with Pillow's options: the file `Image.save(path, quality=q, subsampling=s, optimize=o)` writes on libjpeg-turbo, byte for
+ * byte (csrc/jpeg_opts.hip; contract in README.md, CPU restatement tests/_jpeg_opts_ref.py).  quality 1..100 (libjpeg's scaling, quantisers
+ * clamped to 1..255); (hs, vs) the luma sampling factors, chroma is 1 x 1: (1,1) 4:4:4, (2,1) 4:2:2, (2,2) 4:2:0, one channel: (1,1) only;
+ * optimize 1: libjpeg's two-pass optimize_coding -- the symbols are counted, the four code tables are made on the device and the DHT segments
+ * list only the symbols that occur, so the header's length and the scan's offset are device values; 0: the Annex K tables.  At
+ * {75, 2, 2, 0} (one channel: {75, 1, 1, 0}) the file is st_jpeg_encode_u8's.  Everything else is as for st_jpeg_encode_u8: nothing is read
+ * back, all launches (8, with optimize 10) go to `stream`, the workspace needs no initialisation -- the histograms are cleared by the call -- and
+ * may be reused by the next call on the same stream; a captured call can be replayed on other pixels.
+ * Sizes: codes stay <= 16 bits and at most 12 DC / 162 AC symbols exist, so the header is never longer than 623 bytes (328 for one channel)
+ * and a block never longer than 20 + 63 * 26 bits (csrc/jpeg_opts.hip: sizes); st_jpeg_max_bytes_ex is that bound for the blocks of the
+ * sampling -- 4 * ceil(W / 16) * ceil(H / 8) at 4:2:2, 3 * ceil(W / 8) * ceil(H / 8) at 4:4:4 -- and equals st_jpeg_max_bytes at 4:2:0 and for
+ * one channel.  (st_jpeg_max_bytes itself bounds 4:2:2 and 4:4:4 files of real pictures, which stay far below half of it, but not every input.)
+ * ST_EINVAL before any launch for everything st_jpeg_encode_u8 rejects (with the _ex sizes), and for: a null params; quality outside 1..100;
+ * sampling other than (1,1), (2,1), (2,2); one channel with sampling other than (1,1); optimize other than 0 / 1; a nonzero reserved field.
+ * The size queries return 0 for what the entry rejects.                                                                                     */
+typedef struct st_jpeg_enc_params {
+    int32_t quality;                                /* 1..100                                                                                */
+    int32_t hs, vs;                                 /* luma sampling factors                                                                 */
+    int32_t optimize;                               /* 0: Annex K tables; 1: tables made from the image's symbol counts                      */
+    int32_t reserved[4];                            /* 0                                                                                     */
+} st_jpeg_enc_params;
+int st_abi_jpeg_enc_params_size(void);
+int st_jpeg_workspace_bytes_ex(int32_t H, int32_t W, int32_t channels, const st_jpeg_enc_params* params);
+int st_jpeg_max_bytes_ex(int32_t H, int32_t W, int32_t channels, const st_jpeg_enc_params* params);
+int st_jpeg_encode_u8_ex(const void* src, int32_t H, int32_t W, int32_t channels, int64_t row_stride, const st_jpeg_enc_params* params, void* out,
+                         int64_t out_capacity, int32_t* out_nbytes, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Loader head of evaluate.py and out.py (`PIL.Image.open(path)` on the worker threads): the uint8 [H, W, C] array Pillow returns for a baseline
  * JPEG file on libjpeg-turbo at its defaults (Huffman baseline, integer "islow" IDCT, fancy upsampling, jdcolor.c's fixed-point YCbCr -> RGB),
  * bit for bit, decoded on the device (csrc/jpeg_dec.hip; contract in README.md, CPU restatement tests/_jpeg_dec_ref.py).  The HOST parses the

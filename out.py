@@ -41,6 +41,11 @@ def get_config(argv=None):
     p.add_argument("--skip_if_avg_fusion_exists", action="store_true")
     p.add_argument("--gpu_jpeg", action="store_true",
                    help="encode the result JPEGs on the GPU (the same files, byte for byte) instead of with Pillow on the host")
+    p.add_argument("--jpeg_quality", type=int, default=None, metavar="N",
+                   help="quality (1..100) of the result JPEGs, on either encoder; default: Pillow's 75")
+    p.add_argument("--jpeg_subsampling", type=int, default=None, choices=(0, 1, 2),
+                   help="chroma subsampling of the RGB result JPEGs: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (Pillow's default)")
+    p.add_argument("--jpeg_optimize", action="store_true", help="write the result JPEGs with optimised Huffman tables (Pillow's optimize=True)")
     p.add_argument("--gpu_decode", action="store_true",
                    help="decode the input JPEGs on the GPU (Pillow's pixels, bit for bit); files outside the decoder's contract keep Pillow")
     p.add_argument("--dry-run", dest="dry_run", action="store_true",
@@ -49,7 +54,9 @@ def get_config(argv=None):
     import stitch_amd
     cfg, tps = stitch_amd.load_inference_config(args.inf_cfg, args.model_config_name)
     for k, v in vars(args).items():
-        if k in ("restore_ckpt", "gpu_jpeg", "gpu_decode") and not v:         # (a switch that is off: config.txt stays what it was before the switch existed)
+        if k in ("restore_ckpt", "gpu_jpeg", "gpu_decode", "jpeg_optimize") and not v:         # (a switch that is off: config.txt stays what it was before the switch existed)
+            continue
+        if k in ("jpeg_quality", "jpeg_subsampling") and v is None:
             continue
         cfg[k] = v
     cfg.TPS_PIPELINE_CONFIG = tps
@@ -143,6 +150,14 @@ def to_pillow(t):
     return Image.fromarray(arr)
 
 
+def jpeg_params_of(cfg):
+    """The `save` keywords the flags --jpeg_quality / --jpeg_subsampling / --jpeg_optimize ask for; None when none is given."""
+    kw = {k: getattr(cfg, "jpeg_" + k) for k in ("quality", "subsampling") if getattr(cfg, "jpeg_" + k, None) is not None}
+    if getattr(cfg, "jpeg_optimize", False):
+        kw["optimize"] = True
+    return kw or None
+
+
 class _Saver:
     """JPEG writes of out.py:260-312.  The uint8 conversion runs on the GPU (clip + truncation, as `to_pillow_fn` does on the
     host), the bytes are copied to the host in the caller's thread, the JPEG encode + file write go to ``pool`` when one is given
@@ -150,15 +165,25 @@ class _Saver:
 
     ``gpu_jpeg``: the same uint8 canvas is encoded on the device instead (`ops.jpeg_encode`, the file Pillow would write, byte for
     byte) on the caller's stream; nothing is read back until ``flush`` (the end of a pair), which reads the byte counts of all
-    pending files together, copies exactly those bytes to the host in one transfer and hands the plain file writes to ``pool``."""
+    pending files together, copies exactly those bytes to the host in one transfer and hands the plain file writes to ``pool``.
 
-    def __init__(self, pool=None, gpu_jpeg=False):
+    ``jpeg_params``: Pillow's `save` keywords ``quality``, ``subsampling``, ``optimize`` for every file, on both paths (`jpeg_params_of`);
+    ``subsampling`` is never passed for an L array."""
+
+    def __init__(self, pool=None, gpu_jpeg=False, jpeg_params=None):
         self.pool, self.futures, self.gpu_jpeg = pool, [], gpu_jpeg
         self.pending = []
+        self.jpeg_params = dict(jpeg_params or {})
+        unknown = set(self.jpeg_params) - {"quality", "subsampling", "optimize"}
+        if unknown:
+            raise ValueError(f"jpeg_params: unknown keys {sorted(unknown)}")
+
+    def _keywords(self, ndim):
+        return {k: v for k, v in self.jpeg_params.items() if not (k == "subsampling" and ndim == 2)}
 
     def _write(self, arr, path):
         from PIL import Image
-        Image.fromarray(arr).save(path)
+        Image.fromarray(arr).save(path, **self._keywords(arr.ndim))
 
     @staticmethod
     def _write_bytes(data, path):
@@ -181,7 +206,7 @@ class _Saver:
             import stitch_amd
             if not torch.is_tensor(arr):
                 arr = torch.from_numpy(arr)
-            self.pending.append(stitch_amd.ops.jpeg_encode(arr.cuda()) + (path,))
+            self.pending.append(stitch_amd.ops.jpeg_encode(arr.cuda(), **self._keywords(arr.dim())) + (path,))
             return
         if torch.is_tensor(arr):
             arr = arr.cpu().numpy()
@@ -224,7 +249,7 @@ def load_inpainter(name):
 
 
 def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_model=None, inpainter=None, forward=None, saver=None,
-                       gpu_jpeg=False, gpu_decode=False):
+                       gpu_jpeg=False, gpu_decode=False, jpeg_params=None):
     """out.py:158-312: forward (`test_out`), TPS post-pipeline with the configured `mix_fn`, saves, composition.  The inpainter
     is the caller's, else the pass-through stand-in (`load_inpainter`: `transref_inpainter` needs its checkpoint, the diffusion one is
     out of scope): with the stand-in, in `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the
@@ -234,10 +259,11 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     ``forward``: a callable returning the `test_out` dict of this pair whose network part is already in flight (``main``
     launches pair i + 1's hipGraph before it finishes pair i); default = load + ``warp_model(..., type="test_out")`` here.
     ``saver``: a ``_Saver`` (JPEG encodes on a thread pool); default = write synchronously, with ``gpu_jpeg`` through the device encoder.
-    ``gpu_decode``: the two input files are decoded on the device (`readSingleData`, `ops.jpeg_decode`) when this function loads them."""
+    ``gpu_decode``: the two input files are decoded on the device (`readSingleData`, `ops.jpeg_decode`) when this function loads them.
+    ``jpeg_params``: the `save` keywords of the default saver (`_Saver`); a caller's ``saver`` carries its own."""
     own_saver = saver is None
     statuses = []
-    saver = saver or _Saver(gpu_jpeg=gpu_jpeg)
+    saver = saver or _Saver(gpu_jpeg=gpu_jpeg, jpeg_params=jpeg_params)
     path = data_dict["DATA_PATH"]
     name = os.path.basename(os.path.normpath(path))
     result_path = os.path.join(save_root_path, name) + "/"
@@ -296,7 +322,8 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     return out, result_path
 
 
-def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=None, on_done=None, depth=2, gpu_jpeg=False, gpu_decode=False):
+def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=None, on_done=None, depth=2, gpu_jpeg=False, gpu_decode=False,
+              jpeg_params=None):
     """The inference loop of out.py:351-357 as a software pipeline, `depth` pairs in flight.  While pair i is finished on the host
     (canvas bounds read back, canvas kernels, TPS post-pipeline with its control-point round trips, composition, device->host copies
     of the images), the network parts of pairs i + 1 .. i + depth - 1 -- both nets at 512x512, ~1 000 launches each, replayed from a
@@ -309,7 +336,8 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
     ``gpu_jpeg``: the ten files of a pair are encoded on the device on the pair's stream (`_Saver(gpu_jpeg=True)`) and read back, counts
     first, at the end of the pair; the pool then only writes files.
     ``gpu_decode``: the decode threads only read and probe the files (`readSingleData`), the pixels are made on the pair's stream
-    (`ops.jpeg_decode`) in front of its graph launch; the status words are checked when the pair is finished."""
+    (`ops.jpeg_decode`) in front of its graph launch; the status words are checked when the pair is finished.
+    ``jpeg_params``: Pillow's `save` keywords for the result files (`_Saver`), on either encoder."""
     from concurrent.futures import ThreadPoolExecutor
     if not todo:
         return []
@@ -338,7 +366,7 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
                 return graphs[k], graphs[k].launch(image1, image2), streams[k], statuses
 
         inflight = [launch(j) for j in range(min(depth - 1, len(todo)))]
-        saver = _Saver(enc_pool, gpu_jpeg=gpu_jpeg)
+        saver = _Saver(enc_pool, gpu_jpeg=gpu_jpeg, jpeg_params=jpeg_params)
         for j, dd in enumerate(todo):
             if j + depth - 1 < len(todo):
                 inflight.append(launch(j + depth - 1))
@@ -411,7 +439,7 @@ def main(argv=None):
             continue
         todo.append(dd)
     run_pairs(cfg, todo, save_root, model, composition_model, inpainter, gpu_jpeg=bool(getattr(cfg, "gpu_jpeg", False)),
-              gpu_decode=bool(getattr(cfg, "gpu_decode", False)))
+              gpu_decode=bool(getattr(cfg, "gpu_decode", False)), jpeg_params=jpeg_params_of(cfg))
     if world > 1:
         import torch.distributed as tdist
         tdist.barrier()

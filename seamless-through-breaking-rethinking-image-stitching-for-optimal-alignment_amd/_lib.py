@@ -68,6 +68,11 @@ class JpegDecParams(C.Structure):
                 + [(n, C.c_int32 * 2) for n in ("q_off", "dc_off", "ac_off")] + [("scan_off", C.c_int32), ("scan_len", C.c_int32)])
 
 
+class JpegEncParams(C.Structure):
+    """Mirror of ``st_jpeg_enc_params``."""
+    _fields_ = [(n, C.c_int32) for n in ("quality", "hs", "vs", "optimize")] + [("reserved", C.c_int32 * 4)]
+
+
 def declared_functions(header=HEADER):
     """{name: [ctypes argtypes]} for every ``int st_*(...)`` declaration in the header."""
     src = open(header).read()

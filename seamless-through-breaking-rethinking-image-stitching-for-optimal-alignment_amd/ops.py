@@ -6,7 +6,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import ChainDesc, GemmDesc, JpegDecParams, MlpDesc, check, lib
+from ._lib import ChainDesc, GemmDesc, JpegDecParams, JpegEncParams, MlpDesc, check, lib
 from .jpeg_probe import JpegInfo, probe as _jpeg_probe
 from ._lib import StitchError as StitchErrorBase
 
@@ -17,6 +17,7 @@ assert lib.st_abi_gemm_desc_size() == C.sizeof(GemmDesc), "st_gemm_desc ABI mism
 assert lib.st_abi_chain_desc_size() == C.sizeof(ChainDesc), "st_chain_desc ABI mismatch between header and binding"
 assert lib.st_abi_mlp_desc_size() == C.sizeof(MlpDesc), "st_mlp_desc ABI mismatch between header and binding"
 assert lib.st_abi_jpeg_dec_params_size() == C.sizeof(JpegDecParams), "st_jpeg_dec_params ABI mismatch between header and binding"
+assert lib.st_abi_jpeg_enc_params_size() == C.sizeof(JpegEncParams), "st_jpeg_enc_params ABI mismatch between header and binding"
 
 
 def _stream():
@@ -757,32 +758,63 @@ def load_rgb8(src_u8_hwc, out=None):
     return out
 
 
-def jpeg_encode(u8, workspace=None):
+_JPEG_SAMPLING = {None: (2, 2), 2: (2, 2), 1: (2, 1), 0: (1, 1)}        # Pillow's `subsampling` -> luma sampling factors
+
+
+def _jpeg_enc_params(channels, quality, subsampling, optimize):
+    """The `JpegEncParams` of Pillow's `save` keywords, or None when every keyword is at its default (the encoder of Pillow's defaults)."""
+    if quality is None and subsampling is None and not optimize:
+        return None
+    if subsampling not in _JPEG_SAMPLING or isinstance(subsampling, bool):
+        raise ValueError(f"subsampling {subsampling!r}: None, 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0) expected")
+    if channels == 1 and subsampling is not None:
+        raise ValueError("subsampling applies to RGB arrays only (an L file has one component)")
+    q = 75 if quality is None else quality
+    if isinstance(q, bool) or not isinstance(q, int) or not 1 <= q <= 100:
+        raise ValueError(f"quality {quality!r}: an integer 1..100 expected")
+    hs, vs = _JPEG_SAMPLING[subsampling] if channels == 3 else (1, 1)
+    return JpegEncParams(q, hs, vs, 1 if optimize else 0)
+
+
+def jpeg_encode(u8, workspace=None, quality=None, subsampling=None, optimize=False):
     """out.py:260-312 `Image.fromarray(arr).save(path)` on the GPU: uint8 [H,W,3] (RGB) or [H,W] (L) -> (buf, nbytes), the JPEG file Pillow
-    writes at its defaults, byte for byte (csrc/jpeg.hip).  buf: uint8 device tensor of the worst-case size, nbytes: device int32 [1], the
-    file is buf[:nbytes].  Rows may be strided (a column slice of a wider canvas).  No host synchronisation; current stream.
-    `workspace`: a uint8 device tensor of at least `jpeg_workspace_bytes` to reuse (stream-ordered: same stream as its last use)."""
+    writes, byte for byte.  buf: uint8 device tensor of the worst-case size, nbytes: device int32 [1], the file is buf[:nbytes].  Rows may be
+    strided (a column slice of a wider canvas).  No host synchronisation; current stream.
+    `quality` (1..100), `subsampling` (RGB only: 0 4:4:4, 1 4:2:2, 2 4:2:0) and `optimize` are Pillow's `save` keywords (csrc/jpeg_opts.hip);
+    with all three at their defaults this is the encoder of Pillow's defaults -- quality 75, 4:2:0, the Annex K tables (csrc/jpeg.hip).
+    `workspace`: a uint8 device tensor of at least `jpeg_workspace_bytes` (same keywords) to reuse (stream-ordered: same stream as its last use)."""
     if u8.dtype != torch.uint8 or not (u8.dim() == 2 or (u8.dim() == 3 and u8.shape[2] == 3)):
         raise ValueError(f"uint8 [H,W,3] or [H,W] expected, got {u8.dtype} {tuple(u8.shape)}")
     H, W = u8.shape[:2]
     ch = 3 if u8.dim() == 3 else 1
+    prm = _jpeg_enc_params(ch, quality, subsampling, optimize)
     if (W > 1 and u8.stride(1) != ch) or (ch == 3 and u8.stride(2) != 1) or (H > 1 and u8.stride(0) < W * ch):
         u8 = u8.contiguous()
     row_stride = u8.stride(0) if H > 1 else W * ch
-    cap, need = lib.st_jpeg_max_bytes(H, W, ch), lib.st_jpeg_workspace_bytes(H, W, ch)
+    if prm is None:
+        cap, need = lib.st_jpeg_max_bytes(H, W, ch), lib.st_jpeg_workspace_bytes(H, W, ch)
+    else:
+        cap, need = lib.st_jpeg_max_bytes_ex(H, W, ch, C.byref(prm)), lib.st_jpeg_workspace_bytes_ex(H, W, ch, C.byref(prm))
     if cap == 0:
         raise StitchErrorBase(f"st_jpeg_encode_u8: unsupported shape {tuple(u8.shape)} (sides 1..65535, H * W <= 2^24)")
     if workspace is None:
         workspace = torch.empty((need,), device=u8.device, dtype=torch.uint8)
     buf = torch.empty((cap,), device=u8.device, dtype=torch.uint8)
     nbytes = torch.empty((1,), device=u8.device, dtype=torch.int32)
-    check(lib.st_jpeg_encode_u8(_p(u8), H, W, ch, row_stride, _p(buf), cap, _p(nbytes), _pc(workspace), workspace.numel() * workspace.element_size(),
-                                _stream()), "st_jpeg_encode_u8")
+    if prm is None:
+        check(lib.st_jpeg_encode_u8(_p(u8), H, W, ch, row_stride, _p(buf), cap, _p(nbytes), _pc(workspace), workspace.numel() * workspace.element_size(),
+                                    _stream()), "st_jpeg_encode_u8")
+    else:
+        check(lib.st_jpeg_encode_u8_ex(_p(u8), H, W, ch, row_stride, C.byref(prm), _p(buf), cap, _p(nbytes), _pc(workspace),
+                                       workspace.numel() * workspace.element_size(), _stream()), "st_jpeg_encode_u8_ex")
     return buf, nbytes
 
 
-def jpeg_workspace_bytes(H, W, channels):
-    return lib.st_jpeg_workspace_bytes(H, W, channels)
+def jpeg_workspace_bytes(H, W, channels, quality=None, subsampling=None, optimize=False):
+    prm = _jpeg_enc_params(channels, quality, subsampling, optimize)
+    if prm is None:
+        return lib.st_jpeg_workspace_bytes(H, W, channels)
+    return lib.st_jpeg_workspace_bytes_ex(H, W, channels, C.byref(prm))
 
 
 def jpeg_bytes(buf, nbytes):

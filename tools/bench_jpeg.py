@@ -8,6 +8,12 @@
 * the loop: `run_pairs` on 48 synthetic 512x512 pairs (10 files per pair) with `gpu_jpeg` off and on, at depth 2 and 3, the variants
   alternating, median of the rounds; wall pairs/s and host CPU seconds per pair (`time.process_time`: all threads of the process).
   `--parent-out` adds the loop of another out.py (the commit before the switch existed) to the same alternation.
+
+    python tools/bench_jpeg.py --options [--out profiles/jpeg_opts_bench.json]
+
+* the option rows (csrc/jpeg_opts.hip), in one run: per image Pillow on one thread with the same keywords, the encoder of the defaults
+  (`st_jpeg_encode_u8`), the option entry at the defaults (quality 75, 4:2:0, Annex K tables: the same bytes) and at quality 95, 4:4:4,
+  optimised tables; per kernel one traced child making 200 encodes of the 548x588 canvas at (95, 4:4:4, optimised).
 """
 import argparse
 import contextlib
@@ -38,54 +44,62 @@ def images():
             "mask_548x588": ((ref._smooth(548, 588, 0, 7) > 127) * 255).astype(np.uint8)}
 
 
-def pillow_ms(u8, n=20):
+def pillow_ms(u8, n=20, **kw):
     from PIL import Image
     ts = []
     for _ in range(n):
         buf = io.BytesIO()
         t0 = time.perf_counter()
-        Image.fromarray(u8).save(buf, format="JPEG")
+        Image.fromarray(u8).save(buf, format="JPEG", **kw)
         ts.append((time.perf_counter() - t0) * 1e3)
     return float(np.median(ts)), len(buf.getvalue())
 
 
-def encode_times(u8, n=50):
+def encode_times(u8, n=50, **kw):
     import torch
     from stitch_amd import ops
     x = torch.from_numpy(u8).cuda()
     for _ in range(5):
-        r = ops.jpeg_encode(x)
+        r = ops.jpeg_encode(x, **kw)
     torch.cuda.synchronize()
     single = []
     for _ in range(n):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        r = ops.jpeg_encode(x)
+        r = ops.jpeg_encode(x, **kw)
         e1.record()
         e1.synchronize()
         single.append(e0.elapsed_time(e1))
-    ws = torch.empty((ops.jpeg_workspace_bytes(u8.shape[0], u8.shape[1], 3 if u8.ndim == 3 else 1),), dtype=torch.uint8, device="cuda")
+    ws = torch.empty((ops.jpeg_workspace_bytes(u8.shape[0], u8.shape[1], 3 if u8.ndim == 3 else 1, **kw),), dtype=torch.uint8, device="cuda")
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(n):
-        r = ops.jpeg_encode(x, workspace=ws)
+        r = ops.jpeg_encode(x, workspace=ws, **kw)
     e1.record()
     e1.synchronize()
     return float(np.median(single)), e0.elapsed_time(e1) / n, len(ops.jpeg_bytes(*r))
 
 
-def profile_child(n):
-    """per-kernel stand-alone durations (us per encode) from a traced child making n encodes of the 548x588 canvas"""
+OPTION_ROWS = {"defaults_old_entry": {}, "defaults_new_entry": dict(quality=75, subsampling=2), "q95_444_optimised": dict(quality=95, subsampling=0, optimize=True)}
+
+
+def option_keywords(kw, u8):
+    return {k: v for k, v in kw.items() if not (k == "subsampling" and u8.ndim == 2)}        # an L file has one component
+
+
+def profile_child(n, options=False):
+    """per-kernel stand-alone durations (us per encode) from a traced child making n encodes of the 548x588 canvas (`options`: at
+    quality 95, 4:4:4, optimised tables)"""
     d = tempfile.mkdtemp(prefix="jpeg_prof_")
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "jpeg", "--output-format", "csv", "--",
-           sys.executable, os.path.abspath(__file__), "--inner", str(n)]
+           sys.executable, os.path.abspath(__file__), "--inner", str(n)] + (["--options"] if options else [])
     subprocess.run(cmd, check=True, timeout=600, stdout=subprocess.DEVNULL)
     path = (glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True) or [None])[0]
     if path is None:
         raise RuntimeError(f"rocprofv3 wrote no kernel_stats.csv under {d}")
     rows = []
     for r in csv.DictReader(open(path)):
-        if "jpeg_" in r["Name"]:
+        if "jpeg_" in r["Name"] or "jpego_" in r["Name"]:
             name = re.sub(r"\(.*", "", re.sub(r"^void ", "", r["Name"]).replace("(anonymous namespace)::", ""))
             rows.append(dict(name=name, calls_per_encode=int(r["Calls"]) / n, us_per_encode=float(r["TotalDurationNs"]) / n / 1e3))
     return sorted(rows, key=lambda r: -r["us_per_encode"])
@@ -165,7 +179,8 @@ def loop_bench(pairs, rounds, parent_path):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_bench.json"))
+    ap.add_argument("--out", default="")
+    ap.add_argument("--options", action="store_true", help="the option rows of csrc/jpeg_opts.hip -> profiles/jpeg_opts_bench.json")
     ap.add_argument("--parent-out", default="")
     ap.add_argument("--pairs", type=int, default=48)
     ap.add_argument("--rounds", type=int, default=5)
@@ -173,14 +188,38 @@ def main():
     ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--inner", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "jpeg_opts_bench.json" if a.options else "jpeg_bench.json")
     imgs = images()
     if a.inner:                                            # the traced child
         import torch
         from stitch_amd import ops
         x = torch.from_numpy(imgs["rgb_548x588"]).cuda()
         for _ in range(a.inner):
-            ops.jpeg_encode(x)
+            ops.jpeg_encode(x, **(OPTION_ROWS["q95_444_optimised"] if a.options else {}))
         torch.cuda.synchronize()
+        return
+    if a.options:
+        res = {"what": "GPU JPEG encoder options (csrc/jpeg_opts.hip) vs Pillow (one thread, same keywords) and vs the encoder of the defaults "
+                       "(csrc/jpeg.hip), same run, one MI355X"}
+        rows = profile_child(a.launches, options=True)
+        res["kernels_rgb_548x588_q95_444_optimised"] = dict(source=f"rocprofv3 --kernel-trace --stats, {a.launches} encodes (stand-alone kernel durations)", rows=rows,
+                                                            us_per_encode_total=sum(r["us_per_encode"] for r in rows),
+                                                            table_kernel_us_per_encode=sum(r["us_per_encode"] for r in rows if "table" in r["name"]))
+        import torch
+        assert torch.cuda.is_available(), "needs the GPU"
+        per = {}
+        for name, u8 in imgs.items():
+            per[name] = {}
+            for row, kw in OPTION_ROWS.items():
+                kw = option_keywords(kw, u8)
+                p_ms, p_bytes = pillow_ms(u8, **kw)
+                single, b2b, g_bytes = encode_times(u8, **kw)
+                assert g_bytes == p_bytes
+                per[name][row] = dict(keywords=kw, pillow_ms_one_thread=p_ms, gpu_ms_single_call_hip_events=single, gpu_ms_back_to_back=b2b, file_bytes=g_bytes)
+        res["per_image"] = per
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
         return
     res = {"what": "GPU baseline JPEG encoder (csrc/jpeg.hip) vs Pillow (one thread) on the same arrays, one MI355X; the out.py loop with gpu_jpeg off / on"}
     res["kernels_rgb_548x588"] = dict(source=f"rocprofv3 --kernel-trace --stats, {a.launches} encodes (stand-alone kernel durations)",
