@@ -433,14 +433,15 @@ int st_load_rgb8(const void* src_u8_hwc, float* dst_chw, int32_t B, int32_t H, i
  * st_jpeg_workspace_bytes, an out_capacity below st_jpeg_max_bytes -- the worst case of the code tables: header (623 bytes RGB, 328 L) +
  * 2 * ceil(nblocks * (20 + 63 * 26) / 8) + 2, i.e. <= 20 bits of DC and <= 16 + 10 bits per AC coefficient in every block, doubled for byte
  * stuffing, + EOI; nblocks = 6 * ceil(W / 16) * ceil(H / 16) (RGB) or ceil(W / 8) * ceil(H / 8) (L).  The workspace needs no
- * initialisation and may be reused by the next call on the same stream.  The two size queries return 0 for a rejected shape.          */
+ * initialisation and may be reused by the next call on the same stream.  The two size queries return 0 for a rejected shape.  The three
+ * functions are the _ex ones below at {75, 2, 2, 0} (one channel: {75, 1, 1, 0}): one encoder, same sizes, same launches, same bytes.   */
 int st_jpeg_workspace_bytes(int32_t H, int32_t W, int32_t channels);
 int st_jpeg_max_bytes(int32_t H, int32_t W, int32_t channels);
 int st_jpeg_encode_u8(const void* src, int32_t H, int32_t W, int32_t channels, int64_t row_stride, void* out, int64_t out_capacity,
                       int32_t* out_nbytes, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The same encoder with Pillow's options: the file `Image.save(path, quality=q, subsampling=s, optimize=o)` writes on libjpeg-turbo, byte for
- * byte (csrc/jpeg_opts.hip; contract in README.md, CPU restatement tests/_jpeg_opts_ref.py).  quality 1..100 (libjpeg's scaling, quantisers
+ * byte (csrc/jpeg.hip; contract in README.md, CPU restatement tests/_jpeg_opts_ref.py).  quality 1..100 (libjpeg's scaling, quantisers
  * clamped to 1..255); (hs, vs) the luma sampling factors, chroma is 1 x 1: (1,1) 4:4:4, (2,1) 4:2:2, (2,2) 4:2:0, one channel: (1,1) only;
  * optimize 1: libjpeg's two-pass optimize_coding -- the symbols are counted, the four code tables are made on the device and the DHT segments
  * list only the symbols that occur, so the header's length and the scan's offset are device values; 0: the Annex K tables.  At
@@ -448,9 +449,12 @@ int st_jpeg_encode_u8(const void* src, int32_t H, int32_t W, int32_t channels, i
  * back, all launches (8, with optimize 10) go to `stream`, the workspace needs no initialisation -- the histograms are cleared by the call -- and
  * may be reused by the next call on the same stream; a captured call can be replayed on other pixels.
  * Sizes: codes stay <= 16 bits and at most 12 DC / 162 AC symbols exist, so the header is never longer than 623 bytes (328 for one channel)
- * and a block never longer than 20 + 63 * 26 bits (csrc/jpeg_opts.hip: sizes); st_jpeg_max_bytes_ex is that bound for the blocks of the
+ * and a block never longer than 20 + 63 * 26 bits (csrc/jpeg.hip: sizes); st_jpeg_max_bytes_ex is that bound for the blocks of the
  * sampling -- 4 * ceil(W / 16) * ceil(H / 8) at 4:2:2, 3 * ceil(W / 8) * ceil(H / 8) at 4:4:4 -- and equals st_jpeg_max_bytes at 4:2:0 and for
  * one channel.  (st_jpeg_max_bytes itself bounds 4:2:2 and 4:4:4 files of real pictures, which stay far below half of it, but not every input.)
+ * st_jpeg_workspace_bytes_ex with optimize 0 is the layout of st_jpeg_workspace_bytes -- no table area, nothing of it is read; optimize 1 adds
+ * the area of the four code tables, DHT payloads and histograms (9 312 bytes).  (Before the two encoders became one, optimize 0 reserved that
+ * area too: the query now returns 9 312 bytes less there.)
  * ST_EINVAL before any launch for everything st_jpeg_encode_u8 rejects (with the _ex sizes), and for: a null params; quality outside 1..100;
  * sampling other than (1,1), (2,1), (2,2); one channel with sampling other than (1,1); optimize other than 0 / 1; a nonzero reserved field.
  * The size queries return 0 for what the entry rejects.                                                                                     */

@@ -1,125 +1,140 @@
 // Baseline JPEG encoder for the result files of out.py (reference out.py:260-312 `to_pillow_fn(...).save(path)`): the file Pillow's
-// `Image.save` writes at its defaults on libjpeg-turbo -- quality 75, 4:2:0 (RGB) or one component (L), Annex K Huffman tables, JFIF
-// header, integer "islow" DCT -- byte for byte (contract: README.md; CPU restatement: tests/_jpeg_ref.py).  Integer arithmetic only.
+// `Image.save(path, quality=q, subsampling=s, optimize=o)` writes on libjpeg-turbo -- JFIF header, integer "islow" DCT, 4:2:0 / 4:2:2 /
+// 4:4:4 (RGB) or one component (L), the Annex K Huffman tables or libjpeg's optimised ones -- byte for byte (contract: README.md; CPU
+// restatements: tests/_jpeg_ref.py for Pillow's defaults, tests/_jpeg_opts_ref.py for the keywords).  One kernel set serves both C entries:
+// st_jpeg_encode_u8 is st_jpeg_encode_u8_ex at {75, 4:2:0 or one component, plain}.  The quantisers are kernel arguments, the sampling a
+// template parameter and the code tables memory: the Annex K ones (g_std), or the ones the table kernel has just made from the image's own
+// symbol counts.  Integer arithmetic only.
 //
-//   jpeg_blocks_kernel  one wave per MCU (RGB: 16x16 px -> Y00 Y01 Y10 Y11 Cb Cr) or per 4 blocks of a block row (L): colour conversion,
-//                       h2v2 downsampling, the edge / dummy-block rules, both DCT passes through LDS, quantisation -> int16 [nblocks, 64]
-//                       zigzag coefficients in scan order
-//   jpeg_bits_kernel    per block: DC difference (the predecessor is a closed-form index) and the block's code length in bits
+//   jpeg_blocks_kernel  one wave per MCU (4:2:0 16x16: Y00 Y01 Y10 Y11 Cb Cr; 4:2:2 16x8: Y0 Y1 Cb Cr; 4:4:4 8x8: Y Cb Cr) or per 4 blocks
+//                       of a block row (L): colour conversion, h2v2 / h2v1 downsampling, the edge and dummy-block rules, both DCT passes
+//                       through LDS, quantisation -> int16 [nblocks, 64] zigzag coefficients in scan order; (optimize) workgroup 0 clears the
+//                       histograms
+//   jpeg_hist_kernel    (optimize) the symbols the scan will emit, ZRL and EOB included, counted in LDS per workgroup, merged into
+//                       uint32 [4][257]: DC0, AC0, DC1, AC1
+//   jpeg_table_kernel   (optimize) one wave per table: jpeg_gen_optimal_table (csrc/jpeg_huff_core.h) -> code | length per symbol and the
+//                       DHT payload with its length
+//   jpeg_bits_kernel    per block: DC difference (the predecessor is a closed-form index) and the block's code length in bits, with the
+//                       tables in LDS
 //   jpeg_scan_kernel    exclusive prefix sum (one workgroup walking 4096-entry tiles) -> bit offset of every block, total
 //   jpeg_zero_kernel    clears the words of the unstuffed stream that this image uses (part of the call: a reused workspace is fine)
 //   jpeg_pack_kernel    per block: its codes at its bit offset (atomicOr on the two boundary words, plain stores between them); the
 //                       last block appends the 1-bit padding
 //   jpeg_count_kernel   0xFF bytes per 2048-byte chunk of the stream, scanned by jpeg_scan_kernel again
-//   jpeg_stuff_kernel   scatters the bytes with their 0x00 followers behind the header; workgroup 0 writes the header (size bytes
-//                       patched), EOI and the byte count
+//   jpeg_stuff_kernel   scatters the bytes with their 0x00 followers behind the header; the last workgroup assembles the header -- DQT from
+//                       the arguments, SOF0, the DHTs of fixed or device-computed length -- and writes EOI and the byte count
 #include "common.h"
 #include "jpeg_tables.h"
+#include "jpeg_huff_core.h"
+#include "jpeg_scan.h"
+#include "../../include/stitch_gfx950.h"
 
 namespace {
 
-// ---- tables (ITU-T T.81 Annex K: csrc/jpeg_tables.h), everything derived from them at compile time ----------------------------------
-constexpr int kQuality = 75;
-
-constexpr int kHdrMax = 624;
-struct JTables {
-    uint16_t q8[2][64];        // natural order: the divisor of the scaled-by-8 DCT output, quantiser << 3
-    uint8_t izz[64];           // natural index -> zigzag position
-    uint32_t dc[2][12];        // code | length << 16, index = category
-    uint32_t ac[2][256];       // index = run << 4 | size
-    uint8_t hdr[2][kHdrMax];   // SOI .. SOS; [0]: one component (L), [1]: RGB
-    int32_t hdr_len[2];
-    int32_t size_off[2];       // where SOF0's height (2 bytes) and width (2 bytes) go
+constexpr int kDhtMax = 16 + 256;
+struct JTabs {                         // the four tables in DHT order: DC0, AC0, DC1, AC1
+    uint32_t code[4][256];             // by symbol (DC: the category): code | length << 16
+    uint8_t dht[4][kDhtMax];           // the DHT payload behind the Tc / Th byte: 16 counts, then the symbols
+    int32_t dht_len[4];
 };
 
-constexpr int quantiser(int table, int natural) {
-    const int scale = kQuality < 50 ? 5000 / kQuality : 200 - 2 * kQuality;
-    const int q = (kQBase[table][natural] * scale + 50) / 100;
-    return q < 1 ? 1 : (q > 255 ? 255 : q);
-}
-
-constexpr void huff_codes(uint32_t* tab, const int* bits, const int* vals, bool identity_vals) {
-    uint32_t code = 0;
-    int k = 0;
-    for (int len = 1; len <= 16; ++len) {
-        for (int i = 0; i < bits[len - 1]; ++i, ++k) tab[identity_vals ? k : vals[k]] = code++ | ((uint32_t)len << 16);
-        code <<= 1;
-    }
-}
-
-constexpr JTables make_tables() {
-    JTables t{};
-    for (int c = 0; c < 2; ++c)
-        for (int i = 0; i < 64; ++i) t.q8[c][i] = (uint16_t)(quantiser(c, i) << 3);
-    for (int i = 0; i < 64; ++i) t.izz[kZigzag[i]] = (uint8_t)i;
+constexpr JTabs make_std() {           // ITU-T T.81 Annex K (csrc/jpeg_tables.h), canonical codes (Annex C)
+    JTabs t{};
     for (int c = 0; c < 2; ++c) {
-        huff_codes(t.dc[c], kDcBits[c], nullptr, true);
-        huff_codes(t.ac[c], kAcBits[c], kAcVals[c], false);
-    }
-    for (int v = 0; v < 2; ++v) {
-        const int ncomp = v ? 3 : 1, ntab = v ? 2 : 1;
-        uint8_t* h = t.hdr[v];
-        int n = 0;
-        const uint8_t app0[20] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-        for (int i = 0; i < 20; ++i) h[n++] = app0[i];
-        for (int c = 0; c < ntab; ++c) {
-            h[n++] = 0xFF, h[n++] = 0xDB, h[n++] = 0, h[n++] = 67, h[n++] = (uint8_t)c;
-            for (int i = 0; i < 64; ++i) h[n++] = (uint8_t)quantiser(c, kZigzag[i]);
+        for (int ac = 0; ac < 2; ++ac) {
+            const int* bits = ac ? kAcBits[c] : kDcBits[c];
+            const int nsym = ac ? 162 : 12, i = 2 * c + ac;
+            uint32_t code = 0;
+            int k = 0;
+            for (int len = 1; len <= 16; ++len) {
+                t.dht[i][len - 1] = (uint8_t)bits[len - 1];
+                for (int j = 0; j < bits[len - 1]; ++j, ++k) t.code[i][ac ? kAcVals[c][k] : k] = code++ | ((uint32_t)len << 16);
+                code <<= 1;
+            }
+            for (int j = 0; j < nsym; ++j) t.dht[i][16 + j] = (uint8_t)(ac ? kAcVals[c][j] : j);
+            t.dht_len[i] = 16 + nsym;
         }
-        h[n++] = 0xFF, h[n++] = 0xC0, h[n++] = 0, h[n++] = (uint8_t)(8 + 3 * ncomp), h[n++] = 8;
-        t.size_off[v] = n;
-        n += 4;
-        h[n++] = (uint8_t)ncomp;
-        for (int c = 0; c < ncomp; ++c) h[n++] = (uint8_t)(c + 1), h[n++] = (v && c == 0) ? 0x22 : 0x11, h[n++] = c ? 1 : 0;
-        for (int c = 0; c < ntab; ++c) {
-            h[n++] = 0xFF, h[n++] = 0xC4, h[n++] = 0, h[n++] = 31, h[n++] = (uint8_t)c;
-            for (int i = 0; i < 16; ++i) h[n++] = (uint8_t)kDcBits[c][i];
-            for (int i = 0; i < 12; ++i) h[n++] = (uint8_t)i;
-            h[n++] = 0xFF, h[n++] = 0xC4, h[n++] = 0, h[n++] = 181, h[n++] = (uint8_t)(0x10 | c);
-            for (int i = 0; i < 16; ++i) h[n++] = (uint8_t)kAcBits[c][i];
-            for (int i = 0; i < 162; ++i) h[n++] = (uint8_t)kAcVals[c][i];
-        }
-        h[n++] = 0xFF, h[n++] = 0xDA, h[n++] = 0, h[n++] = (uint8_t)(6 + 2 * ncomp), h[n++] = (uint8_t)ncomp;
-        for (int c = 0; c < ncomp; ++c) h[n++] = (uint8_t)(c + 1), h[n++] = c ? 0x11 : 0x00;
-        h[n++] = 0, h[n++] = 63, h[n++] = 0;
-        t.hdr_len[v] = n;
     }
     return t;
 }
 
-constexpr JTables kTablesHost = make_tables();
-static_assert(kTablesHost.hdr_len[0] == 328 && kTablesHost.hdr_len[1] == 623, "header sizes of the contract");
-__device__ const JTables g_jt = make_tables();
+struct JIzz {
+    uint8_t v[64];                     // natural index -> zigzag position
+};
+constexpr JIzz make_izz() {
+    JIzz z{};
+    for (int i = 0; i < 64; ++i) z.v[kZigzag[i]] = (uint8_t)i;
+    return z;
+}
+
+// SOI + APP0, DQT x n, SOF0, DHT x 2n, SOS: what write_header writes.  (All four lengths are read, needed or not: four loads in flight, where a
+// loop over the tables in use would wait for each -- in every workgroup of the stuff kernel.)
+constexpr uint32_t header_bytes(int ncomp, const JTabs& tabs) {
+    const uint32_t luma = 69u + 2 * 5u + (uint32_t)tabs.dht_len[0] + (uint32_t)tabs.dht_len[1];
+    const uint32_t chroma = 69u + 2 * 5u + (uint32_t)tabs.dht_len[2] + (uint32_t)tabs.dht_len[3];
+    return 20u + (10u + 3 * ncomp) + (8u + 2 * ncomp) + luma + (ncomp == 3 ? chroma : 0u);
+}
+
+constexpr JTabs kStdHost = make_std();
+// no table has more symbols than the Annex K ones, so no header is longer than theirs
+constexpr uint32_t kStdHeaderBytes[2] = {header_bytes(1, kStdHost), header_bytes(3, kStdHost)};
+static_assert(kStdHeaderBytes[0] == 328 && kStdHeaderBytes[1] == 623, "header sizes of the contract");
+__device__ const JTabs g_std = make_std();
+__device__ const JIzz g_izz = make_izz();
+
+struct JDev {                          // the workspace's table area (optimize only)
+    JTabs tabs;
+    uint32_t hist[4][kJhEntries];
+};
+
+struct JQuant {
+    uint16_t q8[2][64];                // natural order: the divisor of the scaled-by-8 DCT output, quantiser << 3
+};
+
+struct JHeader {
+    int32_t H, W, ncomp, hs, vs;
+    uint32_t std_bytes;                // the header's length with the Annex K tables: the plain path starts without a read for it
+    uint8_t q[2][64];                  // zigzag order, as DQT lists them
+};
 
 // ---- sizes ------------------------------------------------------------------------------------------------------------------------
-// A block codes to at most 20 + 63 * 26 bits: DC <= 20 (with the quality-75 quantisers a DC difference has at most 9 magnitude bits, and
-// no DC code of either table is longer than 11), every AC coefficient <= 16 code bits + 10 magnitude bits; ZRL codes only replace
-// coefficients.  Stuffing at most doubles the bytes.
+// A block codes to fewer than 20 + 63 * 26 bits with ANY table of codes <= 16 bits: a coefficient of s magnitude bits is at least
+// 2^(s-1) quantiser steps, the squares of a block's 64 DCT outputs sum to at most 64 * 128^2 = 2^20 (the transform is orthonormal up to its
+// rounding), so 63 AC coefficients can average at most 8 magnitude bits: 63 * (16 + 8) + (16 + 11) = 1539 bits.  Stuffing at most doubles
+// the bytes.
 constexpr uint32_t kMaxBlockBits = 20 + 63 * 26;
-constexpr int64_t kMaxPixels = (int64_t)1 << 24;     // H * W limit: bit offsets stay below 2^32 (<= 442 k blocks * 1658 bits)
+constexpr int64_t kMaxPixels = (int64_t)1 << 24;     // H * W limit: bit offsets stay below 2^32 (<= 3 * 2^18 blocks * 1658 bits)
 constexpr uint32_t kChunk = 2048;                    // stream bytes per workgroup of the stuffing pass (256 threads x 8 bytes)
+constexpr int kWorkLd = 72;        // dwords per block of the row-pass output: 64 + 8, so the column pass of 4 blocks hits 32 distinct banks
 
 struct JGeom {
     int32_t H, W, ch, stride;          // stride: bytes per canvas row
-    int32_t mcu_cols, mcu_rows;        // RGB: 16x16 MCUs
+    int32_t mcu_cols, mcu_rows;
     int32_t wib, hib;                  // 8x8 luma blocks per row / column (ceil)
     int32_t units;                     // waves of jpeg_blocks_kernel: MCUs (RGB) or groups of 4 blocks in a block row (L)
+    int32_t nb, ny;                    // blocks per MCU, of them luma
     uint32_t nblocks;
     uint32_t stream_words, nchunks;    // capacity of the unstuffed stream (32-bit words), of the chunk table
-    size_t off_len, off_cnt, off_tot, off_stream, ws_bytes, out_bytes;
+    size_t off_len, off_cnt, off_tot, off_dev, off_stream, ws_bytes, out_bytes;
 };
 
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-bool make_geom(int32_t H, int32_t W, int32_t ch, JGeom& g) {
-    if ((ch != 1 && ch != 3) || H < 1 || H > 65535 || W < 1 || W > 65535 || (int64_t)H * W > kMaxPixels) return false;
+bool make_geom(int32_t H, int32_t W, int32_t ch, const st_jpeg_enc_params* p, JGeom& g) {
+    if (!p || (ch != 1 && ch != 3) || H < 1 || H > 65535 || W < 1 || W > 65535 || (int64_t)H * W > kMaxPixels) return false;
+    if (p->quality < 1 || p->quality > 100 || (p->optimize != 0 && p->optimize != 1)) return false;
+    if (!((p->hs == 1 && p->vs == 1) || (ch == 3 && p->hs == 2 && (p->vs == 1 || p->vs == 2)))) return false;
+    for (int i = 0; i < 4; ++i)
+        if (p->reserved[i]) return false;
     g.H = H, g.W = W, g.ch = ch, g.stride = 0;
-    g.mcu_cols = (W + 15) / 16, g.mcu_rows = (H + 15) / 16;
+    g.mcu_cols = (W + 8 * p->hs - 1) / (8 * p->hs), g.mcu_rows = (H + 8 * p->vs - 1) / (8 * p->vs);
     g.wib = (W + 7) / 8, g.hib = (H + 7) / 8;
     if (ch == 3) {
+        g.ny = p->hs * p->vs, g.nb = g.ny + 2;
         g.units = g.mcu_cols * g.mcu_rows;
-        g.nblocks = 6u * (uint32_t)g.units;
+        g.nblocks = (uint32_t)g.nb * (uint32_t)g.units;
     } else {
+        g.ny = 1, g.nb = 1;
         g.units = g.hib * ((g.wib + 3) / 4);
         g.nblocks = (uint32_t)g.wib * (uint32_t)g.hib;
     }
@@ -130,22 +145,25 @@ bool make_geom(int32_t H, int32_t W, int32_t ch, JGeom& g) {
     g.off_len = align16((size_t)g.nblocks * 128);
     g.off_cnt = g.off_len + align16((size_t)g.nblocks * 4);
     g.off_tot = g.off_cnt + align16((size_t)g.nchunks * 4);
-    g.off_stream = g.off_tot + 16;
+    g.off_dev = g.off_tot + 16;
+    g.off_stream = g.off_dev + (p->optimize ? align16(sizeof(JDev)) : 0);      // the plain path has no table area and reads none
     g.ws_bytes = g.off_stream + align16((size_t)g.stream_words * 4);
-    g.out_bytes = (size_t)kTablesHost.hdr_len[ch == 3] + 2 * (size_t)bytes + 2;
-    return true;
+    g.out_bytes = (size_t)kStdHeaderBytes[ch == 3] + 2 * (size_t)bytes + 2;
+    return g.ws_bytes <= 0x7fffffffu && g.out_bytes <= 0x7fffffffu;
 }
 
 // ---- kernel 1: canvas -> quantised blocks -----------------------------------------------------------------------------------------
-constexpr int kWorkLd = 72;        // dwords per block of the row-pass output: 64 + 8, so the column pass of 4 blocks hits 32 distinct banks
-
-template <int CH>
-__global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restrict__ src, int16_t* __restrict__ coef, const JGeom g) {
-    constexpr int NB = CH == 3 ? 6 : 4;
+template <int CH, int HS, int VS>
+__global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restrict__ src, int16_t* __restrict__ coef, const JGeom g, const JQuant qt,
+                                                          uint32_t* __restrict__ hist) {
+    constexpr int NY = CH == 3 ? HS * VS : 4, NB = CH == 3 ? NY + 2 : 4;
+    constexpr int MW = 8 * HS, MH = 8 * VS;
     __shared__ int16_t s_samp[4][NB * 64];
-    __shared__ int16_t s_cbcr[4][CH == 3 ? 512 : 1];
+    __shared__ int16_t s_cbcr[4][(CH == 3 && HS == 2) ? 2 * MW * MH : 1];
     __shared__ int s_work[4][NB * kWorkLd];
     __shared__ __attribute__((aligned(4))) int16_t s_out[4][NB * 64];
+    if (hist && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < 4 * kJhEntries; i += 256) hist[i] = 0u;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int unit = blockIdx.x * 4 + wv;
     const bool live = unit < g.units;
@@ -161,29 +179,41 @@ __global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restr
         int16_t* cbcr = s_cbcr[wv];
         if (live) {
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int row = p * 4 + (lane >> 4), col = lane & 15;
-                const int y = min(uy * 16 + row, g.H - 1), x = min(ux * 16 + col, g.W - 1);
+            for (int p = 0; p < HS * VS; ++p) {
+                const int idx = p * 64 + lane, row = idx / MW, col = idx % MW;
+                const int y = min(uy * MH + row, g.H - 1), x = min(ux * MW + col, g.W - 1);
                 const uint8_t* px = src + (size_t)y * g.stride + (size_t)x * 3;
                 const int r = px[0], gg = px[1], b = px[2];
                 const int Y = (19595 * r + 38470 * gg + 7471 * b + 32768) >> 16;
                 const int cb = (-11059 * r - 21709 * gg + 32768 * b + (128 << 16) + 32767) >> 16;
                 const int cr = (32768 * r - 27439 * gg - 5329 * b + (128 << 16) + 32767) >> 16;
-                samp[((row >> 3) * 2 + (col >> 3)) * 64 + (row & 7) * 8 + (col & 7)] = (int16_t)(Y - 128);
-                cbcr[row * 16 + col] = (int16_t)cb;
-                cbcr[256 + row * 16 + col] = (int16_t)cr;
+                samp[((row >> 3) * HS + (col >> 3)) * 64 + (row & 7) * 8 + (col & 7)] = (int16_t)(Y - 128);
+                if (HS == 1) {                                      // 4:4:4: chroma is copied
+                    samp[64 + idx] = (int16_t)(cb - 128);
+                    samp[128 + idx] = (int16_t)(cr - 128);
+                } else {
+                    cbcr[row * MW + col] = (int16_t)cb;
+                    cbcr[MW * MH + row * MW + col] = (int16_t)cr;
+                }
             }
         }
-        __syncthreads();
-        if (live) {
-            // h2v2: columns come from the (edge-replicated) input, rows past ceil(H / 2) replicate the last DOWNSAMPLED row
-            const int cy = lane >> 3, cx = lane & 7;
-            const int cyl = min(uy * 8 + cy, (g.H + 1) / 2 - 1) - uy * 8;
-            const int bias = (cx & 1) ? 2 : 1;
+        if (HS == 2) {
+            __syncthreads();
+            if (live) {
+                const int cy = lane >> 3, cx = lane & 7;
 #pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int16_t* f = cbcr + c * 256 + (2 * cyl) * 16 + 2 * cx;
-                samp[(4 + c) * 64 + lane] = (int16_t)(((f[0] + f[1] + f[16] + f[17] + bias) >> 2) - 128);
+                for (int c = 0; c < 2; ++c) {
+                    if (VS == 2) {
+                        // h2v2: columns come from the (edge-replicated) input, rows past ceil(H / 2) replicate the last DOWNSAMPLED row
+                        const int cyl = min(uy * 8 + cy, (g.H + 1) / 2 - 1) - uy * 8;
+                        const int16_t* f = cbcr + c * 256 + (2 * cyl) * 16 + 2 * cx;
+                        samp[(4 + c) * 64 + lane] = (int16_t)(((f[0] + f[1] + f[16] + f[17] + ((cx & 1) ? 2 : 1)) >> 2) - 128);
+                    } else {
+                        // h2v1: the same column rule; the bias alternates 0, 1 over the output columns
+                        const int16_t* f = cbcr + c * 128 + cy * 16 + 2 * cx;
+                        samp[(2 + c) * 64 + lane] = (int16_t)(((f[0] + f[1] + (cx & 1)) >> 1) - 128);
+                    }
+                }
             }
         }
     } else {
@@ -212,14 +242,14 @@ __global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restr
 #pragma unroll
         for (int k = 0; k < 8; ++k) d[k] = work[blk * kWorkLd + k * 8 + rc];
         fdct8<false>(d);
-        const int t = (CH == 3 && blk >= 4) ? 1 : 0;
+        const int t = (CH == 3 && blk >= NY) ? 1 : 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int nat = k * 8 + rc;
-            const uint32_t q8 = g_jt.q8[t][nat];
+            const uint32_t q8 = qt.q8[t][nat];
             const uint32_t a = (uint32_t)abs(d[k]);
             const int r = (int)((a + (q8 >> 1)) / q8);
-            outc[blk * 64 + g_jt.izz[nat]] = (int16_t)(d[k] < 0 ? -r : r);
+            outc[blk * 64 + g_izz.v[nat]] = (int16_t)(d[k] < 0 ? -r : r);
         }
     }
     __syncthreads();
@@ -229,16 +259,18 @@ __global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restr
     if (CH == 3) {
         // a Y block its MCU needs past the image's blocks is a dummy: AC zero, DC of the block before it in the MCU (a dummy bottom
         // row: DC of the last block of the row above)
-        const bool cdum = 2 * ux + 1 >= g.wib, rdum = 2 * uy + 1 >= g.hib;
+        const bool cdum = HS == 2 && 2 * ux + 1 >= g.wib, rdum = VS == 2 && 2 * uy + 1 >= g.hib;
         const uint32_t dc0 = (uint16_t)outc[0], dc1 = cdum ? dc0 : (uint16_t)outc[64], dc2 = rdum ? dc1 : (uint16_t)outc[128];
 #pragma unroll
-        for (int p = 0; p < 3; ++p) {
+        for (int p = 0; p < (NB + 1) / 2; ++p) {
             const int w = p * 64 + lane, b = w >> 5;
-            uint32_t v = out32[w];
-            if (b == 1 && cdum) v = (w & 31) ? 0u : dc0;
-            if (b == 2 && rdum) v = (w & 31) ? 0u : dc1;
-            if (b == 3 && (rdum || cdum)) v = (w & 31) ? 0u : (rdum ? dc1 : dc2);
-            dst[(size_t)unit * 192 + w] = v;
+            if (w < NB * 32) {
+                uint32_t v = out32[w];
+                if (b == 1 && cdum) v = (w & 31) ? 0u : dc0;
+                if (VS == 2 && b == 2 && rdum) v = (w & 31) ? 0u : dc1;
+                if (VS == 2 && b == 3 && (rdum || cdum)) v = (w & 31) ? 0u : (rdum ? dc1 : dc2);
+                dst[(size_t)unit * (NB * 32) + w] = v;
+            }
         }
     } else {
         const size_t b0 = (size_t)uy * g.wib + (size_t)ux * 4;
@@ -252,25 +284,25 @@ __global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restr
 
 // ---- entropy coding ---------------------------------------------------------------------------------------------------------------
 struct HuffLds {
-    uint32_t dc[2][12];
+    uint32_t dc[2][16];
     uint32_t ac[2][256];
 };
 
-__device__ __forceinline__ void load_huff(HuffLds& h) {
-    for (int i = threadIdx.x; i < 512; i += blockDim.x) h.ac[i >> 8][i & 255] = g_jt.ac[i >> 8][i & 255];
-    if (threadIdx.x < 24) h.dc[threadIdx.x / 12][threadIdx.x % 12] = g_jt.dc[threadIdx.x / 12][threadIdx.x % 12];
+__device__ __forceinline__ void load_huff(HuffLds& h, const JTabs* __restrict__ tabs) {
+    for (int i = threadIdx.x; i < 512; i += blockDim.x) h.ac[i >> 8][i & 255] = tabs->code[2 * (i >> 8) + 1][i & 255];
+    if (threadIdx.x < 32) h.dc[threadIdx.x >> 4][threadIdx.x & 15] = tabs->code[2 * (threadIdx.x >> 4)][threadIdx.x & 15];
     __syncthreads();
 }
 
 // scan-order predecessor of block b inside its component (-1: none) and the block's table (0 luma, 1 chroma)
-__device__ __forceinline__ int64_t block_pred(uint32_t b, int ch, int& table) {
+__device__ __forceinline__ int64_t block_pred(uint32_t b, uint32_t nb, uint32_t ny, int& table) {
     table = 0;
-    if (ch == 1) return (int64_t)b - 1;
-    const uint32_t m = b / 6, j = b - m * 6;
-    table = j >= 4;
-    if (j >= 1 && j <= 3) return (int64_t)b - 1;
+    if (nb == 1) return (int64_t)b - 1;
+    const uint32_t m = b / nb, j = b - m * nb;
+    table = j >= ny;
+    if (j >= 1 && j < ny) return (int64_t)b - 1;
     if (m == 0) return -1;
-    return (int64_t)(m - 1) * 6 + (j == 0 ? 3 : j);
+    return (int64_t)(m - 1) * nb + (j == 0 ? ny - 1 : j);
 }
 
 __device__ __forceinline__ int coef_at(const uint4& w, int e) {      // e: constant after unrolling
@@ -280,16 +312,11 @@ __device__ __forceinline__ int coef_at(const uint4& w, int e) {      // e: const
 
 __device__ __forceinline__ int magnitude_bits(int v) { return 32 - __clz(abs(v)); }
 
-__global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ len, uint32_t nblocks, int ch) {
-    __shared__ HuffLds h;
-    load_huff(h);
-    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= nblocks) return;
-    int t;
-    const int64_t pb = block_pred(b, ch, t);
-    const int pred = pb < 0 ? 0 : (int)coef[pb * 64];
+// the symbols of block b in scan order: dc(category, difference), then per nonzero coefficient zrl(k), the k >= 0 ZRL symbols (0xF0) of a run
+// above 15, and ac(run << 4 | size, value, size) with the rest of the run; EOB is ac(0x00, 0, 0)
+template <class DC, class ZRL, class AC>
+__device__ __forceinline__ void walk_block(const int16_t* __restrict__ coef, uint32_t b, int pred, DC&& dc, ZRL&& zrl, AC&& ac) {
     const uint4* c4 = (const uint4*)(coef + (size_t)b * 64);
-    uint32_t bits = 0;
     int run = 0;
 #pragma unroll 1
     for (int q = 0; q < 8; ++q) {
@@ -298,19 +325,89 @@ __global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t* __restric
         for (int e = 0; e < 8; ++e) {
             const int v = coef_at(w, e);
             if (q == 0 && e == 0) {
-                const int n = magnitude_bits(v - pred);
-                bits += (h.dc[t][n] >> 16) + n;
+                dc(magnitude_bits(v - pred), v - pred);
             } else if (v == 0) {
                 ++run;
             } else {
-                bits += (uint32_t)(run >> 4) * (h.ac[t][0xF0] >> 16);
+                zrl(run >> 4);
                 const int n = magnitude_bits(v);
-                bits += (h.ac[t][((run & 15) << 4) | n] >> 16) + n;
+                ac(((run & 15) << 4) | n, v, n);
                 run = 0;
             }
         }
     }
-    if (run) bits += h.ac[t][0] >> 16;
+    if (run) ac(0x00, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void jpeg_hist_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ hist, uint32_t nblocks, uint32_t nb, uint32_t ny) {
+    __shared__ uint32_t s_hist[4 * kJhEntries];
+    for (int i = threadIdx.x; i < 4 * kJhEntries; i += 256) s_hist[i] = 0u;
+    __syncthreads();
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b < nblocks) {
+        int t;
+        const int64_t pb = block_pred(b, nb, ny, t);
+        const int pred = pb < 0 ? 0 : (int)coef[pb * 64];
+        uint32_t* hd = s_hist + (2 * t) * kJhEntries;
+        uint32_t* ha = hd + kJhEntries;
+        walk_block(
+            coef, b, pred, [&](int n, int) { atomicAdd(hd + (n & 15), 1u); },
+            [&](int k) {
+                if (k) atomicAdd(ha + 0xF0, (uint32_t)k);
+            },
+            [&](int sym, int, int) { atomicAdd(ha + (sym & 255), 1u); });
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 4 * kJhEntries; i += 256) {
+        const uint32_t v = s_hist[i];
+        if (v) atomicAdd(hist + i, v);
+    }
+}
+
+struct WaveTeam {
+    static constexpr int LANES = 64;
+    __device__ __forceinline__ int lane() const { return (int)threadIdx.x; }
+    __device__ __forceinline__ static uint64_t xor64(uint64_t v, int o) {
+        return ((uint64_t)__shfl_xor((uint32_t)(v >> 32), o, 64) << 32) | __shfl_xor((uint32_t)v, o, 64);
+    }
+    __device__ __forceinline__ void min2_u64(uint64_t& a, uint64_t& b) const {      // butterfly: partners merge disjoint sets of lanes
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t pa = xor64(a, o), pb = xor64(b, o);
+            const uint64_t lo = a < pa ? a : pa, hi = a < pa ? pa : a, rest = b < pb ? b : pb;
+            a = lo, b = hi < rest ? hi : rest;
+        }
+    }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+};
+
+__global__ __launch_bounds__(64) void jpeg_table_kernel(JDev* __restrict__ dev) {
+    __shared__ JhWork s;
+    const int t = blockIdx.x;
+    jh_gen_optimal_table(WaveTeam{}, dev->hist[t], s);
+    JTabs& o = dev->tabs;
+    for (int i = threadIdx.x; i < 256; i += 64) {
+        o.code[t][i] = s.code[i];
+        o.dht[t][16 + i] = i < s.nsym ? s.huffval[i] : (uint8_t)0;
+    }
+    if (threadIdx.x < 16) o.dht[t][threadIdx.x] = (uint8_t)s.bits[threadIdx.x + 1];
+    if (threadIdx.x == 0) o.dht_len[t] = 16 + s.nsym;
+}
+
+// dev: the tables the table kernel made, or nullptr for the Annex K ones (here and below)
+__global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ len, const JDev* __restrict__ dev, uint32_t nblocks,
+                                                        uint32_t nb, uint32_t ny) {
+    __shared__ HuffLds h;
+    load_huff(h, dev ? &dev->tabs : &g_std);
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= nblocks) return;
+    int t;
+    const int64_t pb = block_pred(b, nb, ny, t);
+    const int pred = pb < 0 ? 0 : (int)coef[pb * 64];
+    uint32_t bits = 0;
+    walk_block(
+        coef, b, pred, [&](int n, int) { bits += (h.dc[t][n & 15] >> 16) + n; }, [&](int k) { bits += (uint32_t)k * (h.ac[t][0xF0] >> 16); },
+        [&](int sym, int, int n) { bits += (h.ac[t][sym & 255] >> 16) + n; });
     len[b] = bits;
 }
 
@@ -361,6 +458,7 @@ __global__ __launch_bounds__(256) void jpeg_zero_kernel(uint32_t* __restrict__ s
 
 struct BitWriter {
     uint32_t* word;      // next word of the stream (bytes in stream order: the big-endian word, byte-swapped)
+    uint32_t* end;       // one past the stream's capacity: nothing is written from here on
     uint64_t acc;        // pending bits in the low `n`
     int n;
     bool first;          // the next word is shared with the blocks before this one
@@ -372,74 +470,41 @@ __device__ __forceinline__ void put_bits(BitWriter& w, uint32_t v, int len) {
     if (w.n >= 32) {
         w.n -= 32;
         const uint32_t word = __builtin_bswap32((uint32_t)(w.acc >> w.n));
-        if (w.first) atomicOr(w.word, word);
-        else *w.word = word;
+        if (w.word < w.end) {
+            if (w.first) atomicOr(w.word, word);
+            else *w.word = word;
+        }
         w.first = false;
         ++w.word;
     }
 }
 
 __global__ __launch_bounds__(256) void jpeg_pack_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ off, const uint32_t* __restrict__ total_bits,
-                                                        uint32_t* __restrict__ stream, uint32_t nblocks, int ch) {
+                                                        uint32_t* __restrict__ stream, uint32_t cap_words, const JDev* __restrict__ dev, uint32_t nblocks, uint32_t nb,
+                                                        uint32_t ny) {
     __shared__ HuffLds h;
-    load_huff(h);
+    load_huff(h, dev ? &dev->tabs : &g_std);
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b >= nblocks) return;
     int t;
-    const int64_t pb = block_pred(b, ch, t);
+    const int64_t pb = block_pred(b, nb, ny, t);
     const int pred = pb < 0 ? 0 : (int)coef[pb * 64];
-    const uint4* c4 = (const uint4*)(coef + (size_t)b * 64);
     const uint32_t o = off[b];
-    BitWriter w{stream + (o >> 5), 0, (int)(o & 31u), true};
-    int run = 0;
-#pragma unroll 1
-    for (int q = 0; q < 8; ++q) {
-        const uint4 cw = c4[q];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int v = coef_at(cw, e);
-            if (q == 0 && e == 0) {
-                v -= pred;
-                const int n = magnitude_bits(v);
-                const uint32_t cl = h.dc[t][n];
-                put_bits(w, ((cl & 0xffffu) << n) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << n) - 1u)), (int)(cl >> 16) + n);
-            } else if (v == 0) {
-                ++run;
-            } else {
-                const uint32_t zrl = h.ac[t][0xF0];
-                for (; run > 15; run -= 16) put_bits(w, zrl & 0xffffu, (int)(zrl >> 16));
-                const int n = magnitude_bits(v);
-                const uint32_t cl = h.ac[t][(run << 4) | n];
-                put_bits(w, ((cl & 0xffffu) << n) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << n) - 1u)), (int)(cl >> 16) + n);
-                run = 0;
-            }
-        }
-    }
-    if (run) put_bits(w, h.ac[t][0] & 0xffffu, (int)(h.ac[t][0] >> 16));
+    BitWriter w{stream + (o >> 5), stream + cap_words, 0, (int)(o & 31u), true};
+    auto put = [&](uint32_t cl, int v, int n) {
+        put_bits(w, ((cl & 0xffffu) << n) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << n) - 1u)), (int)(cl >> 16) + n);
+    };
+    walk_block(
+        coef, b, pred, [&](int n, int v) { put(h.dc[t][n & 15], v, n); },
+        [&](int k) {
+            for (; k > 0; --k) put(h.ac[t][0xF0], 0, 0);
+        },
+        [&](int sym, int v, int n) { put(h.ac[t][sym & 255], v, n); });
     if (b == nblocks - 1) {                                           // the final partial byte is padded with 1-bits
         const int pad = (int)((8u - (*total_bits & 7u)) & 7u);
         put_bits(w, (1u << pad) - 1u, pad);
     }
-    if (w.n > 0) atomicOr(w.word, __builtin_bswap32((uint32_t)(w.acc << (32 - w.n))));
-}
-
-__device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t& exclusive, uint32_t* s_wave) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int k = 0; k < 4; ++k) {
-        if (k < wv) before += s_wave[k];
-        all += s_wave[k];
-    }
-    exclusive = before + inc - v;
-    return all;
+    if (w.n > 0 && w.word < w.end) atomicOr(w.word, __builtin_bswap32((uint32_t)(w.acc << (32 - w.n))));
 }
 
 __device__ __forceinline__ uint32_t ff_bytes(uint2 d, uint32_t i0, uint32_t nbytes) {
@@ -452,6 +517,7 @@ __device__ __forceinline__ uint32_t ff_bytes(uint2 d, uint32_t i0, uint32_t nbyt
     return c;
 }
 
+// chunks behind the stream get no count: jpeg_scan_kernel bounds itself with the same total_bits
 __global__ __launch_bounds__(256) void jpeg_count_kernel(const uint32_t* __restrict__ stream, const uint32_t* __restrict__ total_bits, uint32_t* __restrict__ cnt) {
     __shared__ uint32_t s_wave[4];
     const uint32_t nbytes = (*total_bits + 7u) >> 3;
@@ -463,21 +529,57 @@ __global__ __launch_bounds__(256) void jpeg_count_kernel(const uint32_t* __restr
     if (threadIdx.x == 0) cnt[blockIdx.x] = all;
 }
 
+// SOI, APP0, DQT x n, SOF0, DHT x n (DC0, AC0, DC1, AC1), SOS; one workgroup
+__device__ __forceinline__ void write_header(uint8_t* __restrict__ out, const JHeader& hp, const JTabs* __restrict__ tabs) {
+    const int ntab = hp.ncomp == 3 ? 2 : 1, nc = hp.ncomp, tid = threadIdx.x;
+    uint32_t n = 0;
+    if (tid < 20) {
+        const uint32_t lo = 0xE0FFD8FFu, mid = 0x464A1000u;                      // FF D8 FF E0 | 00 10 'J' 'F'
+        const uint8_t rest[12] = {'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+        uint8_t v = 0;
+        if (tid < 4) v = (uint8_t)(lo >> (8 * tid));
+        else if (tid < 8) v = (uint8_t)(mid >> (8 * (tid - 4)));
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            if (tid == 8 + k) v = rest[k];
+        out[tid] = v;
+    }
+    n = 20;
+    for (int c = 0; c < ntab; ++c, n += 69) {
+        if (tid < 5) out[n + tid] = tid == 0 ? 0xFF : tid == 1 ? 0xDB : tid == 2 ? 0 : tid == 3 ? 67 : (uint8_t)c;
+        if (tid < 64) out[n + 5 + tid] = hp.q[c][tid];
+    }
+    if (tid == 0) {
+        uint8_t* h = out + n;
+        h[0] = 0xFF, h[1] = 0xC0, h[2] = 0, h[3] = (uint8_t)(8 + 3 * nc), h[4] = 8;
+        h[5] = (uint8_t)(hp.H >> 8), h[6] = (uint8_t)(hp.H & 255), h[7] = (uint8_t)(hp.W >> 8), h[8] = (uint8_t)(hp.W & 255), h[9] = (uint8_t)nc;
+        for (int c = 0; c < nc; ++c) h[10 + 3 * c] = (uint8_t)(c + 1), h[11 + 3 * c] = c ? 0x11 : (uint8_t)(hp.hs << 4 | hp.vs), h[12 + 3 * c] = c ? 1 : 0;
+    }
+    n += 10 + 3 * nc;
+    for (int i = 0; i < 2 * ntab; ++i) {
+        const uint32_t len = (uint32_t)tabs->dht_len[i];
+        if (tid < 5) out[n + tid] = tid == 0 ? 0xFF : tid == 1 ? 0xC4 : tid == 2 ? (uint8_t)((len + 3) >> 8) : tid == 3 ? (uint8_t)((len + 3) & 255) : (uint8_t)((i & 1) << 4 | (i >> 1));
+        for (uint32_t k = tid; k < len; k += 256) out[n + 5 + k] = tabs->dht[i][k];
+        n += 5 + len;
+    }
+    if (tid == 0) {
+        uint8_t* h = out + n;
+        h[0] = 0xFF, h[1] = 0xDA, h[2] = 0, h[3] = (uint8_t)(6 + 2 * nc), h[4] = (uint8_t)nc;
+        for (int c = 0; c < nc; ++c) h[5 + 2 * c] = (uint8_t)(c + 1), h[6 + 2 * c] = c ? 0x11 : 0x00;
+        h[5 + 2 * nc] = 0, h[6 + 2 * nc] = 63, h[7 + 2 * nc] = 0;
+    }
+}
+
 __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint32_t* __restrict__ stream, const uint32_t* __restrict__ totals, const uint32_t* __restrict__ cnt_off,
-                                                         uint8_t* __restrict__ out, int32_t* __restrict__ out_nbytes, int H, int W, int rgb) {
+                                                         uint8_t* __restrict__ out, int32_t* __restrict__ out_nbytes, const JHeader hp, const JDev* __restrict__ dev) {
     __shared__ uint32_t s_wave[4];
+    const JTabs* tabs = dev ? &dev->tabs : &g_std;
     const uint32_t nbytes = (totals[0] + 7u) >> 3;
-    const uint32_t hdr = (uint32_t)g_jt.hdr_len[rgb];
-    if (blockIdx.x == 0) {
-        const uint32_t so = (uint32_t)g_jt.size_off[rgb];
-        for (uint32_t i = threadIdx.x; i < hdr; i += 256) {
-            uint8_t v = g_jt.hdr[rgb][i];
-            if (i == so) v = (uint8_t)(H >> 8);
-            if (i == so + 1) v = (uint8_t)(H & 255);
-            if (i == so + 2) v = (uint8_t)(W >> 8);
-            if (i == so + 3) v = (uint8_t)(W & 255);
-            out[i] = v;
-        }
+    const uint32_t hdr = dev ? header_bytes(hp.ncomp, dev->tabs) : hp.std_bytes;
+    // the header is the last workgroup's: its chunk lies behind the stream unless the image fills the worst case, so the header is written
+    // beside the scatter and not in front of workgroup 0's
+    if (blockIdx.x == gridDim.x - 1) {
+        write_header(out, hp, tabs);
         if (threadIdx.x == 0) {
             const uint32_t end = hdr + nbytes + totals[1];
             out[end] = 0xFF, out[end + 1] = 0xD9;
@@ -500,60 +602,109 @@ __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint32_t* __restr
     }
 }
 
+int quantiser(int table, int natural, int quality) {                 // jpeg_quality_scaling + jpeg_add_quant_table, baseline clamp
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    const int q = (kQBase[table][natural] * scale + 50) / 100;
+    return q < 1 ? 1 : (q > 255 ? 255 : q);
+}
+
+st_jpeg_enc_params default_params(int32_t channels) {                // Pillow's defaults: quality 75, 4:2:0 (one channel: 1 x 1), Annex K tables
+    const int32_t s = channels == 3 ? 2 : 1;
+    return st_jpeg_enc_params{75, s, s, 0, {0, 0, 0, 0}};
+}
+
 }  // namespace
 
-// jpeg_scan_kernel for csrc/jpeg_dec.hip (its chunk and block counts): in-place exclusive prefix sum of data[0 .. n), total -> *total
 hipError_t st_jpeg_scan_u32(uint32_t* data, uint32_t n, uint32_t* total, hipStream_t st) {
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, data, n, (const uint32_t*)nullptr, total);
     return hipGetLastError();
 }
 
-extern "C" int st_jpeg_workspace_bytes(int32_t H, int32_t W, int32_t channels) {
+extern "C" int st_abi_jpeg_enc_params_size(void) { return (int)sizeof(st_jpeg_enc_params); }
+
+extern "C" int st_jpeg_workspace_bytes_ex(int32_t H, int32_t W, int32_t channels, const st_jpeg_enc_params* params) {
     JGeom g;
-    return make_geom(H, W, channels, g) ? (int)g.ws_bytes : 0;
+    return make_geom(H, W, channels, params, g) ? (int)g.ws_bytes : 0;
 }
 
-extern "C" int st_jpeg_max_bytes(int32_t H, int32_t W, int32_t channels) {
+extern "C" int st_jpeg_max_bytes_ex(int32_t H, int32_t W, int32_t channels, const st_jpeg_enc_params* params) {
     JGeom g;
-    return make_geom(H, W, channels, g) ? (int)g.out_bytes : 0;
+    return make_geom(H, W, channels, params, g) ? (int)g.out_bytes : 0;
 }
 
-extern "C" int st_jpeg_encode_u8(const void* src, int32_t H, int32_t W, int32_t channels, int64_t row_stride, void* out, int64_t out_capacity,
-                                 int32_t* out_nbytes, void* workspace, int64_t workspace_bytes, void* stream) {
+extern "C" int st_jpeg_encode_u8_ex(const void* src, int32_t H, int32_t W, int32_t channels, int64_t row_stride, const st_jpeg_enc_params* params, void* out,
+                                    int64_t out_capacity, int32_t* out_nbytes, void* workspace, int64_t workspace_bytes, void* stream) {
     JGeom g;
-    if (!src || !out || !out_nbytes || !workspace || !make_geom(H, W, channels, g)) return ST_EINVAL;
+    if (!src || !out || !out_nbytes || !workspace || !make_geom(H, W, channels, params, g)) return ST_EINVAL;
     if (row_stride < (int64_t)W * channels || row_stride > 0x7fffffff || ((uintptr_t)workspace & 15)) return ST_EINVAL;
     if (out_capacity < (int64_t)g.out_bytes || workspace_bytes < (int64_t)g.ws_bytes) return ST_EINVAL;
     g.stride = (int32_t)row_stride;
+    JQuant qt;
+    JHeader hp;
+    hp.H = H, hp.W = W, hp.ncomp = channels, hp.hs = params->hs, hp.vs = params->vs, hp.std_bytes = kStdHeaderBytes[channels == 3];
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 64; ++i) {
+            qt.q8[c][i] = (uint16_t)(quantiser(c, i, params->quality) << 3);
+            hp.q[c][i] = (uint8_t)quantiser(c, kZigzag[i], params->quality);
+        }
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     int16_t* coef = (int16_t*)ws;
     uint32_t* len = (uint32_t*)(ws + g.off_len);
     uint32_t* cnt = (uint32_t*)(ws + g.off_cnt);
     uint32_t* tot = (uint32_t*)(ws + g.off_tot);          // [0] bits of the scan, [1] its 0xFF bytes
+    JDev* dev = params->optimize ? (JDev*)(ws + g.off_dev) : nullptr;
     uint32_t* bits = (uint32_t*)(ws + g.off_stream);
-    const unsigned per_block = (g.nblocks + 255) / 256;
-    if (channels == 3)
-        hipLaunchKernelGGL(jpeg_blocks_kernel<3>, dim3((g.units + 3) / 4), dim3(256), 0, st, (const uint8_t*)src, coef, g);
+    uint32_t* hist = dev ? &dev->hist[0][0] : nullptr;
+    const unsigned per_block = (g.nblocks + 255) / 256, grid = (g.units + 3) / 4;
+    const uint32_t nb = (uint32_t)g.nb, ny = (uint32_t)g.ny;
+    if (channels == 1)
+        hipLaunchKernelGGL((jpeg_blocks_kernel<1, 1, 1>), dim3(grid), dim3(256), 0, st, (const uint8_t*)src, coef, g, qt, hist);
+    else if (params->hs == 1)
+        hipLaunchKernelGGL((jpeg_blocks_kernel<3, 1, 1>), dim3(grid), dim3(256), 0, st, (const uint8_t*)src, coef, g, qt, hist);
+    else if (params->vs == 1)
+        hipLaunchKernelGGL((jpeg_blocks_kernel<3, 2, 1>), dim3(grid), dim3(256), 0, st, (const uint8_t*)src, coef, g, qt, hist);
     else
-        hipLaunchKernelGGL(jpeg_blocks_kernel<1>, dim3((g.units + 3) / 4), dim3(256), 0, st, (const uint8_t*)src, coef, g);
+        hipLaunchKernelGGL((jpeg_blocks_kernel<3, 2, 2>), dim3(grid), dim3(256), 0, st, (const uint8_t*)src, coef, g, qt, hist);
     ST_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_bits_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, len, g.nblocks, channels);
+    if (dev) {
+        hipLaunchKernelGGL(jpeg_hist_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, hist, g.nblocks, nb, ny);
+        ST_CHECK_LAUNCH();
+        hipLaunchKernelGGL(jpeg_table_kernel, dim3(channels == 3 ? 4 : 2), dim3(64), 0, st, dev);
+        ST_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(jpeg_bits_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, len, (const JDev*)dev, g.nblocks, nb, ny);
     ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, len, g.nblocks, (const uint32_t*)nullptr, tot);
     ST_CHECK_LAUNCH();
     const unsigned zero_grid = (g.stream_words + 255) / 256 < 512 ? (g.stream_words + 255) / 256 : 512;
     hipLaunchKernelGGL(jpeg_zero_kernel, dim3(zero_grid), dim3(256), 0, st, bits, (const uint32_t*)tot, g.stream_words);
     ST_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_pack_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, (const uint32_t*)len, (const uint32_t*)tot, bits, g.nblocks,
-                       channels);
+    hipLaunchKernelGGL(jpeg_pack_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, (const uint32_t*)len, (const uint32_t*)tot, bits, g.stream_words,
+                       (const JDev*)dev, g.nblocks, nb, ny);
     ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_count_kernel, dim3(g.nchunks), dim3(256), 0, st, (const uint32_t*)bits, (const uint32_t*)tot, cnt);
     ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, g.nchunks, (const uint32_t*)tot, tot + 1);
     ST_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3(g.nchunks), dim3(256), 0, st, (const uint32_t*)bits, (const uint32_t*)tot, (const uint32_t*)cnt, (uint8_t*)out,
-                       out_nbytes, H, W, channels == 3 ? 1 : 0);
+    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3(g.nchunks), dim3(256), 0, st, (const uint32_t*)bits, (const uint32_t*)tot, (const uint32_t*)cnt, (uint8_t*)out, out_nbytes,
+                       hp, (const JDev*)dev);
     ST_CHECK_LAUNCH();
     return ST_OK;
+}
+
+extern "C" int st_jpeg_workspace_bytes(int32_t H, int32_t W, int32_t channels) {
+    const st_jpeg_enc_params p = default_params(channels);
+    return st_jpeg_workspace_bytes_ex(H, W, channels, &p);
+}
+
+extern "C" int st_jpeg_max_bytes(int32_t H, int32_t W, int32_t channels) {
+    const st_jpeg_enc_params p = default_params(channels);
+    return st_jpeg_max_bytes_ex(H, W, channels, &p);
+}
+
+extern "C" int st_jpeg_encode_u8(const void* src, int32_t H, int32_t W, int32_t channels, int64_t row_stride, void* out, int64_t out_capacity,
+                                 int32_t* out_nbytes, void* workspace, int64_t workspace_bytes, void* stream) {
+    const st_jpeg_enc_params p = default_params(channels);
+    return st_jpeg_encode_u8_ex(src, H, W, channels, row_stride, &p, out, out_capacity, out_nbytes, workspace, workspace_bytes, stream);
 }

@@ -17,9 +17,8 @@
 //   jpegd_pixels_kernel   one thread per pixel: fancy h2v1 / h2v2 upsampling (replication at chroma width <= 2), colour conversion, HWC store
 #include "common.h"
 #include "jpeg_dec_core.h"
+#include "jpeg_scan.h"
 #include "../../include/stitch_gfx950.h"
-
-hipError_t st_jpeg_scan_u32(uint32_t* data, uint32_t n, uint32_t* total, hipStream_t st);      // csrc/jpeg.hip
 
 namespace {
 
@@ -84,25 +83,6 @@ bool make_geom(int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, int6
 }
 
 // ---- unstuffing -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t& exclusive, uint32_t* s_wave) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int k = 0; k < 4; ++k) {
-        if (k < wv) before += s_wave[k];
-        all += s_wave[k];
-    }
-    exclusive = before + inc - v;
-    return all;
-}
-
 // the 8 scan bytes from i0 and the byte before them; bit k of the result: byte i0 + k is a stuffed 0x00
 __device__ __forceinline__ uint32_t stuffed_mask(const uint8_t* __restrict__ scan, uint32_t i0, uint32_t n, uint8_t (&b)[8]) {
     uint32_t prev = (i0 > 0 && i0 <= n) ? scan[i0 - 1] : 0u, m = 0;

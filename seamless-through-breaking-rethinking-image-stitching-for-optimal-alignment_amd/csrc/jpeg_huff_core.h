@@ -1,4 +1,4 @@
-// libjpeg's jpeg_gen_optimal_table (jchuff.c) for csrc/jpeg_opts.hip's table kernel, in plain C++ so that a host program
+// libjpeg's jpeg_gen_optimal_table (jchuff.c) for csrc/jpeg.hip's table kernel, in plain C++ so that a host program
 // (tools/jpeg_huff_host_check.cpp, built with the host compiler's sanitizers) runs exactly what the kernel runs.  Contract: README.md; CPU
 // restatement: tests/_jpeg_opts_ref.py `gen_optimal_table`.
 //

@@ -762,7 +762,8 @@ _JPEG_SAMPLING = {None: (2, 2), 2: (2, 2), 1: (2, 1), 0: (1, 1)}        # Pillow
 
 
 def _jpeg_enc_params(channels, quality, subsampling, optimize):
-    """The `JpegEncParams` of Pillow's `save` keywords, or None when every keyword is at its default (the encoder of Pillow's defaults)."""
+    """The `JpegEncParams` of Pillow's `save` keywords, or None when every keyword is at its default (`st_jpeg_encode_u8`, which fills in
+    Pillow's defaults itself)."""
     if quality is None and subsampling is None and not optimize:
         return None
     if subsampling not in _JPEG_SAMPLING or isinstance(subsampling, bool):
@@ -780,8 +781,9 @@ def jpeg_encode(u8, workspace=None, quality=None, subsampling=None, optimize=Fal
     """out.py:260-312 `Image.fromarray(arr).save(path)` on the GPU: uint8 [H,W,3] (RGB) or [H,W] (L) -> (buf, nbytes), the JPEG file Pillow
     writes, byte for byte.  buf: uint8 device tensor of the worst-case size, nbytes: device int32 [1], the file is buf[:nbytes].  Rows may be
     strided (a column slice of a wider canvas).  No host synchronisation; current stream.
-    `quality` (1..100), `subsampling` (RGB only: 0 4:4:4, 1 4:2:2, 2 4:2:0) and `optimize` are Pillow's `save` keywords (csrc/jpeg_opts.hip);
-    with all three at their defaults this is the encoder of Pillow's defaults -- quality 75, 4:2:0, the Annex K tables (csrc/jpeg.hip).
+    `quality` (1..100), `subsampling` (RGB only: 0 4:4:4, 1 4:2:2, 2 4:2:0) and `optimize` are Pillow's `save` keywords (`st_jpeg_encode_u8_ex`);
+    with all three at their defaults the call goes to `st_jpeg_encode_u8`, the same encoder (csrc/jpeg.hip) at Pillow's defaults -- quality 75,
+    4:2:0, the Annex K tables.
     `workspace`: a uint8 device tensor of at least `jpeg_workspace_bytes` (same keywords) to reuse (stream-ordered: same stream as its last use)."""
     if u8.dtype != torch.uint8 or not (u8.dim() == 2 or (u8.dim() == 3 and u8.shape[2] == 3)):
         raise ValueError(f"uint8 [H,W,3] or [H,W] expected, got {u8.dtype} {tuple(u8.shape)}")

@@ -1,7 +1,7 @@
 """CPU restatement of the JPEG encoder's options, on top of tests/_jpeg_ref.py (its DCT, colour conversion, h2v2 downsampling and, for the
 Annex K tables, its entropy coder): the file `Image.fromarray(u8).save(path, quality=q, subsampling=s, optimize=o)` writes on
-libjpeg-turbo, in integer numpy.  csrc/jpeg_opts.hip implements the same contract on the GPU; tests/test_jpeg_opts_cpu.py pins this file to
-Pillow (tests/golden/jpeg_opts_pil.npz, written by tools/make_jpeg_opts_golden.py).
+libjpeg-turbo, in integer numpy.  csrc/jpeg.hip implements the same contract on the GPU (`st_jpeg_encode_u8_ex`);
+tests/test_jpeg_opts_cpu.py pins this file to Pillow (tests/golden/jpeg_opts_pil.npz, written by tools/make_jpeg_opts_golden.py).
 
   quality      1..100: libjpeg's scaling (5000 / q below 50, 200 - 2 q from 50 up), (base * scale + 50) / 100 clamped to 1..255
   subsampling  None / 2: 4:2:0 (16x16 MCU), 1: 4:2:2 (16x8 MCU: Y Y Cb Cr, h2v1 with the alternating 0 / 1 bias), 0: 4:4:4 (8x8 MCU)

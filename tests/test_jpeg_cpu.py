@@ -1,6 +1,7 @@
 """The JPEG contract, decided on the CPU: tests/_jpeg_ref.py (what csrc/jpeg.hip implements) equals Pillow's files byte for byte, the golden
-cases exercise every rule of the contract (a planted defect changes a file), the C entry rejects bad arguments before any launch, and the
-kernels use no scratch and the LDS the README states."""
+cases exercise every rule of the contract (a planted defect changes a file), the C entry rejects bad arguments before any launch, the size
+queries of both entries return the documented formulas, and the kernels use no scratch and the LDS the README states."""
+import ctypes as C
 import importlib.util
 import io
 import os
@@ -90,6 +91,33 @@ def test_entry_rejects_bad_arguments_without_touching_the_gpu():
     assert call(need=need - 1) == 1001 and call(ws=ws + 4) == 1001 and call(stride=W * 3 - 1) == 1001
 
 
+SIZE_SHAPES = [(1, 1, 1), (1, 1, 3), (37, 53, 3), (33, 41, 1), (548, 588, 3), (4096, 4096, 3), (65535, 256, 1)]
+
+
+def test_size_queries_return_the_documented_formulas():
+    """No GPU is touched.  Both entries at Pillow's defaults: the layout without a table area; `optimize` adds the table area, a constant."""
+    from stitch_amd._lib import JpegEncParams, lib
+
+    def a16(v):
+        return (v + 15) & ~15
+    extra = set()
+    for H, W, ch in SIZE_SHAPES:
+        nb = 6 * -(-W // 16) * -(-H // 16) if ch == 3 else -(-W // 8) * -(-H // 8)
+        bits = nb * 1658
+        words, nbytes = -(-bits // 32) + 4, -(-bits // 8)
+        chunks = -(-nbytes // 2048)
+        ws = a16(128 * nb) + a16(4 * nb) + a16(4 * chunks) + 16 + a16(4 * words)
+        out = (623 if ch == 3 else 328) + 2 * nbytes + 2
+        assert (lib.st_jpeg_workspace_bytes(H, W, ch), lib.st_jpeg_max_bytes(H, W, ch)) == (ws, out), (H, W, ch)
+        s = 2 if ch == 3 else 1
+        plain, opt = JpegEncParams(75, s, s, 0), JpegEncParams(75, s, s, 1)
+        assert (lib.st_jpeg_workspace_bytes_ex(H, W, ch, C.byref(plain)), lib.st_jpeg_max_bytes_ex(H, W, ch, C.byref(plain))) == (ws, out), (H, W, ch)
+        assert lib.st_jpeg_max_bytes_ex(H, W, ch, C.byref(opt)) == out
+        extra.add(lib.st_jpeg_workspace_bytes_ex(H, W, ch, C.byref(opt)) - ws)
+    (table_area,) = extra                                           # the same for every shape: four code tables, DHT payloads and histograms
+    assert table_area >= 9312 and table_area % 16 == 0
+
+
 def _resource_report():
     spec = importlib.util.spec_from_file_location("_stitch_build", os.path.join(ROOT, "seamless-through-breaking-rethinking-image-stitching-for-optimal-alignment_amd", "build.py"))
     build = importlib.util.module_from_spec(spec)
@@ -108,10 +136,15 @@ def _resource_report():
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_kernels_use_no_scratch_and_the_stated_lds():
     rep, text = _resource_report()
-    lds = {"jpeg_blocks_kernelILi3E": 17152, "jpeg_blocks_kernelILi1E": 8704, "jpeg_bits_kernel": 2144, "jpeg_scan_kernel": 68, "jpeg_zero_kernel": 0,
-           "jpeg_pack_kernel": 2144, "jpeg_count_kernel": 16, "jpeg_stuff_kernel": 16}
+    lds = {"jpeg_blocks_kernelILi1ELi1ELi1E": 8704, "jpeg_blocks_kernelILi3ELi1ELi1E": 6528, "jpeg_blocks_kernelILi3ELi2ELi1E": 10752,
+           "jpeg_blocks_kernelILi3ELi2ELi2E": 17152, "jpeg_hist_kernel": 4112, "jpeg_table_kernel": 1808, "jpeg_bits_kernel": 2176, "jpeg_scan_kernel": 68,
+           "jpeg_zero_kernel": 0, "jpeg_pack_kernel": 2176, "jpeg_count_kernel": 16, "jpeg_stuff_kernel": 16}
     assert len(rep) == len(lds), sorted(rep)
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    readme = readme[readme.index("## gpu_jpeg"):readme.index("## gpu_decode")]             # (the decoder's table lists the scan kernel too)
     for key, want in lds.items():
         (name, r), = [(n, r) for n, r in rep.items() if key in n]
         assert r["scratch"] == 0 and r["spill"] == 0 and r["lds"] == want and r["vgpr"] <= 64, (name, r)
+        row, = [l for l in readme.splitlines() if l.startswith("| `" + re.sub(r"ILi(\d)ELi(\d)ELi(\d)E", r"<\1, \2, \3>", key) + "`")]
+        assert row.rstrip().endswith(f"| {want} |"), row                                    # the README's kernel table states the same LDS
     assert not re.search(r"^\s*scratch_(load|store)", text, re.M)                           # no stack traffic at all

@@ -1,13 +1,12 @@
-"""The contract of the JPEG encoder's options, decided on the CPU: tests/_jpeg_opts_ref.py (what csrc/jpeg_opts.hip implements) equals Pillow's
-files byte for byte at every quality, sampling and with optimised tables; the golden cases exercise every rule (a planted defect changes a
-file); the C entry rejects bad arguments before any launch; the kernels use no scratch and the LDS the README states; and the table builder
-the kernel runs (csrc/jpeg_huff_core.h) gives the restatement's tables on 1 000 histograms under the host compiler's sanitizers."""
+"""The contract of the JPEG encoder's options, decided on the CPU: tests/_jpeg_opts_ref.py (what csrc/jpeg.hip implements behind
+`st_jpeg_encode_u8_ex`) equals Pillow's files byte for byte at every quality, sampling and with optimised tables; the golden cases exercise
+every rule (a planted defect changes a file); the C entry rejects bad arguments before any launch; and the table builder the kernel runs
+(csrc/jpeg_huff_core.h) gives the restatement's tables on 1 000 histograms under the host compiler's sanitizers."""
 import ctypes as C
 import hashlib
 import importlib.util
 import io
 import os
-import re
 import shutil
 import struct
 import subprocess
@@ -195,37 +194,6 @@ def test_unset_flags_leave_the_config_as_it_was():
     cfg = outmod.get_config(["--jpeg_quality", "95", "--jpeg_subsampling", "0", "--jpeg_optimize"])
     assert outmod.jpeg_params_of(cfg) == dict(quality=95, subsampling=0, optimize=True)
     assert outmod.jpeg_params_of(outmod.get_config(["--jpeg_subsampling", "1"])) == dict(subsampling=1)
-
-
-def _resource_report():
-    spec = importlib.util.spec_from_file_location("_stitch_build", os.path.join(PKG, "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "jpeg_opts.s")
-        subprocess.check_call(build.compile_cmd("jpeg_opts.hip", out, ["-S", "--cuda-device-only"]), stderr=subprocess.DEVNULL)
-        text = open(out).read()
-    rep = {}
-    for m in re.finditer(r"\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+)\n.*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)",
-                         text, re.S):
-        rep[m.group(2)] = dict(lds=int(m.group(1)), scratch=int(m.group(3)), vgpr=int(m.group(4)), spill=int(m.group(5)))
-    return rep, text
-
-
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
-def test_kernels_use_no_scratch_and_the_stated_lds():
-    rep, text = _resource_report()
-    lds = {"jpego_blocks_kernelILi1ELi1ELi1E": 8704, "jpego_blocks_kernelILi3ELi1ELi1E": 6528, "jpego_blocks_kernelILi3ELi2ELi1E": 10752,
-           "jpego_blocks_kernelILi3ELi2ELi2E": 17152, "jpego_hist_kernel": 4112, "jpego_table_kernel": 1808, "jpego_bits_kernel": 2176,
-           "jpego_zero_kernel": 0, "jpego_pack_kernel": 2176, "jpego_count_kernel": 16, "jpego_stuff_kernel": 16}
-    assert len(rep) == len(lds), sorted(rep)
-    readme = open(os.path.join(ROOT, "README.md")).read()
-    for key, want in lds.items():
-        (name, r), = [(n, r) for n, r in rep.items() if key in n]
-        assert r["scratch"] == 0 and r["spill"] == 0 and r["lds"] == want and r["vgpr"] <= 64, (name, r)
-        row, = [l for l in readme.splitlines() if l.startswith("| `" + re.sub(r"ILi(\d)ELi(\d)ELi(\d)E", r"<\1, \2, \3>", key) + "`")]
-        assert row.rstrip().endswith(f"| {want} |"), row                                    # the README's kernel table states the same LDS
-    assert not re.search(r"^\s*scratch_(load|store)", text, re.M)                           # no stack traffic at all
 
 
 def _histograms():

@@ -1,4 +1,4 @@
-"""csrc/jpeg_opts.hip on the GPU: `ops.jpeg_encode(quality=, subsampling=, optimize=)` writes Pillow's file byte for byte on every golden case
+"""The options of csrc/jpeg.hip on the GPU: `ops.jpeg_encode(quality=, subsampling=, optimize=)` writes Pillow's file byte for byte on every golden case
 (tests/golden/jpeg_opts_pil.npz) and on the code-length-limit case, whatever the row stride, stream, workspace history or hipGraph replay;
 `jpeg_decode` reads the files back as Pillow does; and `out.py`'s saver writes the same ten files with the options on either path."""
 import hashlib
@@ -110,6 +110,25 @@ def test_optimised_encode_row_stride_streams_and_workspace_reuse(canvas, golden)
         ops.jpeg_encode(ta, workspace=ws[:1024], **kw)
 
 
+def test_plain_encodes_ignore_the_tables_an_optimised_encode_left_in_the_workspace():
+    """One workspace of the optimised size, filled with 255: an optimised encode leaves its histograms and code tables where the plain layout
+    has its stream; the encodes of Pillow's defaults through either entry must read none of it."""
+    from stitch_amd import ops
+    H, W = 37, 53
+    rng = np.random.RandomState(11)
+    noise, other = rng.randint(0, 256, (H, W, 3)).astype(np.uint8), ref._smooth(H, W, 3, 13)
+    kw = dict(quality=95, subsampling=0, optimize=True)
+    ws = torch.full((ops.jpeg_workspace_bytes(H, W, 3, **kw),), 255, dtype=torch.uint8).cuda()
+    assert ws.numel() > ops.jpeg_workspace_bytes(H, W, 3)
+    got = ops.jpeg_bytes(*ops.jpeg_encode(torch.from_numpy(noise).cuda(), workspace=ws, **kw))
+    assert got == opts.encode(noise, **kw), _first_diff(got, opts.encode(noise, **kw))
+    want = ref.encode(other)
+    got = ops.jpeg_bytes(*ops.jpeg_encode(torch.from_numpy(other).cuda(), workspace=ws))                               # st_jpeg_encode_u8
+    assert got == want, _first_diff(got, want)
+    got = ops.jpeg_bytes(*ops.jpeg_encode(torch.from_numpy(noise).cuda(), workspace=ws, quality=75, subsampling=2))    # _ex at {75, 2, 2, 0}
+    assert got == opts.encode(noise, quality=75, subsampling=2), _first_diff(got, opts.encode(noise, quality=75, subsampling=2))
+
+
 def test_captured_optimised_encode_replays_on_other_pixels(canvas):
     from stitch_amd import ops
     a, want_a, b, want_b, kw = canvas
@@ -204,7 +223,7 @@ def test_without_jpeg_params_the_pair_writes_todays_files(pair_runner):
     gpu = run("gpu0", gpu_jpeg=True)
     none = run("gpu_none", gpu_jpeg=True, jpeg_params=None)
     assert len(pil) == 10 and gpu == pil and none == pil
-    for f, d in pil.items():                                        # Pillow's defaults: the fixed header of csrc/jpeg.hip
+    for f, d in pil.items():                                        # Pillow's defaults: the Annex K header
         ncomp = d[d.index(b"\xff\xc0") + 9]
         H, W = int.from_bytes(d[d.index(b"\xff\xc0") + 5:][:2], "big"), int.from_bytes(d[d.index(b"\xff\xc0") + 7:][:2], "big")
         assert d[:ref.HEADER_BYTES[ncomp]] == ref.header(H, W, ncomp), f

@@ -11,9 +11,17 @@
 
     python tools/bench_jpeg.py --options [--out profiles/jpeg_opts_bench.json]
 
-* the option rows (csrc/jpeg_opts.hip), in one run: per image Pillow on one thread with the same keywords, the encoder of the defaults
-  (`st_jpeg_encode_u8`), the option entry at the defaults (quality 75, 4:2:0, Annex K tables: the same bytes) and at quality 95, 4:4:4,
-  optimised tables; per kernel one traced child making 200 encodes of the 548x588 canvas at (95, 4:4:4, optimised).
+* the option rows, in one run: per image Pillow on one thread with the same keywords, `st_jpeg_encode_u8` (`defaults_old_entry`),
+  `st_jpeg_encode_u8_ex` at the defaults (`defaults_new_entry`: quality 75, 4:2:0, Annex K tables) -- the first entry calls the second, so
+  the two rows time one code path and are kept as a check of each other -- and quality 95, 4:4:4, optimised tables; per kernel one traced
+  child making 200 encodes of the 548x588 canvas at (95, 4:4:4, optimised).
+
+    python tools/bench_jpeg.py --against OTHER_ROOT [--rounds 7] [--out profiles/jpeg_unify_bench.json]
+
+* this tree's library against the one built in another checkout (OTHER_ROOT: an exported commit with its library built), per image at the
+  defaults and at (95, 4:4:4, optimised): every sample is a fresh child process that imports one of the two trees, the two alternate for
+  `--rounds` rounds; per row both versions' medians over the rounds and each version's min-max, and whether this tree's median stays within
+  the other's median plus the other's own min-max spread; then one traced child per version (200 default encodes of the 548x588 canvas).
 """
 import argparse
 import contextlib
@@ -87,19 +95,52 @@ def option_keywords(kw, u8):
     return {k: v for k, v in kw.items() if not (k == "subsampling" and u8.ndim == 2)}        # an L file has one component
 
 
-def profile_child(n, options=False):
+VERSION_ROWS = {"defaults": {}, "q95_444_optimised": OPTION_ROWS["q95_444_optimised"]}
+
+
+def version_sample(root):
+    """one child: the timings of `encode_times` for every image and row of VERSION_ROWS, with the package of the checkout at `root`"""
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--sample", "--root", root], check=True, timeout=300, stdout=subprocess.PIPE, text=True)
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def versions_bench(other_root, rounds):
+    roots = {"other": os.path.abspath(other_root), "this": ROOT}
+    samples = {v: [] for v in roots}
+    for _ in range(rounds):
+        for v, root in roots.items():
+            samples[v].append(version_sample(root))
+    res = {}
+    for name in samples["this"][0]:
+        res[name] = {}
+        for row in VERSION_ROWS:
+            entry = {}
+            for v in roots:
+                assert len({s_[name][row]["file_bytes"] for s_ in samples["this"] + samples["other"]}) == 1
+                for key in ("single_call_us", "back_to_back_us"):
+                    xs = [s_[name][row][key] for s_ in samples[v]]
+                    entry.setdefault(key, {})[v] = dict(median=float(np.median(xs)), min=min(xs), max=max(xs))
+            for key in ("single_call_us", "back_to_back_us"):
+                o, t = entry[key]["other"], entry[key]["this"]
+                entry[key]["other_spread"] = o["max"] - o["min"]
+                entry[key]["this_within_other_median_plus_spread"] = bool(t["median"] <= o["median"] + (o["max"] - o["min"]))
+            res[name][row] = entry
+    return res
+
+
+def profile_child(n, options=False, root=""):
     """per-kernel stand-alone durations (us per encode) from a traced child making n encodes of the 548x588 canvas (`options`: at
-    quality 95, 4:4:4, optimised tables)"""
+    quality 95, 4:4:4, optimised tables; `root`: with the package of another checkout)"""
     d = tempfile.mkdtemp(prefix="jpeg_prof_")
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "jpeg", "--output-format", "csv", "--",
-           sys.executable, os.path.abspath(__file__), "--inner", str(n)] + (["--options"] if options else [])
+           sys.executable, os.path.abspath(__file__), "--inner", str(n)] + (["--options"] if options else []) + (["--root", root] if root else [])
     subprocess.run(cmd, check=True, timeout=600, stdout=subprocess.DEVNULL)
     path = (glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True) or [None])[0]
     if path is None:
         raise RuntimeError(f"rocprofv3 wrote no kernel_stats.csv under {d}")
     rows = []
     for r in csv.DictReader(open(path)):
-        if "jpeg_" in r["Name"] or "jpego_" in r["Name"]:
+        if "jpeg_" in r["Name"]:
             name = re.sub(r"\(.*", "", re.sub(r"^void ", "", r["Name"]).replace("(anonymous namespace)::", ""))
             rows.append(dict(name=name, calls_per_encode=int(r["Calls"]) / n, us_per_encode=float(r["TotalDurationNs"]) / n / 1e3))
     return sorted(rows, key=lambda r: -r["us_per_encode"])
@@ -180,7 +221,11 @@ def loop_bench(pairs, rounds, parent_path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
-    ap.add_argument("--options", action="store_true", help="the option rows of csrc/jpeg_opts.hip -> profiles/jpeg_opts_bench.json")
+    ap.add_argument("--options", action="store_true", help="the option rows -> profiles/jpeg_opts_bench.json")
+    ap.add_argument("--against", default="", help="another checkout with its library built -> profiles/jpeg_unify_bench.json")
+    ap.add_argument("--against-label", default="", help="how the result file names the other checkout (default: its path)")
+    ap.add_argument("--sample", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--root", default="", help=argparse.SUPPRESS)
     ap.add_argument("--parent-out", default="")
     ap.add_argument("--pairs", type=int, default=48)
     ap.add_argument("--rounds", type=int, default=5)
@@ -188,8 +233,33 @@ def main():
     ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--inner", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "jpeg_opts_bench.json" if a.options else "jpeg_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "jpeg_unify_bench.json" if a.against else "jpeg_opts_bench.json" if a.options else "jpeg_bench.json")
     imgs = images()
+    if a.root:                                             # a child of --against: the package of the checkout at a.root
+        sys.path.insert(0, a.root)
+        from stitch_amd import _lib
+        assert os.path.dirname(os.path.dirname(_lib.LIB_PATH)) == a.root, _lib.LIB_PATH
+    if a.sample:
+        out = {}
+        for name, u8 in imgs.items():
+            out[name] = {}
+            for row, kw in VERSION_ROWS.items():
+                single, b2b, nbytes = encode_times(u8, **option_keywords(kw, u8))
+                out[name][row] = dict(single_call_us=single * 1e3, back_to_back_us=b2b * 1e3, file_bytes=nbytes)
+        print(json.dumps(out))
+        return
+    if a.against:
+        res = {"what": "ops.jpeg_encode of this tree against the library of another checkout, one MI355X: HIP-event median of 50 single calls and "
+                       "50 calls back to back per sample, every sample a fresh process, the two versions alternating",
+               "other": a.against_label or a.against, "rounds": a.rounds, "per_image": versions_bench(a.against, a.rounds)}
+        res["kernels_rgb_548x588_defaults"] = dict(source=f"rocprofv3 --kernel-trace --stats, {a.launches} encodes per version, each traced child a run of its own",
+                                                   other=profile_child(a.launches, root=os.path.abspath(a.against)), this=profile_child(a.launches))
+        res["every_row_within_margin"] = all(e[k]["this_within_other_median_plus_spread"] for im in res["per_image"].values() for e in im.values()
+                                             for k in ("single_call_us", "back_to_back_us"))
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     if a.inner:                                            # the traced child
         import torch
         from stitch_amd import ops
@@ -199,8 +269,8 @@ def main():
         torch.cuda.synchronize()
         return
     if a.options:
-        res = {"what": "GPU JPEG encoder options (csrc/jpeg_opts.hip) vs Pillow (one thread, same keywords) and vs the encoder of the defaults "
-                       "(csrc/jpeg.hip), same run, one MI355X"}
+        res = {"what": "GPU JPEG encoder (csrc/jpeg.hip) with options vs Pillow (one thread, same keywords), same run, one MI355X; defaults_old_entry "
+                       "(st_jpeg_encode_u8) and defaults_new_entry (st_jpeg_encode_u8_ex at the defaults) are one code path, timed twice"}
         rows = profile_child(a.launches, options=True)
         res["kernels_rgb_548x588_q95_444_optimised"] = dict(source=f"rocprofv3 --kernel-trace --stats, {a.launches} encodes (stand-alone kernel durations)", rows=rows,
                                                             us_per_encode_total=sum(r["us_per_encode"] for r in rows),

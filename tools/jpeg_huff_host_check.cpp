@@ -1,4 +1,4 @@
-// Runs the table builder of csrc/jpeg_opts.hip's table kernel (csrc/jpeg_huff_core.h, plain C++) on the host, stand-alone, so that the host
+// Runs the table builder of csrc/jpeg.hip's table kernel (csrc/jpeg_huff_core.h, plain C++) on the host, stand-alone, so that the host
 // compiler's sanitizers see it:   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I <pkg>/csrc tools/jpeg_huff_host_check.cpp
 //
 //   jpeg_huff_host_check <cases.bin> <out.bin>
