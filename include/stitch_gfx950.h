@@ -136,6 +136,14 @@ int st_set_gemm_observer(void* callback, void* user);
  * Used by tools/gemm_shapes_csv.py to label every launch of a step (profiles/r2_gemm_shapes.csv). */
 int st_gemm_last_plan(int32_t* plan4);
 
+/* The dispatch decision alone, from the functions st_conv_gemm / st_conv_gemm_pair run themselves.  pair_with == NULL: returns what
+ * st_conv_gemm(desc) returns before it launches anything (0, or 1001 for a descriptor it rejects) and, on 0, writes to plan4 the four values
+ * st_gemm_last_plan reports after that call (for a descriptor whose rows run in chunks: those of its last chunk).  pair_with != NULL: the same for
+ * st_conv_gemm_pair(desc, pair_with).  Host arithmetic only: no launch, no HIP call, none of the descriptor's pointers is followed (their
+ * alignment is read), and the calling thread's last plan stays as it is.  For callers that want to know the kernel before they launch
+ * and for tests/test_gemm_plan_cpu.py, which pins the dispatch table without a GPU. */
+int st_gemm_plan(const st_gemm_desc* desc, const st_gemm_desc* pair_with, int32_t* plan4);
+
 /* sizeof(st_gemm_desc) as compiled into the library (binding self-check; returns the size). */
 int st_abi_gemm_desc_size(void);
 

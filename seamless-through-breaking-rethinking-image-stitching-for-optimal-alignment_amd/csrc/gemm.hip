@@ -10,8 +10,9 @@
 // both operands so the contraction pairs up without any transposition.
 //
 // This file is the fp32 family and the dispatcher; the exact-split bf16 kernels (gemm_split3.h) are launched from gemm_split3.hip, the
-// C = 128 row kernels (rowchain128 / rowmlp128, mlp_split3.h) from gemm_rows.hip; what the three share is gemm_common.h.
-// Kernels in this file (dispatch: conv_gemm_launch):
+// C = 128 row kernels (rowchain128 / rowmlp128, mlp_split3.h) from gemm_rows.hip; what the three share -- the descriptor checks among it -- is gemm_common.h.
+// Dispatch (conv_gemm_launch): check_f32 -> for_each_row_chunk if the rows are beyond one launch -> plan_f32, a pure function -> launch_f32, a switch on
+// the plan; st_gemm_plan runs the first three alone.  Kernels in this file:
 //   conv_gemm_dma_kernel   Cin % 32 == 0 (the default): global -> LDS DMA ring, VALU-free K loop, optional persistent walk
 //                          over M tiles; tiles 64x64 / 128x64 / 128x32
 //   conv_gemm_kernel       any Cin % 4 == 0 (or scalar gather otherwise): register-staged, [rows][BK+4] padded LDS tiles
@@ -905,26 +906,24 @@ static int launch_cfg(const st_gemm_desc& d, bool vec, hipStream_t s) {
     return ST_OK;
 }
 
+static const int f32_bms[6] = {0, 128, 128, 64, 128, 64}, f32_bns[6] = {0, 128, 64, 64, 32, 128};      // tile by tile_cfg (register-staged 1-4) or tile_cfg - 10 (LDS-DMA 12-15)
+#define DMA_STAGES 4            // ring depth of every LDS-DMA instantiation launch_f32 uses
+// 512 workgroup slots = both of a CU's slots for the LDS-DMA kernel's footprint.  One slot per CU (a workgroup walking >= 2 M tiles, the second slot
+// left to another stream's kernel) was measured in round 5 and not adopted: faster on uniform GEMMs alone, slower in the product (bench.py,
+// 3 pairs in flight, same box A/B/A: 82.66 / 82.58 -> 81.09 / 80.67 pairs/s; one pair in flight 72.4 -> 69.0).
+#define DMA_SLOTS 512
 template <int WM, int WN, int TM, int TN, int STAGES>
-static int launch_dma(const st_gemm_desc& d, hipStream_t s) {
+static int launch_dma(const st_gemm_desc& d, bool persist, hipStream_t s) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
     const int batch = d.batch > 0 ? d.batch : 1;
     const size_t lds = (size_t)STAGES * (BM + BN) * 32 * sizeof(float);
-    // persistent walk over M tiles: plain matrices whose K is a whole number of ring turns and whose grid would
-    // otherwise be many short workgroups (two resident per CU with this LDS footprint)
-    const bool plain = d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0 && d.H * d.W == d.M &&
-                       d.Ho * d.Wo == d.M;
-    // 512 workgroup slots = both of a CU's slots for this LDS footprint.  One slot per CU (a workgroup walking >= 2 M tiles, the second slot
-    // left to another stream's kernel) was measured in round 5 and not adopted: faster on uniform GEMMs alone, slower in the product (bench.py,
-    // 3 pairs in flight, same box A/B/A: 82.66 / 82.58 -> 81.09 / 80.67 pairs/s; one pair in flight 72.4 -> 69.0).
-    const int slots = 512 / batch;
-    if (STAGES == 4 && plain && !d.a2 && d.split_k <= 1 && (d.K / 32) % STAGES == 0 && (long)ntm * ntn > slots && ntn <= slots && slots > 0) {
+    const int slots = DMA_SLOTS / batch;
+    if (persist) {                                  // persistent walk over M tiles (plan_f32)
         int G = slots / ntn;
         if (G > ntm) G = ntm;
         auto k = d.c_t ? conv_gemm_dma_kernel<WM, WN, TM, TN, STAGES, true, true> : conv_gemm_dma_kernel<WM, WN, TM, TN, STAGES, true>;
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        g_last_plan[3] = 1;
         hipLaunchKernelGGL(k, dim3(G * ntn, 1, batch), dim3(256), lds, s, d);
         ST_CHECK_LAUNCH();
         return ST_OK;
@@ -941,18 +940,25 @@ static int launch_dma(const st_gemm_desc& d, hipStream_t s) {
 // row-streaming kernel: S column slices of `cps` 32-column chunks, G workgroups (512 threads, one per CU) per slice.
 // S is the smallest power of two that (a) keeps a slice within `max_cps` chunks and (b) yields at least one (row block,
 // slice) item per wave of the chip; G * S = 256, G a multiple of 8 (one run of workgroups per XCD).
-template <int KC>
-static int launch_rowstream(const st_gemm_desc& d, int max_cps, hipStream_t s) {
-    const int nchunks = (d.N + 31) / 32;
-    const int nblk = (d.M + 31) / 32;
+// (the slicing is host arithmetic only: plan_f32 runs it to reject what no slicing fits, the launcher to size its grid)
+static int rowstream_slices(const st_gemm_desc& d, int KC, int& cps, int& S) {
+    const int nchunks = (d.N + 31) / 32, nblk = (d.M + 31) / 32;
     const int lds_cap = (160 * 1024 - 1024) / (32 * (32 * KC + 4) * 4);
-    if (max_cps > lds_cap) max_cps = lds_cap;
-    int S = 1;
+    const int max_cps = lds_cap < 8 ? lds_cap : 8;      // 8-chunk slices (4-chunk ones, which would let a 64-KiB GEMM workgroup co-reside, measured 0.3 % slower with 3 pairs in flight)
+    S = 1;
     while (S < 32 && ((nchunks + S - 1) / S > max_cps || ((long)nblk * S < 2048 && 2 * S <= nchunks))) S *= 2;
-    const int cps = (nchunks + S - 1) / S;
+    cps = (nchunks + S - 1) / S;
     if (cps > lds_cap) return ST_EINVAL;
-    S = (nchunks + cps - 1) / cps;                 // drop empty slices ...
-    int G = (256 / S) / 8 * 8;                      // ... (G * S <= 256)
+    S = (nchunks + cps - 1) / cps;                 // drop empty slices
+    return ST_OK;
+}
+
+template <int KC>
+static int launch_rowstream(const st_gemm_desc& d, hipStream_t s) {
+    const int nblk = (d.M + 31) / 32;
+    int cps, S;
+    if (rowstream_slices(d, KC, cps, S)) return ST_EINVAL;
+    int G = (256 / S) / 8 * 8;                      // (G * S <= 256)
     if (G < 8) G = 8;
     const int need = ((nblk + 7) / 8 + 7) / 8 * 8;
     if (G > need) G = need;
@@ -964,133 +970,90 @@ static int launch_rowstream(const st_gemm_desc& d, int max_cps, hipStream_t s) {
     return ST_OK;
 }
 
-static int conv_gemm_launch(const st_gemm_desc* desc, void* stream) {
-    if (!c_planes_ok(*desc)) return ST_EINVAL;
-    if (desc->split3) return conv_gemm_split3_launch(desc, stream);
-    st_gemm_desc d = *desc;
-    if (!d.a || !d.w || !d.c || d.M <= 0 || d.N <= 0 || d.K <= 0) return ST_EINVAL;
-    if (d.kh <= 0 || d.kw <= 0 || d.K != d.kh * d.kw * d.Cin) return ST_EINVAL;
-    if (d.Ho <= 0 || d.Wo <= 0 || d.M % (d.Ho * d.Wo)) return ST_EINVAL;
-    if (d.epi != ST_EPI_STORE && !d.aux1) return ST_EINVAL;
-    if (d.epi == ST_EPI_GRU && !d.aux2) return ST_EINVAL;
-    if (d.epi == ST_EPI_ZR && (!d.c2 || (d.N & 1))) return ST_EINVAL;
-    if (d.reserved0 != 0 || d.reserved1 != 0 || d.reserved2 != 0 || d.reserved3 != 0) return ST_EINVAL;
-    if (d.c_t && (d.epi != ST_EPI_STORE || (d.M & 3) || (d.ld_ct & 3) || d.ld_ct < d.M || ((uintptr_t)d.c_t & 15) || d.split_k > 1 || d.a_ln ||
-                  (int64_t)d.N * d.ld_ct * 4 >= ((int64_t)1 << 31)))
-        return ST_EINVAL;
-    if (d.a2 && (d.a2_channels <= 0 || d.a2_channels % 32 || d.a2_channels > d.Cin || d.batch > 1 || ((uintptr_t)d.a2 & 15))) return ST_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    // byte extents of one batch slice of A and W for the buffer descriptors (must stay below 2 GiB so the
-    // out-of-range sentinel offset is always past num_records)
-    {
-        const bool plain_mat = d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0 && (int64_t)d.H * d.W == d.M &&
-                               (int64_t)d.Ho * d.Wo == d.M;          // a matrix: every row is its own "image"
-        const int64_t hw = plain_mat ? 1 : (int64_t)d.Ho * d.Wo, nimg = d.M / hw, img_rows = plain_mat ? 1 : (int64_t)d.H * d.W;
-        const int64_t ab = ((nimg * img_rows - 1) * d.ldx + d.Cin) * 4, wb = ((int64_t)(d.N - 1) * d.ldw + d.K) * 4;
-        if (wb >= (int64_t)ST_OOB) return ST_EINVAL;
-        // the epilogue addresses C / aux operands with 32-bit buffer offsets (first row of a lane + SGPR row step)
-        const int64_t lim = (int64_t)1 << 31;
-        int64_t ldmax = d.ldc > d.N ? d.ldc : d.N;
-        if (d.aux0 && d.ld_aux0 > ldmax) ldmax = d.ld_aux0;
-        if (d.aux1 && d.ld_aux1 > ldmax) ldmax = d.ld_aux1;
-        if (d.aux2 && d.ld_aux2 > ldmax) ldmax = d.ld_aux2;
-        if (d.c2 && d.ldc2 > ldmax) ldmax = d.ldc2;
-        if (ab >= (int64_t)ST_OOB || ((int64_t)d.M + 256) * ldmax * 4 >= lim) {
-            // Larger than the 32-bit offsets reach (whole-batch PatchEmbed maps at B >= 4, ...): run the rows in chunks.
-            // A chunk is a whole number of images (convs) and of aux0 mapping periods, so every operand just shifts its base.
-            if ((d.batch > 1) || d.split_k > 1 || d.c_t || d.c_planes) return ST_EINVAL;
-            const int64_t div = d.aux0_row_div > 1 ? d.aux0_row_div : 1, mod = d.aux0_row_mod > 0 ? d.aux0_row_mod : 1;
-            int64_t unit = hw;                                           // rows per indivisible unit
-            {
-                const int64_t period = div * mod;                       // lcm(unit, period) via gcd
-                int64_t a = unit, b = period;
-                while (b) { const int64_t t = a % b; a = b; b = t; }
-                unit = unit / a * period;
-            }
-            const int64_t in_rows_per_unit = unit / hw * img_rows;
-            int64_t per_out = (lim / 4 / ldmax - 256) / unit, per_in = ((int64_t)ST_OOB / 4 / d.ldx) / in_rows_per_unit;
-            int64_t units = per_out < per_in ? per_out : per_in;
-            // strictly inside both limits (the same tests as above, on the chunk)
-            while (units > 0 && (((units * in_rows_per_unit - 1) * d.ldx + d.Cin) * 4 >= (int64_t)ST_OOB ||
-                                 (units * unit + 256) * ldmax * 4 >= lim))
-                --units;
-            if (units < 1 || d.M % unit || units * unit >= d.M) return ST_EINVAL;      // (a chunk must be a strict part)
-            {
-                const int64_t total = d.M / unit, nchunks = (total + units - 1) / units;  // equal-sized chunks
-                units = (total + nchunks - 1) / nchunks;
-            }
-            const int64_t chunk = units * unit;
-            for (int64_t m0 = 0; m0 < d.M; m0 += chunk) {
-                st_gemm_desc c = *desc;
-                c.M = (int32_t)((d.M - m0) < chunk ? (d.M - m0) : chunk);
-                c.a = d.a + m0 / hw * img_rows * d.ldx;
-                if (d.a2) c.a2 = d.a2 + m0 / hw * img_rows * d.ldx;
-                c.c = d.c + m0 * d.ldc;
-                if (d.c2) c.c2 = d.c2 + m0 * d.ldc2;
-                if (d.aux1) c.aux1 = d.aux1 + m0 * d.ld_aux1;
-                if (d.aux2) c.aux2 = d.aux2 + m0 * d.ld_aux2;
-                if (d.aux0 && d.aux0_row_mod <= 0) c.aux0 = d.aux0 + m0 / div * d.ld_aux0;   // with a modulus the chunk starts a period
-                if (plain_mat) { c.H = 1; c.W = c.M; c.Ho = 1; c.Wo = c.M; }
-                const int rc = conv_gemm_launch(&c, stream);
-                if (rc) return rc;
-            }
-            return ST_OK;
-        }
-        d.a_bytes = (uint32_t)ab; d.w_bytes = (uint32_t)wb;
+// ---- fp32 dispatch: check, chunk if needed, plan, launch -- the first three without a HIP call, so st_gemm_plan answers from the same code ----
+// The fp32 path's own rules on top of desc_common_check.  `chunked`: the rows must run in pieces (for_each_row_chunk).
+static int check_f32(const st_gemm_desc& d, bool& chunked) {
+    // a_ln belongs to the row-streaming kernel, c_t to the LDS-DMA kernels (plan_f32 would refuse the combination as well; the rule stays where it was)
+    if (!desc_common_check(d) || (d.c_t && d.a_ln)) return ST_EINVAL;
+    const f32_extent e = desc_f32_extent(d);
+    if (e.w_bytes >= (int64_t)ST_OOB) return ST_EINVAL;         // (W is never cut)
+    chunked = e.a_bytes >= (int64_t)ST_OOB || !desc_epi_reach_ok(d);
+    return ST_OK;
+}
+
+// Larger than the 32-bit offsets reach (whole-batch PatchEmbed maps at B >= 4, ...): run the rows in chunks.  A chunk is a whole number of images (convs)
+// and of aux0 mapping periods, so every operand just shifts its base.  piece(chunk descriptor) is called in row order; a non-zero return ends the walk.
+template <class F>
+static int for_each_row_chunk(const st_gemm_desc& d, F&& piece) {
+    if ((d.batch > 1) || d.split_k > 1 || d.c_t || d.c_planes) return ST_EINVAL;
+    const bool plain_mat = desc_is_plain_matrix(d);
+    const f32_extent e = desc_f32_extent(d);
+    const int64_t hw = e.hw, img_rows = e.img_rows, lim = (int64_t)1 << 31, ldmax = desc_epi_ldmax(d);
+    const int64_t div = d.aux0_row_div > 1 ? d.aux0_row_div : 1, mod = d.aux0_row_mod > 0 ? d.aux0_row_mod : 1;
+    int64_t a = hw, b = div * mod;                               // rows per indivisible unit: lcm(hw, aux0 period) via gcd
+    while (b) { const int64_t t = a % b; a = b; b = t; }
+    const int64_t unit = hw / a * (div * mod);
+    const int64_t in_rows_per_unit = unit / hw * img_rows;
+    int64_t per_out = (lim / 4 / ldmax - 256) / unit, per_in = ((int64_t)ST_OOB / 4 / d.ldx) / in_rows_per_unit;
+    int64_t units = per_out < per_in ? per_out : per_in;
+    // strictly inside both limits (check_f32's tests, on the chunk)
+    while (units > 0 && (((units * in_rows_per_unit - 1) * d.ldx + d.Cin) * 4 >= (int64_t)ST_OOB || (units * unit + 256) * ldmax * 4 >= lim)) --units;
+    if (units < 1 || d.M % unit || units * unit >= d.M) return ST_EINVAL;      // (a chunk must be a strict part)
+    const int64_t total = d.M / unit, nchunks = (total + units - 1) / units;      // equal-sized chunks
+    const int64_t chunk = (total + nchunks - 1) / nchunks * unit;
+    for (int64_t m0 = 0; m0 < d.M; m0 += chunk) {
+        st_gemm_desc c = d;
+        c.M = (int32_t)((d.M - m0) < chunk ? (d.M - m0) : chunk);
+        c.a = d.a + m0 / hw * img_rows * d.ldx;
+        if (d.a2) c.a2 = d.a2 + m0 / hw * img_rows * d.ldx;
+        c.c = d.c + m0 * d.ldc;
+        if (d.c2) c.c2 = d.c2 + m0 * d.ldc2;
+        if (d.aux1) c.aux1 = d.aux1 + m0 * d.ld_aux1;
+        if (d.aux2) c.aux2 = d.aux2 + m0 * d.ld_aux2;
+        if (d.aux0 && d.aux0_row_mod <= 0) c.aux0 = d.aux0 + m0 / div * d.ld_aux0;   // with a modulus the chunk starts a period
+        if (plain_mat) { c.H = 1; c.W = c.M; c.Ho = 1; c.Wo = c.M; }
+        const int rc = piece(c);
+        if (rc) return rc;
     }
-    const bool aligned = ((uintptr_t)d.a % 16 == 0) && ((uintptr_t)d.w % 16 == 0) && (d.ldx % 4 == 0) &&
-                         (d.ldw % 4 == 0) && (d.Cin % 4 == 0) &&
+    return ST_OK;
+}
+
+// What a descriptor that passed check_f32 in one piece launches: kernel family, tile, split-K, persistent walk.  Every threshold is a measured choice
+// (the comments say where); tests/test_gemm_plan_cpu.py pins both sides of each at the workload's shapes.
+static int plan_f32(const st_gemm_desc& d, gemm_plan& p) {
+    const f32_extent e = desc_f32_extent(d);
+    p = gemm_plan{0, 0, 0, 0, false, false, (uint32_t)e.a_bytes, (uint32_t)e.w_bytes};
+    auto chosen = [&p](int family, int tile, int split, int walk) { p.family = family; p.tile_cfg = tile; p.split = split; p.persistent = walk; return ST_OK; };
+    const bool aligned = ((uintptr_t)d.a % 16 == 0) && ((uintptr_t)d.w % 16 == 0) && (d.ldx % 4 == 0) && (d.ldw % 4 == 0) && (d.Cin % 4 == 0) &&
                          (d.batch_stride_a % 4 == 0) && (d.batch_stride_w % 4 == 0);
     const int batch = d.batch > 0 ? d.batch : 1;
-    if (d.M <= 8 && d.kh == 1 && d.kw == 1 && aligned && batch == 1 && d.epi == ST_EPI_STORE && !d.aux0 && d.H * d.W == d.M && !d.a2 && !d.c_t && !d.c_planes) {
-        st_plan_set(0, 0, 1, 0);
-        hipLaunchKernelGGL(skinny_gemm_kernel<8>, dim3((d.N * 64 + 255) / 256), dim3(256), 0, s, d);
-        ST_CHECK_LAUNCH();
-        return ST_OK;
-    }
+    if (d.M <= 8 && d.kh == 1 && d.kw == 1 && aligned && batch == 1 && d.epi == ST_EPI_STORE && !d.aux0 && d.H * d.W == d.M && !d.a2 && !d.c_t && !d.c_planes)
+        return chosen(0, 0, 1, 0);
     if (d.N <= 4 && aligned && batch == 1 && d.epi != ST_EPI_ZR && d.M >= 1024 && d.tile_cfg == 0 && d.split_k <= 1 && !d.a2 && !d.c_t && !d.c_planes) {
-        st_plan_set(1, 0, 1, 0);
-        if (d.N <= 2 && d.Cin == 256 && d.kh == 3 && d.kw == 3 && d.sh == 1 && d.sw == 1 && d.ph == 1 && d.pw == 1 && d.dh <= 1 && d.dw <= 1 &&
-            d.Ho == d.H && d.Wo == d.W) {
-            const int waves = (d.M / (d.H * d.W)) * d.H * ((d.W + 7) / 8);
-            hipLaunchKernelGGL(narrow_conv3x3_kernel<2>, dim3((waves + 3) / 4), dim3(256), 0, s, d);
-            ST_CHECK_LAUNCH();
-            return ST_OK;
-        }
-        hipLaunchKernelGGL(narrow_conv_kernel<4>, dim3((d.M + 3) / 4), dim3(256), 0, s, d);
-        ST_CHECK_LAUNCH();
-        return ST_OK;
+        p.narrow3x3 = d.N <= 2 && d.Cin == 256 && d.kh == 3 && d.kw == 3 && d.sh == 1 && d.sw == 1 && d.ph == 1 && d.pw == 1 && d.dh <= 1 && d.dw <= 1 && d.Ho == d.H && d.Wo == d.W;
+        return chosen(1, 0, 1, 0);
     }
-    {
-        // row-streaming kernel (weights resident in LDS, A rows in registers): plain matrices with K = 64 / 128 and enough
-        // 32-row blocks to give every wave of the chip at least one
-        const bool plain = d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0 && (int64_t)d.H * d.W == d.M;
-        const bool map_ok = (d.aux0_row_div <= 1 && (d.aux0_row_mod <= 0 || d.aux0_row_mod % 32 == 0)) ||
-                            (d.aux0_row_div == 8 && d.aux0_row_mod <= 0) || !d.aux0;
-        const bool rs_ok = plain && aligned && batch == 1 && !d.a2 && !d.c_t && !d.c_planes && d.split_k <= 1 && (d.K == 64 || d.K == 128) &&
-                           d.epi != ST_EPI_ZR && d.epi != ST_EPI_GRU && map_ok;
-        // measured on MI355X, in the pipeline and stand-alone (tools/rowstream_bench.py): ahead of the LDS-DMA kernel for K = 64,
-        // for M >= 262144 and for N >= 384; behind it by ~2 us per launch at M <= 65536, N = 128 (one block per wave: all
-        // start-up); K = 256 (no room for the prefetch) was 10-30 % slower everywhere and is not instantiated
-        const bool rs_want = d.tile_cfg == 20 || (d.tile_cfg == 0 && d.M >= 16384 &&
-                                                  (d.K == 64 || d.M >= 262144 || (d.N >= 384 && d.M >= 32768)));
-        if (d.a_ln && !(rs_ok && (d.tile_cfg == 0 || d.tile_cfg == 20))) return ST_EINVAL;
-        if (rs_ok && (rs_want || d.a_ln)) {
-            st_plan_set(4, 20, 1, 1);
-            return d.K == 64 ? launch_rowstream<2>(d, 8, s) : launch_rowstream<4>(d, 8, s);      // 8-chunk slices (4-chunk ones, which would let a
-            //                                                       64-KiB GEMM workgroup co-reside, measured 0.3 % slower with 3 pairs in flight)
-        }
-        if (d.tile_cfg >= 20) return ST_EINVAL;
+    // row-streaming kernel (weights resident in LDS, A rows in registers): plain matrices with K = 64 / 128 and enough
+    // 32-row blocks to give every wave of the chip at least one
+    const bool map_ok = (d.aux0_row_div <= 1 && (d.aux0_row_mod <= 0 || d.aux0_row_mod % 32 == 0)) || (d.aux0_row_div == 8 && d.aux0_row_mod <= 0) || !d.aux0;
+    const bool rs_ok = desc_is_plain_input(d) && aligned && batch == 1 && !d.a2 && !d.c_t && !d.c_planes && d.split_k <= 1 && (d.K == 64 || d.K == 128) &&
+                       d.epi != ST_EPI_ZR && d.epi != ST_EPI_GRU && map_ok;
+    // measured on MI355X, in the pipeline and stand-alone (tools/rowstream_bench.py): ahead of the LDS-DMA kernel for K = 64,
+    // for M >= 262144 and for N >= 384; behind it by ~2 us per launch at M <= 65536, N = 128 (one block per wave: all
+    // start-up); K = 256 (no room for the prefetch) was 10-30 % slower everywhere and is not instantiated
+    const bool rs_want = d.tile_cfg == 20 || (d.tile_cfg == 0 && d.M >= 16384 && (d.K == 64 || d.M >= 262144 || (d.N >= 384 && d.M >= 32768)));
+    if (d.a_ln && !(rs_ok && (d.tile_cfg == 0 || d.tile_cfg == 20))) return ST_EINVAL;
+    if (rs_ok && (rs_want || d.a_ln)) {
+        int cps, S;
+        return rowstream_slices(d, d.K == 64 ? 2 : 4, cps, S) ? ST_EINVAL : chosen(4, 20, 1, 1);
     }
-    // tile choice: largest tile that still yields >= ~1.5 waves of workgroups over the 256 CUs
-    auto nwg = [&](int bm, int bn) { return (long)((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn) * batch; };
+    if (d.tile_cfg >= 20) return ST_EINVAL;
     int cfg = d.tile_cfg;
     // the LDS-DMA pipelined kernel needs whole 32-channel K steps inside one tap
     const bool dma_ok = aligned && d.Cin % 32 == 0;
     if (cfg == 0) {
         // measured on MI355X (tools/tile_sweep.py, tools/dma_sweep.py): the 64x64 tile wins for every short-K /
         // mid-size shape of this path (more resident workgroups); 128-wide tiles stay selectable through tile_cfg.
-        const bool plain = d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0 && d.H * d.W == d.M;
         // K >= 128 (four K steps): the DMA ring already beats the register-staged kernel by 25-35 % per launch
         // (graph replay, tools/shortk_bench.py: 8192x256x160 14.4 -> 10.6 us, 8192x128x192 10.9 -> 7.6, 4096x128x128 7.8 -> 5.9)
         const bool dma = dma_ok && d.K >= 128;
@@ -1100,12 +1063,14 @@ static int conv_gemm_launch(const st_gemm_desc* desc, void* stream) {
         // measured it equal on the real z|r launches (67.0 / 65.3 vs 66.6 / 64.7 us, tools/tile15_bench.py, bit-identical) and 0.8 % slower
         // in the pipeline, 82.7 -> 82.0 pairs/s; it wins 2-5 % only on plain N = 256 long-K convs, which the path does not have)
     }
+    if (!(cfg >= 1 && cfg <= 4) && !(cfg >= 12 && cfg <= 15)) return ST_EINVAL;
     if (cfg > 10 && !dma_ok) return ST_EINVAL;
     if ((d.a2 || d.c_t) && cfg <= 10) return ST_EINVAL;        // second A source / transposed copy: LDS-DMA kernels only
     // split-K: a launch that cannot fill the 256 CUs (M = 4096-pixel maps x 64..256 channels) is cut
     // along K into slabs reduced by a second tiny kernel (deterministic order; no atomics).
-    static const int bms[6] = {0, 128, 128, 64, 128, 64}, bns[6] = {0, 128, 64, 64, 32, 128};
-    const long tiles = cfg > 10 ? nwg(bms[cfg - 10], bns[cfg - 10]) : nwg(bms[cfg], bns[cfg]);
+    const int bm = f32_bms[cfg > 10 ? cfg - 10 : cfg], bn = f32_bns[cfg > 10 ? cfg - 10 : cfg];
+    const int ntm = (d.M + bm - 1) / bm, ntn = (d.N + bn - 1) / bn;
+    const long tiles = (long)ntm * ntn * batch;
     int split = d.split_k;
     if (split == 0) {
         split = 1;
@@ -1125,76 +1090,92 @@ static int conv_gemm_launch(const st_gemm_desc* desc, void* stream) {
         }
     }
     if (split > 1 && (batch != 1 || !d.workspace || (int64_t)split * d.M * d.N > d.workspace_floats)) return ST_EINVAL;
-    d.split_k = split;
-    st_plan_set(cfg > 10 ? 3 : 2, cfg, split, 0);
-    if (cfg == 12) return launch_dma<2, 2, 2, 1, 4>(d, s);
-    // (a 3-deep ring -- 48 KB, three workgroups per CU -- is correct with this body (the K-block fold is independent of the ring depth) and
-    // was measured: kernels of different pairs overlap better (3-in-flight / 1-in-flight 1.18 instead of 1.135) but a tile then has ONE K
-    // step to land and every kernel slows down: 71.9 -> 67.9 pairs/s with one pair in flight, 81.6 -> 80.2 with three; a 5-deep ring
-    // -- 80 KB, four tiles ahead -- for the convs and K >= 1024, round 4: 82.65 -> 81.5 / 72.5 -> 71.6: two workgroups no longer share a CU)
-    if (cfg == 13) return launch_dma<2, 2, 1, 1, 4>(d, s);
-    if (cfg == 15) return launch_dma<2, 2, 1, 2, 4>(d, s);      // 64x128: selectable only (see the tile choice above)
-    if (cfg == 14) return launch_dma<4, 1, 1, 1, 4>(d, s);      // (80 KB of LDS; a 3-deep ring, 60 KB, measured neutral: PatchEmbed's 6x3 conv is not occupancy-bound)
-    switch (cfg) {
-        case 1: return launch_cfg<2, 2, 2, 2>(d, aligned, s);
-        case 2: return launch_cfg<2, 2, 2, 1>(d, aligned, s);
-        case 3: return launch_cfg<2, 2, 1, 1>(d, aligned, s);
-        case 4: return launch_cfg<4, 1, 1, 1>(d, aligned, s);
+    p.vec = aligned;
+    // persistent walk over M tiles (LDS-DMA kernels): plain matrices whose K is a whole number of ring turns and whose grid would
+    // otherwise be many short workgroups (two resident per CU with this LDS footprint)
+    const int slots = DMA_SLOTS / batch;
+    const bool walk = cfg > 10 && desc_is_plain_matrix(d) && !d.a2 && split <= 1 && (d.K / 32) % DMA_STAGES == 0 && (long)ntm * ntn > slots && ntn <= slots && slots > 0;
+    return chosen(cfg > 10 ? 3 : 2, cfg, split, walk);
+}
+
+static int launch_f32(st_gemm_desc d, const gemm_plan& p, hipStream_t s) {
+    d.a_bytes = p.a_bytes; d.w_bytes = p.w_bytes;
+    if (p.family == 4) return d.K == 64 ? launch_rowstream<2>(d, s) : launch_rowstream<4>(d, s);
+    if (p.family <= 1) {
+        if (p.family == 0) hipLaunchKernelGGL(skinny_gemm_kernel<8>, dim3((d.N * 64 + 255) / 256), dim3(256), 0, s, d);
+        else if (p.narrow3x3) {
+            const int waves = (d.M / (d.H * d.W)) * d.H * ((d.W + 7) / 8);
+            hipLaunchKernelGGL(narrow_conv3x3_kernel<2>, dim3((waves + 3) / 4), dim3(256), 0, s, d);
+        } else hipLaunchKernelGGL(narrow_conv_kernel<4>, dim3((d.M + 3) / 4), dim3(256), 0, s, d);
+        ST_CHECK_LAUNCH();
+        return ST_OK;
+    }
+    d.split_k = p.split;
+    switch (p.tile_cfg) {
+        case 12: return launch_dma<2, 2, 2, 1, 4>(d, p.persistent, s);
+        // (a 3-deep ring -- 48 KB, three workgroups per CU -- is correct with this body (the K-block fold is independent of the ring depth) and
+        // was measured: kernels of different pairs overlap better (3-in-flight / 1-in-flight 1.18 instead of 1.135) but a tile then has ONE K
+        // step to land and every kernel slows down: 71.9 -> 67.9 pairs/s with one pair in flight, 81.6 -> 80.2 with three; a 5-deep ring
+        // -- 80 KB, four tiles ahead -- for the convs and K >= 1024, round 4: 82.65 -> 81.5 / 72.5 -> 71.6: two workgroups no longer share a CU)
+        case 13: return launch_dma<2, 2, 1, 1, 4>(d, p.persistent, s);
+        case 15: return launch_dma<2, 2, 1, 2, 4>(d, p.persistent, s);      // 64x128: selectable only (see the tile choice in plan_f32)
+        case 14: return launch_dma<4, 1, 1, 1, 4>(d, p.persistent, s);      // (80 KB of LDS; a 3-deep ring, 60 KB, measured neutral: PatchEmbed's 6x3 conv is not occupancy-bound)
+        case 1: return launch_cfg<2, 2, 2, 2>(d, p.vec, s);
+        case 2: return launch_cfg<2, 2, 2, 1>(d, p.vec, s);
+        case 3: return launch_cfg<2, 2, 1, 1>(d, p.vec, s);
+        case 4: return launch_cfg<4, 1, 1, 1>(d, p.vec, s);
         default: return ST_EINVAL;
     }
 }
 
-// Checks + buffer extents of a descriptor that must run on the plain (non-persistent, unsplit) 64x64 LDS-DMA kernel.
-static int pair_member_prepare(const st_gemm_desc* desc, st_gemm_desc& d) {
-    d = *desc;
-    if (!c_planes_ok(d)) return ST_EINVAL;
-    if (!d.a || !d.w || !d.c || d.M <= 0 || d.N <= 0 || d.K <= 0) return ST_EINVAL;
-    if (d.kh <= 0 || d.kw <= 0 || d.K != d.kh * d.kw * d.Cin || d.K < 128 || d.Cin % 32) return ST_EINVAL;
-    if (d.Ho <= 0 || d.Wo <= 0 || d.M % (d.Ho * d.Wo)) return ST_EINVAL;
-    if (d.epi != ST_EPI_STORE && !d.aux1) return ST_EINVAL;
-    if (d.epi == ST_EPI_GRU && !d.aux2) return ST_EINVAL;
-    if (d.epi == ST_EPI_ZR && (!d.c2 || (d.N & 1))) return ST_EINVAL;
-    if (d.reserved0 != 0 || d.reserved1 != 0 || d.reserved2 != 0 || d.reserved3 != 0 || d.split3 || d.c_t || d.a_ln || d.batch > 1 || d.split_k > 1 || (d.tile_cfg != 0 && d.tile_cfg != 13)) return ST_EINVAL;
-    if (d.a2 && (d.a2_channels <= 0 || d.a2_channels % 32 || d.a2_channels > d.Cin || ((uintptr_t)d.a2 & 15))) return ST_EINVAL;
-    if (((uintptr_t)d.a & 15) || ((uintptr_t)d.w & 15) || (d.ldx & 3) || (d.ldw & 3)) return ST_EINVAL;
-    const bool plain_mat = d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0 && (int64_t)d.H * d.W == d.M &&
-                           (int64_t)d.Ho * d.Wo == d.M;
-    const int64_t hw = plain_mat ? 1 : (int64_t)d.Ho * d.Wo, nimg = d.M / hw, img_rows = plain_mat ? 1 : (int64_t)d.H * d.W;
-    const int64_t ab = ((nimg * img_rows - 1) * d.ldx + d.Cin) * 4, wb = ((int64_t)(d.N - 1) * d.ldw + d.K) * 4;
-    int64_t ldmax = d.ldc > d.N ? d.ldc : d.N;
-    if (d.aux0 && d.ld_aux0 > ldmax) ldmax = d.ld_aux0;
-    if (d.aux1 && d.ld_aux1 > ldmax) ldmax = d.ld_aux1;
-    if (d.aux2 && d.ld_aux2 > ldmax) ldmax = d.ld_aux2;
-    if (d.c2 && d.ldc2 > ldmax) ldmax = d.ldc2;
-    if (wb >= (int64_t)ST_OOB || ab >= (int64_t)ST_OOB || ((int64_t)d.M + 256) * ldmax * 4 >= ((int64_t)1 << 31)) return ST_EINVAL;   // (no row chunking here)
-    d.a_bytes = (uint32_t)ab; d.w_bytes = (uint32_t)wb;
-    d.split_k = 1; d.batch = 1;
+// check, chunk if needed, plan; `go(descriptor, plan)` is what happens to each planned piece (st_conv_gemm: launch it, st_gemm_plan: note the plan)
+template <class Go>
+static int dispatch_f32(const st_gemm_desc& d, Go& go) {
+    bool chunked;
+    if (check_f32(d, chunked)) return ST_EINVAL;
+    if (chunked) return for_each_row_chunk(d, [&go](const st_gemm_desc& c) { return dispatch_f32(c, go); });
+    gemm_plan p;
+    return plan_f32(d, p) ? ST_EINVAL : go(d, p);
+}
+
+static int conv_gemm_launch(const st_gemm_desc* desc, void* stream) {
+    if (desc->split3) return conv_gemm_split3_launch(desc, stream);
+    auto go = [stream](const st_gemm_desc& d, const gemm_plan& p) { st_plan_set(p); return launch_f32(d, p, (hipStream_t)stream); };
+    return dispatch_f32(*desc, go);
+}
+
+// An fp32 member of st_conv_gemm_pair (which = 0 / 1): one piece on the plain (non-persistent, unsplit) 64x64 LDS-DMA kernel.
+static int plan_f32_pair_member(const st_gemm_desc& d, int which, gemm_plan& p) {
+    if (!desc_common_check(d)) return ST_EINVAL;
+    // both members share one grid of one tile shape: no batches, no split-K slabs, tile_cfg 13 only -- and nothing only another kernel carries
+    if (d.split3 || d.c_t || d.a_ln || d.batch > 1 || d.split_k > 1 || (d.tile_cfg != 0 && d.tile_cfg != 13)) return ST_EINVAL;
+    // the LDS-DMA kernel's preconditions, which plan_f32 answers by choosing another kernel: whole 32-channel K steps, a full ring, 16-byte rows
+    if (d.K < 128 || d.Cin % 32 || ((uintptr_t)d.a & 15) || ((uintptr_t)d.w & 15) || (d.ldx & 3) || (d.ldw & 3)) return ST_EINVAL;
+    const f32_extent e = desc_f32_extent(d);
+    if (e.w_bytes >= (int64_t)ST_OOB || e.a_bytes >= (int64_t)ST_OOB || !desc_epi_reach_ok(d)) return ST_EINVAL;   // (no row chunking here)
+    p = gemm_plan{3, 13, 1, 2 + which, false, false, (uint32_t)e.a_bytes, (uint32_t)e.w_bytes};
     return ST_OK;
 }
 
 extern "C" int st_conv_gemm_pair(const st_gemm_desc* desc0, const st_gemm_desc* desc1, void* stream) {
     if (!desc0 || !desc1) return ST_EINVAL;
     if (desc0->split3 || desc1->split3) return conv_gemm_split3_pair_launch(desc0, desc1, stream);
-    st_gemm_pair_args g;
-    int rc = pair_member_prepare(desc0, g.d[0]);
+    gemm_plan p[2];
+    if (plan_f32_pair_member(*desc0, 0, p[0]) || plan_f32_pair_member(*desc1, 1, p[1])) return ST_EINVAL;
+    return launch_pair(conv_gemm_dma_pair_kernel<2, 2, 1, 1, 4>, 256, (size_t)4 * (64 + 64) * 32 * sizeof(float), desc0, desc1, p, stream);
+}
+
+// What st_conv_gemm(desc) -- or, with pair_with, st_conv_gemm_pair(desc, pair_with) -- would do, from the functions they run themselves: ST_EINVAL, or
+// ST_OK and the four values st_gemm_last_plan reports after that call.  Launches nothing, follows no pointer, leaves the thread's last plan alone.
+extern "C" int st_gemm_plan(const st_gemm_desc* desc, const st_gemm_desc* pair_with, int32_t* plan4) {
+    if (!desc || !plan4) return ST_EINVAL;
+    gemm_plan p[2];                                             // p[1]: the plan reported last
+    auto go = [&p](const st_gemm_desc&, const gemm_plan& q) { p[1] = q; return ST_OK; };
+    const int rc = !pair_with ? (desc->split3 ? conv_gemm_split3_plan(*desc, p[1]) : dispatch_f32(*desc, go))
+                   : (desc->split3 || pair_with->split3) ? conv_gemm_split3_pair_plan(*desc, *pair_with, p)
+                   : (plan_f32_pair_member(*desc, 0, p[0]) || plan_f32_pair_member(*pair_with, 1, p[1])) ? ST_EINVAL : ST_OK;
     if (rc) return rc;
-    rc = pair_member_prepare(desc1, g.d[1]);
-    if (rc) return rc;
-    auto tiles = [](const st_gemm_desc& d) { return ((d.M + 63) / 64) * ((d.N + 63) / 64); };
-    g.tiles0 = tiles(g.d[0]);
-    const int total = g.tiles0 + tiles(g.d[1]);
-    // plan[3]: 2 = first member of a pair (no dispatch of its own: the observer sees an empty bracket), 3 = second member (the
-    // pair's single dispatch and all of its time)
-    st_plan_set(3, 13, 1, 2);
-    const bool obs = st_observe(desc0, stream, 0);
-    if (obs) { st_observe(desc0, stream, 1); st_observe(desc1, stream, 0); }
-    st_plan_set(3, 13, 1, 3);
-    auto k = conv_gemm_dma_pair_kernel<2, 2, 1, 1, 4>;
-    const size_t lds = (size_t)4 * (64 + 64) * 32 * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3(total), dim3(256), lds, (hipStream_t)stream, g);
-    if (obs) st_observe(desc1, stream, 1);                      // (the pair's time is attributed to its second member)
-    ST_CHECK_LAUNCH();
+    plan4[0] = p[1].family; plan4[1] = p[1].tile_cfg; plan4[2] = p[1].split; plan4[3] = p[1].persistent;
     return ST_OK;
 }
 
@@ -1202,20 +1183,12 @@ extern "C" int st_conv_gemm_pair(const st_gemm_desc* desc0, const st_gemm_desc* 
 extern "C" int st_corr_volume(const float* f1, const float* f2, float* vol, int32_t B, int32_t N1, int32_t N2,
                               int32_t C, void* stream) {
     if (!f1 || !f2 || !vol || B <= 0 || N1 <= 0 || N2 <= 0 || C <= 0) return ST_EINVAL;
-    st_gemm_desc d = {};
-    d.a = f1; d.w = f2; d.c = vol;
-    d.M = N1; d.N = N2; d.K = C;
-    d.H = 1; d.W = N1; d.Cin = C; d.ldx = C;
-    d.kh = d.kw = 1; d.sh = d.sw = 1; d.ph = d.pw = 0; d.Ho = 1; d.Wo = N1;
-    d.ldw = C; d.ldc = N2; d.alpha = 1.0f;
-    d.batch = B; d.batch_stride_a = (int64_t)N1 * C; d.batch_stride_w = (int64_t)N2 * C;
-    d.batch_stride_c = (int64_t)N1 * N2;
-    return st_conv_gemm(&d, stream);
+    return Gemm(f1, C, f2, C, vol, N2, N1, N2, C).batched(B, (int64_t)N1 * C, (int64_t)N2 * C, (int64_t)N1 * N2).run(stream);
 }
 
 // 1 = one product with a transposed second store, 0 = two products.  The transposed store needs a shape of the LDS-DMA kernel
 // (N % 4 == 0, C % 32 == 0, C >= 128, 16-byte aligned operands) AND a volume that the 32-bit buffer offsets reach in one piece:
-// N * N * 4 < 2^31 for the transposed copy (conv_gemm_launch rejects c_t otherwise) and (N + 256) * N * 4 < 2^31, f1 / f2 extents
+// N * N * 4 < 2^31 for the transposed copy (desc_common_check rejects c_t otherwise) and (N + 256) * N * 4 < 2^31, f1 / f2 extents
 // < 2^31 for the row-chunked path, which cannot carry c_t (N > ~23 000, i.e. flow grids beyond ~1 200 x 1 200 pixels / 8).
 extern "C" int st_corr_volume_both_plan(int32_t B, int32_t N, int32_t C, int32_t aligned16) {
     if (B <= 0 || N <= 0 || C <= 0) return 0;
@@ -1233,15 +1206,7 @@ extern "C" int st_corr_volume_both(const float* f1, const float* f2, float* vol1
         const int rc = st_corr_volume(f1, f2, vol12, B, N, N, C, stream);
         return rc ? rc : st_corr_volume(f2, f1, vol21, B, N, N, C, stream);
     }
-    st_gemm_desc d = {};
-    d.a = f1; d.w = f2; d.c = vol12; d.c_t = vol21; d.ld_ct = N;
-    d.M = N; d.N = N; d.K = C;
-    d.H = 1; d.W = N; d.Cin = C; d.ldx = C;
-    d.kh = d.kw = 1; d.sh = d.sw = 1; d.ph = d.pw = 0; d.Ho = 1; d.Wo = N;
-    d.ldw = C; d.ldc = N; d.alpha = 1.0f;
-    d.batch = B; d.batch_stride_a = (int64_t)N * C; d.batch_stride_w = (int64_t)N * C;
-    d.batch_stride_c = (int64_t)N * N;
-    return st_conv_gemm(&d, stream);
+    return Gemm(f1, C, f2, C, vol12, N, N, N, C).transposed(vol21, N).batched(B, (int64_t)N * C, (int64_t)N * C, (int64_t)N * N).run(stream);
 }
 
 extern "C" int st_gemm_last_plan(int32_t* plan4) {

@@ -1,12 +1,14 @@
 // What the three translation units of the implicit-GEMM family share: gemm.hip (the fp32-MFMA kernels and their dispatcher),
 // gemm_split3.hip (the exact-split bf16 kernels of gemm_split3.h) and gemm_rows.hip (the C = 128 row kernels, mlp_split3.h).
 //   device side: the vector types, the raw-buffer / LDS-DMA loaders and the one epilogue every tiled kernel ends with;
-//   host side:   declarations of the few internals that cross the files (each defined once, in the file named beside it).
+//   host side:   the descriptor checks every path opens with, the launch plan, the plain-GEMM descriptor builder, the pair launcher, and declarations
+//                of the few internals that cross the files (each defined once, in the file named beside it).
 // Templates, __forceinline__ / inline functions, types and macros only -- no __global__ and no non-inline definition: the library is
 // built without relocatable device code, every .hip is its own code object.  Macros of one family stay in that family's file.
 #pragma once
 #include "common.h"
 #include <string.h>
+#include <algorithm>
 #include "../../include/stitch_gfx950.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -390,12 +392,117 @@ inline bool c_planes_ok(const st_gemm_desc& d) {
     return 2 * (2 * d.c_plane_stride + chunks * d.c_plane_rows * 32) < ((int64_t)1 << 31);
 }
 
+// ---- descriptor checks, written once: the fp32 path, the fp32 pair members (gemm.hip) and the split3 path (gemm_split3.hip) each add their own rules ----
+// a 1x1 window, unit stride, no padding over an input of exactly M pixels: A is read as M rows.  (Says nothing about Ho / Wo: the row-streaming
+// kernel's test, which never looks at them -- a descriptor with Ho * Wo a proper divisor of M passes the common checks and takes that kernel.)
+inline bool desc_is_plain_input(const st_gemm_desc& d) { return d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0 && (int64_t)d.H * d.W == d.M; }
+// a matrix: every row is its own "image".  (Products in 64 bits at every site; the LDS-DMA walk's copy took them in 32, which differs only where H * W
+// overflows int32 -- undefined there, and with ldx >= 1 such an input has already failed the 2 GiB test of its A extent.)
+inline bool desc_is_plain_matrix(const st_gemm_desc& d) { return desc_is_plain_input(d) && (int64_t)d.Ho * d.Wo == d.M; }
+
+// the epilogue addresses C / aux operands with 32-bit buffer offsets (first row of a lane + SGPR row step): the largest leading dimension it uses ...
+inline int64_t desc_epi_ldmax(const st_gemm_desc& d) {
+    const int64_t ld[6] = {d.ldc, d.N, d.aux0 ? d.ld_aux0 : 0, d.aux1 ? d.ld_aux1 : 0, d.aux2 ? d.ld_aux2 : 0, d.c2 ? d.ldc2 : 0};
+    return *std::max_element(ld, ld + 6);
+}
+inline bool desc_epi_reach_ok(const st_gemm_desc& d) { return ((int64_t)d.M + 256) * desc_epi_ldmax(d) * 4 < ((int64_t)1 << 31); }     // ... and whether it reaches every row
+inline bool desc_common_check(const st_gemm_desc& d) {           // what every path checks
+    if (!d.a || !d.w || !d.c || d.M <= 0 || d.N <= 0 || d.K <= 0) return false;
+    if (d.kh <= 0 || d.kw <= 0 || d.K != d.kh * d.kw * d.Cin) return false;
+    if (d.Ho <= 0 || d.Wo <= 0 || d.M % (d.Ho * d.Wo)) return false;
+    if (d.epi != ST_EPI_STORE && !d.aux1) return false;
+    if (d.epi == ST_EPI_GRU && !d.aux2) return false;
+    if (d.epi == ST_EPI_ZR && (!d.c2 || (d.N & 1))) return false;
+    if (d.reserved0 != 0 || d.reserved1 != 0 || d.reserved2 != 0 || d.reserved3 != 0) return false;
+    // transposed second store: 16-byte runs of four rows, inside the 32-bit offsets, never from split-K slabs
+    if (d.c_t && (d.epi != ST_EPI_STORE || (d.M & 3) || (d.ld_ct & 3) || d.ld_ct < d.M || ((uintptr_t)d.c_t & 15) || d.split_k > 1 ||
+                  (int64_t)d.N * d.ld_ct * 4 >= ((int64_t)1 << 31)))
+        return false;
+    // second A source: whole 32-channel K steps, one batch (the pair members reject batch > 1 outright, so the batch half is moot there)
+    if (d.a2 && (d.a2_channels <= 0 || d.a2_channels % 32 || d.a2_channels > d.Cin || d.batch > 1 || ((uintptr_t)d.a2 & 15))) return false;
+    return c_planes_ok(d);
+}
+
+// byte extents of one batch slice of the fp32 operands A and W for the buffer descriptors (both must stay below 2 GiB so that the out-of-range
+// sentinel offset is always past num_records); hw / img_rows = output / input rows per image (1 / 1 for a matrix)
+struct f32_extent { int64_t hw, img_rows, a_bytes, w_bytes; };
+inline f32_extent desc_f32_extent(const st_gemm_desc& d) {
+    const bool plain_mat = desc_is_plain_matrix(d);
+    const int64_t hw = plain_mat ? 1 : (int64_t)d.Ho * d.Wo, img_rows = plain_mat ? 1 : (int64_t)d.H * d.W;
+    return {hw, img_rows, ((d.M / hw * img_rows - 1) * d.ldx + d.Cin) * 4, ((int64_t)(d.N - 1) * d.ldw + d.K) * 4};
+}
+
+// What a checked descriptor launches.  The first four are st_gemm_last_plan's values, in its order; plan_f32 (gemm.hip) and plan_split3
+// (gemm_split3.hip) fill one without a HIP call or a global, the launchers switch on it.
+struct gemm_plan {
+    int32_t family, tile_cfg, split, persistent;
+    bool vec, narrow3x3;        // family 2: the register-staged kernel's 16-byte loads (VEC), not its scalar gather; family 1: narrow_conv3x3_kernel, not narrow_conv_kernel
+    uint32_t a_bytes, w_bytes;  // st_gemm_desc.a_bytes / w_bytes of the launch
+};
+
+// The plain A . B^T descriptor and what the callers put on top of it (the operator entry points, st_corr_volume*, the row launchers' observer image)
+struct Gemm {
+    st_gemm_desc d;
+    Gemm(const float* a, int32_t lda, const float* w, int32_t ldw, float* c, int32_t ldc, int32_t M, int32_t N, int32_t Cin) {
+        memset(&d, 0, sizeof(d));
+        d.a = a; d.w = w; d.c = c; d.M = M; d.N = N; d.K = Cin; d.ldx = lda; d.ldw = ldw; d.ldc = ldc;
+        d.H = 1; d.W = M; d.Cin = Cin; d.kh = d.kw = d.sh = d.sw = 1; d.Ho = 1; d.Wo = M;
+        d.alpha = 1.f; d.batch = 1;
+    }
+    Gemm& conv(int32_t B, int32_t H, int32_t W, int32_t kh, int32_t kw, int32_t sh, int32_t sw, int32_t ph, int32_t pw, int32_t Ho = -1, int32_t Wo = -1) {
+        d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.sh = sh; d.sw = sw; d.ph = ph; d.pw = pw;
+        d.Ho = Ho >= 0 ? Ho : (H + 2 * ph - kh) / sh + 1; d.Wo = Wo >= 0 ? Wo : (W + 2 * pw - kw) / sw + 1;
+        d.M = B * d.Ho * d.Wo; d.K = kh * kw * d.Cin;
+        return *this;
+    }
+    Gemm& bias(const float* b) { d.bias = b; return *this; }
+    Gemm& act(int a) { d.act = a; return *this; }
+    Gemm& alpha(float a) { d.alpha = a; return *this; }
+    Gemm& aux0(const float* p, int32_t ld, int32_t row_div = 0, int32_t row_mod = 0) { d.aux0 = p; d.ld_aux0 = ld; d.aux0_row_div = row_div; d.aux0_row_mod = row_mod; return *this; }
+    Gemm& epi(int e, const float* a1, int32_t ld1, const float* a2 = nullptr, int32_t ld2 = 0) { d.epi = e; d.aux1 = a1; d.ld_aux1 = ld1; d.aux2 = a2; d.ld_aux2 = ld2; return *this; }
+    Gemm& scale(const float* s) { d.scale_ptr = s; return *this; }
+    Gemm& out2(float* c2, int32_t ld) { d.c2 = c2; d.ldc2 = ld; return *this; }
+    Gemm& a2(const float* p, int32_t channels) { d.a2 = p; d.a2_channels = channels; return *this; }
+    Gemm& batched(int32_t n, int64_t sa, int64_t sw, int64_t sc) { d.batch = n; d.batch_stride_a = sa; d.batch_stride_w = sw; d.batch_stride_c = sc; return *this; }
+    Gemm& transposed(float* c_t, int32_t ld) { d.c_t = c_t; d.ld_ct = ld; return *this; }
+    Gemm& work(void* ws, int64_t floats) { d.workspace = (float*)ws; d.workspace_floats = floats; return *this; }
+    int run(void* stream) { return st_conv_gemm(&d, stream); }
+};
+
 // ---- host-side internals that cross the translation units (not part of the C ABI) ---------------------------------------------------
 // The profiling observer (st_set_gemm_observer) and the calling thread's last launch plan (st_gemm_last_plan).  The state is private to
-// gemm.hip; every launcher of the family, in whichever file, reports through these three.
+// gemm.hip; every launcher of the family, in whichever file, reports through these.
 void st_plan_set(int kernel, int tile, int split_k, int persistent);      // the calling thread's last plan (st_gemm_last_plan's four values)
+inline void st_plan_set(const gemm_plan& p) { st_plan_set(p.family, p.tile_cfg, p.split, p.persistent); }
 bool st_observer_installed(void);                                          // lets a launcher build a descriptor for the observer only when one listens
 bool st_observe(const st_gemm_desc* od, void* stream, int phase);         // phase 0 before a launch, 1 after it; false when no observer is installed
 void splitk_reduce_launch(const st_gemm_desc& d, hipStream_t s);          // gemm.hip: the split-K tail (splitk_reduce_kernel) behind a launch with d.split_k > 1
-int conv_gemm_split3_launch(const st_gemm_desc* desc, void* stream);       // gemm_split3.hip: st_conv_gemm with desc->split3
-int conv_gemm_split3_pair_launch(const st_gemm_desc* desc0, const st_gemm_desc* desc1, void* stream);      // gemm_split3.hip: st_conv_gemm_pair with split3 members
+// gemm_split3.hip: st_conv_gemm / st_conv_gemm_pair with split3 set, and what each would launch (checks + plan_split3, no HIP call: st_gemm_plan)
+int conv_gemm_split3_launch(const st_gemm_desc* desc, void* stream);
+int conv_gemm_split3_pair_launch(const st_gemm_desc* desc0, const st_gemm_desc* desc1, void* stream);
+int conv_gemm_split3_plan(const st_gemm_desc& desc, gemm_plan& p);
+int conv_gemm_split3_pair_plan(const st_gemm_desc& desc0, const st_gemm_desc& desc1, gemm_plan (&p)[2]);
+
+// One launch for both members of a pair (fp32: conv_gemm_dma_pair_kernel, split3: conv_gemm_split3_pair_kernel): workgroups [0, tiles0) of 64x64 tiles
+// run desc0, the rest desc1.  p: the members' plans; plan[3] = 2 for the first member (no dispatch of its own: the observer sees an empty bracket),
+// 3 for the second (the pair's single dispatch and all of its time).
+template <class K>
+inline int launch_pair(K k, int block, size_t lds, const st_gemm_desc* desc0, const st_gemm_desc* desc1, const gemm_plan (&p)[2], void* stream) {
+    st_gemm_pair_args g;
+    for (int i = 0; i < 2; ++i) {
+        g.d[i] = i ? *desc1 : *desc0;
+        g.d[i].a_bytes = p[i].a_bytes; g.d[i].w_bytes = p[i].w_bytes; g.d[i].split_k = 1; g.d[i].batch = 1;
+    }
+    auto tiles = [](const st_gemm_desc& d) { return ((d.M + 63) / 64) * ((d.N + 63) / 64); };
+    g.tiles0 = tiles(g.d[0]);
+    const int total = g.tiles0 + tiles(g.d[1]);
+    st_plan_set(p[0]);
+    const bool obs = st_observe(desc0, stream, 0);
+    if (obs) { st_observe(desc0, stream, 1); st_observe(desc1, stream, 0); }
+    st_plan_set(p[1]);
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, dim3(total), dim3(block), lds, (hipStream_t)stream, g);
+    if (obs) st_observe(desc1, stream, 1);                      // (the pair's time is attributed to its second member)
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}

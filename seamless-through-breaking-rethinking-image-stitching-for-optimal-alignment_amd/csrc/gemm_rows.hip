@@ -15,10 +15,8 @@ static bool row_launch_begin(st_gemm_desc& od, int kernel, int tile, void* strea
                              int split3) {
     bool obs = st_observer_installed();
     if (obs) {
-        memset(&od, 0, sizeof(od));
-        od.a = a; od.c = c; od.w = (const float*)w;
-        od.M = M; od.N = N; od.K = 128; od.H = 1; od.W = M; od.Cin = 128; od.ldx = lda; od.ldc = ldc; od.ldw = 128;
-        od.kh = od.kw = od.sh = od.sw = 1; od.Ho = 1; od.Wo = M; od.batch = 1; od.alpha = 1.f; od.split3 = split3;
+        od = Gemm(a, lda, (const float*)w, 128, c, ldc, M, N, 128).d;
+        od.split3 = split3;
         obs = st_observe(&od, stream, 0);
     }
     st_plan_set(kernel, tile, 1, 1);

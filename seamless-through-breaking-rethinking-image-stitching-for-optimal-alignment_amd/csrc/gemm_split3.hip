@@ -1,61 +1,53 @@
 // Host side of the exact-split fp32 contraction on the bf16 matrix cores ("split3": every fp32 operand as three bf16 planes, six bf16 MFMA
 // products per fp32 product -- the kernels and their story are in gemm_split3.h, the epilogue they share with the fp32 kernels in
-// gemm_common.h): descriptor checks, the tile / split-K plan, the launches.  Reached from st_conv_gemm / st_conv_gemm_pair (gemm.hip) for
+// gemm_common.h): the split3 rules on top of the common descriptor checks (check_split3), the tile / split-K / persistent-walk plan as a pure
+// function (plan_split3), the launches by a switch on that plan.  Reached from st_conv_gemm / st_conv_gemm_pair / st_gemm_plan (gemm.hip) for
 // descriptors with split3 set, and through st_split3_pack and st_corr_volume_split3.
 #include "gemm_split3.h"
 
-template <int WM, int WN, int TM, int TN, int STAGES>
+// KPAR: two consumer groups per workgroup (csrc/gemm_split3.h): 768 threads, same tiles, same ring
+template <int WM, int WN, int TM, int TN, int STAGES, bool KPAR = false>
 static int launch_split3(const st_gemm_desc& d, hipStream_t s) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
     const int batch = d.batch > 0 ? d.batch : 1;
     const size_t lds = (size_t)STAGES * 3 * (BM + BN) * 64;
     void (*k)(const st_gemm_desc) = conv_gemm_split3_kernel<WM, WN, TM, TN, STAGES>;
-    if constexpr (TM * TN == 1 && WM == 2 && WN == 2 && STAGES == 3) k = conv_gemm_split3_kernel64<STAGES>;
+    if constexpr (KPAR) k = conv_gemm_split3_kpar_kernel<WM, WN, TM, TN, STAGES>;
+    else if constexpr (TM * TN == 1 && WM == 2 && WN == 2 && STAGES == 3) k = conv_gemm_split3_kernel64<STAGES>;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3(ntm * ntn, 1, d.split_k > 1 ? d.split_k : batch), dim3(512), lds, s, d);
+    hipLaunchKernelGGL(k, dim3(ntm * ntn, 1, d.split_k > 1 ? d.split_k : batch), dim3(KPAR ? 768 : 512), lds, s, d);
     if (d.split_k > 1) splitk_reduce_launch(d, s);
     ST_CHECK_LAUNCH();
     return ST_OK;
 }
 
-// two consumer groups per workgroup (KPAR = 2, csrc/gemm_split3.h): 768 threads, same tiles, same ring
-template <int WM, int WN, int TM, int TN, int STAGES>
-static int launch_split3_kpar(const st_gemm_desc& d, hipStream_t s) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
+// tile_cfg 37: up to 512 / batch workgroups walk the 64x64 tiles
+static int launch_split3_persist(const st_gemm_desc& d, hipStream_t s) {
     const int batch = d.batch > 0 ? d.batch : 1;
-    const size_t lds = (size_t)STAGES * 3 * (BM + BN) * 64;
-    void (*k)(const st_gemm_desc) = conv_gemm_split3_kpar_kernel<WM, WN, TM, TN, STAGES>;
+    const long ntl64 = (long)((d.M + 63) / 64) * ((d.N + 63) / 64);
+    int G = 512 / batch;
+    if (G < 1) G = 1;
+    if (G > ntl64) G = (int)ntl64;
+    const size_t lds = (size_t)3 * 3 * 128 * 64;
+    void (*k)(const st_gemm_desc) = d.c_t ? conv_gemm_split3_persist_kernel<true> : conv_gemm_split3_persist_kernel<false>;
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3(ntm * ntn, 1, batch), dim3(768), lds, s, d);
+    hipLaunchKernelGGL(k, dim3(G, 1, batch), dim3(512), lds, s, d);
     ST_CHECK_LAUNCH();
     return ST_OK;
 }
 
-// checks + buffer extents of a split3 descriptor (shared by st_conv_gemm and st_conv_gemm_pair)
-static int split3_prepare(const st_gemm_desc* desc, st_gemm_desc& d) {
-    d = *desc;
-    if (!d.a || !d.w || !d.c || d.M <= 0 || d.N <= 0 || d.K <= 0) return ST_EINVAL;
-    if (d.kh <= 0 || d.kw <= 0 || d.K != d.kh * d.kw * d.Cin || d.Cin % 32) return ST_EINVAL;
-    if (d.Ho <= 0 || d.Wo <= 0 || d.M % (d.Ho * d.Wo)) return ST_EINVAL;
-    if (d.epi != ST_EPI_STORE && !d.aux1) return ST_EINVAL;
-    if (d.epi == ST_EPI_GRU && !d.aux2) return ST_EINVAL;
-    if (d.epi == ST_EPI_ZR && (!d.c2 || (d.N & 1))) return ST_EINVAL;
-    if (d.reserved0 != 0 || d.reserved1 != 0 || d.reserved2 != 0 || d.reserved3 != 0 || d.a_ln) return ST_EINVAL;
-    if (d.c_t && (d.epi != ST_EPI_STORE || (d.M & 3) || (d.ld_ct & 3) || d.ld_ct < d.M || ((uintptr_t)d.c_t & 15) || d.split_k > 1 || d.a2 || d.c_planes ||
-                  (int64_t)d.N * d.ld_ct * 4 >= ((int64_t)1 << 31)))
-        return ST_EINVAL;                              // (transposed second store: the persistent 64x64 kernel only)
-    if (!c_planes_ok(d)) return ST_EINVAL;
-    if (d.split3 != 1) return ST_EINVAL;
+// The split3 path's own rules on top of desc_common_check, and the extents of its operands (shared by st_conv_gemm and st_conv_gemm_pair)
+static int check_split3(const st_gemm_desc& d, gemm_plan& p) {
+    if (!desc_common_check(d)) return ST_EINVAL;
+    // the operands are planes of whole 32-channel chunks; LayerNorm of the A rows is the fp32 row-streaming kernel's
+    if (d.split3 != 1 || d.Cin % 32 || d.a_ln) return ST_EINVAL;
+    // transposed second store: the persistent 64x64 kernel only, which reads one A source (plan_split3 refuses a2 on tile 37 as well, and
+    // c_planes_ok refuses c_t beside c_planes: both halves are kept as the rule stood)
+    if (d.c_t && (d.a2 || d.c_planes)) return ST_EINVAL;
     if (d.a_plane_stride <= 0 || d.w_plane_stride <= 0 || d.a_rows <= 0 || d.w_rows < d.N) return ST_EINVAL;
-    if (((uintptr_t)d.a & 15) || ((uintptr_t)d.w & 15) || (d.a_plane_stride & 7) || (d.w_plane_stride & 7) || (d.batch_stride_a & 7) ||
-        (d.batch_stride_w & 7))
-        return ST_EINVAL;
-    if (d.a2 && (d.a2_channels <= 0 || d.a2_channels % 32 || d.a2_channels > d.Cin || d.batch > 1 || ((uintptr_t)d.a2 & 15))) return ST_EINVAL;
-    const bool plain_mat = d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0 && (int64_t)d.H * d.W == d.M &&
-                           (int64_t)d.Ho * d.Wo == d.M;
-    const int64_t nimg = d.M / ((int64_t)d.Ho * d.Wo), in_rows = plain_mat ? d.M : nimg * d.H * d.W;
+    if ((((uintptr_t)d.a | (uintptr_t)d.w) & 15) || ((d.a_plane_stride | d.w_plane_stride | d.batch_stride_a | d.batch_stride_w) & 7)) return ST_EINVAL;
+    const int64_t nimg = d.M / ((int64_t)d.Ho * d.Wo), in_rows = desc_is_plain_matrix(d) ? d.M : nimg * d.H * d.W;
     if (in_rows > d.a_rows) return ST_EINVAL;
     // batch b reads rows b * batch_stride / 32 onwards of every chunk (the kernels shift the base, not the buffer extents): the last batch's
     // planes must end inside the caller's
@@ -66,23 +58,14 @@ static int split3_prepare(const st_gemm_desc* desc, st_gemm_desc& d) {
     // extents (bytes) from the plane-0 base to the end of plane 2; the 32-bit buffer offsets and the out-of-range sentinel need < 2 GiB
     const int64_t ab = 2 * (2 * d.a_plane_stride + (int64_t)(d.Cin / 32) * d.a_rows * 32);
     const int64_t wb = 2 * (2 * d.w_plane_stride + (int64_t)(d.K / 32) * d.w_rows * 32);
-    if (ab >= (int64_t)ST_OOB || wb >= (int64_t)ST_OOB) return ST_EINVAL;
-    int64_t ldmax = d.ldc > d.N ? d.ldc : d.N;
-    if (d.aux0 && d.ld_aux0 > ldmax) ldmax = d.ld_aux0;
-    if (d.aux1 && d.ld_aux1 > ldmax) ldmax = d.ld_aux1;
-    if (d.aux2 && d.ld_aux2 > ldmax) ldmax = d.ld_aux2;
-    if (d.c2 && d.ldc2 > ldmax) ldmax = d.ldc2;
-    if (((int64_t)d.M + 256) * ldmax * 4 >= ((int64_t)1 << 31)) return ST_EINVAL;
-    d.a_bytes = (uint32_t)ab; d.w_bytes = (uint32_t)wb;
+    if (ab >= (int64_t)ST_OOB || wb >= (int64_t)ST_OOB || !desc_epi_reach_ok(d)) return ST_EINVAL;      // (no row chunking on this path)
+    p = gemm_plan{8, 0, 0, 0, false, false, (uint32_t)ab, (uint32_t)wb};
     return ST_OK;
 }
 
-int conv_gemm_split3_launch(const st_gemm_desc* desc, void* stream) {
-    st_gemm_desc d;
-    {
-        const int rc = split3_prepare(desc, d);
-        if (rc) return rc;
-    }
+// What a descriptor that passed check_split3 launches (family 8): tile, split-K, persistent walk.  No HIP call, no global.  Every threshold is a
+// measured choice; tests/test_gemm_plan_cpu.py pins both sides of each at the workload's shapes.
+static int plan_split3(const st_gemm_desc& d, gemm_plan& p) {
     const int batch = d.batch > 0 ? d.batch : 1;
     int cfg = d.tile_cfg;
     // measured (tools/split3_probe.py, profiles/r6_split3_probe.json): 128x64 tiles on a 4-stage ring win when they still give every CU a
@@ -121,24 +104,26 @@ int conv_gemm_split3_launch(const st_gemm_desc* desc, void* stream) {
         const int nkt = d.K / 32, per = (nkt + split - 1) / split;
         split = (nkt + per - 1) / per;                     // no empty slice
     }
-    d.split_k = split;
-    st_plan_set(8, cfg, split, 0);
+    p.tile_cfg = cfg; p.split = split; p.persistent = cfg == 37;
+    return ST_OK;
+}
+
+int conv_gemm_split3_plan(const st_gemm_desc& desc, gemm_plan& p) {
+    const int rc = check_split3(desc, p);
+    return rc ? rc : plan_split3(desc, p);
+}
+
+int conv_gemm_split3_launch(const st_gemm_desc* desc, void* stream) {
+    gemm_plan p;
+    if (conv_gemm_split3_plan(*desc, p)) return ST_EINVAL;
+    st_gemm_desc d = *desc;
+    d.a_bytes = p.a_bytes; d.w_bytes = p.w_bytes; d.split_k = p.split;
+    st_plan_set(p);
     hipStream_t s = (hipStream_t)stream;
-    if (cfg == 37) {
-        int G = 512 / batch;
-        if (G < 1) G = 1;
-        if (G > ntl64) G = (int)ntl64;
-        const size_t lds = (size_t)3 * 3 * 128 * 64;
-        void (*k)(const st_gemm_desc) = d.c_t ? conv_gemm_split3_persist_kernel<true> : conv_gemm_split3_persist_kernel<false>;
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        st_plan_set(8, cfg, split, 1);
-        hipLaunchKernelGGL(k, dim3(G, 1, batch), dim3(512), lds, s, d);
-        ST_CHECK_LAUNCH();
-        return ST_OK;
-    }
-    switch (cfg) {
-        case 38: return launch_split3_kpar<2, 2, 2, 1, 4>(d, s);
-        case 39: return launch_split3_kpar<2, 2, 1, 1, 4>(d, s);
+    switch (p.tile_cfg) {
+        case 37: return launch_split3_persist(d, s);
+        case 38: return launch_split3<2, 2, 2, 1, 4, true>(d, s);
+        case 39: return launch_split3<2, 2, 1, 1, 4, true>(d, s);
         case 31: return launch_split3<2, 2, 2, 2, 3>(d, s);
         case 32: return launch_split3<2, 2, 2, 1, 4>(d, s);
         case 33: return launch_split3<2, 2, 1, 2, 4>(d, s);
@@ -161,32 +146,25 @@ extern "C" int st_split3_pack(const float* x, void* planes, int64_t rows, int32_
     return ST_OK;
 }
 
-// st_conv_gemm_pair with split3 members (both must be): 64x64 tiles, no split-K, one launch of 8-wave workgroups
-int conv_gemm_split3_pair_launch(const st_gemm_desc* desc0, const st_gemm_desc* desc1, void* stream) {
-    if (!desc0->split3 || !desc1->split3) return ST_EINVAL;
-    st_gemm_pair_args g;
+// st_conv_gemm_pair with split3 members (both must be): 64x64 tiles (tile_cfg 34), no batches, no split-K -- one grid of one tile shape for both
+int conv_gemm_split3_pair_plan(const st_gemm_desc& desc0, const st_gemm_desc& desc1, gemm_plan (&p)[2]) {
+    if (!desc0.split3 || !desc1.split3) return ST_EINVAL;
     for (int i = 0; i < 2; ++i) {
-        const st_gemm_desc* di = i ? desc1 : desc0;
-        if (di->batch > 1 || di->split_k > 1 || (di->tile_cfg != 0 && di->tile_cfg != 34)) return ST_EINVAL;
-        const int rc = split3_prepare(di, g.d[i]);
+        const st_gemm_desc& di = i ? desc1 : desc0;
+        if (di.batch > 1 || di.split_k > 1 || (di.tile_cfg != 0 && di.tile_cfg != 34)) return ST_EINVAL;
+        const int rc = check_split3(di, p[i]);
         if (rc) return rc;
-        g.d[i].split_k = 1; g.d[i].batch = 1;
+        p[i].tile_cfg = 34; p[i].split = 1; p[i].persistent = 2 + i;
     }
-    auto tiles = [](const st_gemm_desc& d) { return ((d.M + 63) / 64) * ((d.N + 63) / 64); };
-    g.tiles0 = tiles(g.d[0]);
-    const int total = g.tiles0 + tiles(g.d[1]);
-    // plan[3] and the observer's brackets as in the fp32 pair (st_conv_gemm_pair, gemm.hip): the pair's one dispatch belongs to its second member
-    st_plan_set(8, 34, 1, 2);
-    const bool obs = st_observe(desc0, stream, 0);
-    if (obs) { st_observe(desc0, stream, 1); st_observe(desc1, stream, 0); }
-    st_plan_set(8, 34, 1, 3);
-    auto k = conv_gemm_split3_pair_kernel<2, 2, 1, 1, 3>;
-    const size_t lds = (size_t)3 * 3 * 128 * 64;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3(total), dim3(512), lds, (hipStream_t)stream, g);
-    if (obs) st_observe(desc1, stream, 1);
-    ST_CHECK_LAUNCH();
     return ST_OK;
+}
+
+// one launch of 8-wave workgroups; plan[3] and the observer's brackets as in the fp32 pair (launch_pair, gemm_common.h)
+int conv_gemm_split3_pair_launch(const st_gemm_desc* desc0, const st_gemm_desc* desc1, void* stream) {
+    gemm_plan p[2];
+    const int rc = conv_gemm_split3_pair_plan(*desc0, *desc1, p);
+    if (rc) return rc;
+    return launch_pair(conv_gemm_split3_pair_kernel<2, 2, 1, 1, 3>, 512, (size_t)3 * 3 * 128 * 64, desc0, desc1, p, stream);
 }
 
 // All-pairs volume(s) from the feature maps' planes (st_gemm_desc.split3; planes [3][C/32][rows][32], sample b = rows b*N ..): vol12[b] = f1[b] . f2[b]^T and,
@@ -194,14 +172,9 @@ int conv_gemm_split3_pair_launch(const st_gemm_desc* desc0, const st_gemm_desc* 
 extern "C" int st_corr_volume_split3(const void* f1_planes, const void* f2_planes, int64_t pstride, int64_t prows, float* vol12, float* vol21, int32_t B,
                                      int32_t N, int32_t C, void* stream) {
     if (!f1_planes || !f2_planes || !vol12 || B <= 0 || N <= 0 || C <= 0 || (C & 31) || prows < (int64_t)B * N) return ST_EINVAL;
-    st_gemm_desc d = {};
-    d.a = (const float*)f1_planes; d.w = (const float*)f2_planes; d.c = vol12; d.c_t = vol21; d.ld_ct = N;
-    d.M = N; d.N = N; d.K = C;
-    d.H = 1; d.W = N; d.Cin = C; d.ldx = C;
-    d.kh = d.kw = 1; d.sh = d.sw = 1; d.ph = d.pw = 0; d.Ho = 1; d.Wo = N;
-    d.ldw = C; d.ldc = N; d.alpha = 1.0f;
-    d.batch = B; d.batch_stride_a = (int64_t)N * 32; d.batch_stride_w = (int64_t)N * 32; d.batch_stride_c = (int64_t)N * N;
-    d.split3 = 1; d.a_plane_stride = pstride; d.w_plane_stride = pstride; d.a_rows = prows; d.w_rows = prows;
-    d.tile_cfg = 37;
-    return st_conv_gemm(&d, stream);
+    Gemm g((const float*)f1_planes, C, (const float*)f2_planes, C, vol12, N, N, N, C);
+    g.transposed(vol21, N).batched(B, (int64_t)N * 32, (int64_t)N * 32, (int64_t)N * N);
+    g.d.split3 = 1; g.d.a_plane_stride = pstride; g.d.w_plane_stride = pstride; g.d.a_rows = prows; g.d.w_rows = prows;
+    g.d.tile_cfg = 37;
+    return g.run(stream);
 }

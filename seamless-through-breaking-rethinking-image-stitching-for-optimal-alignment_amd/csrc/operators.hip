@@ -2,58 +2,13 @@
 // (SURVEY.md 8b minimum symbol set).  Host-side composition only: each function enqueues the library's own
 // kernels (gemm.hip, gemm_split3.hip, gemm_rows.hip, nn.hip, flowops.hip, geom.hip) on the caller's stream, works in caller-provided scratch,
 // allocates nothing and keeps no state.
-#include "common.h"
-#include "../../include/stitch_gfx950.h"
-#include <string.h>
-
-namespace {
-
-struct Gemm {
-    st_gemm_desc d;
-    Gemm(const float* a, int32_t lda, const float* w, int32_t ldw, float* c, int32_t ldc, int32_t M, int32_t N, int32_t Cin) {
-        memset(&d, 0, sizeof(d));
-        d.a = a; d.w = w; d.c = c;
-        d.M = M; d.N = N; d.K = Cin;
-        d.H = 1; d.W = M; d.Cin = Cin; d.ldx = lda;
-        d.kh = d.kw = d.sh = d.sw = 1; d.Ho = 1; d.Wo = M;
-        d.ldw = ldw; d.ldc = ldc;
-        d.alpha = 1.f; d.batch = 1;
-    }
-    Gemm& conv(int32_t B, int32_t H, int32_t W, int32_t kh, int32_t kw, int32_t sh, int32_t sw, int32_t ph, int32_t pw,
-               int32_t Ho = -1, int32_t Wo = -1) {
-        d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.sh = sh; d.sw = sw; d.ph = ph; d.pw = pw;
-        d.Ho = Ho >= 0 ? Ho : (H + 2 * ph - kh) / sh + 1;
-        d.Wo = Wo >= 0 ? Wo : (W + 2 * pw - kw) / sw + 1;
-        d.M = B * d.Ho * d.Wo;
-        d.K = kh * kw * d.Cin;
-        return *this;
-    }
-    Gemm& bias(const float* b) { d.bias = b; return *this; }
-    Gemm& act(int a) { d.act = a; return *this; }
-    Gemm& alpha(float a) { d.alpha = a; return *this; }
-    Gemm& aux0(const float* p, int32_t ld, int32_t row_div = 0, int32_t row_mod = 0) {
-        d.aux0 = p; d.ld_aux0 = ld; d.aux0_row_div = row_div; d.aux0_row_mod = row_mod; return *this;
-    }
-    Gemm& epi(int e, const float* a1, int32_t ld1, const float* a2 = nullptr, int32_t ld2 = 0) {
-        d.epi = e; d.aux1 = a1; d.ld_aux1 = ld1; d.aux2 = a2; d.ld_aux2 = ld2; return *this;
-    }
-    Gemm& scale(const float* s) { d.scale_ptr = s; return *this; }
-    Gemm& out2(float* c2, int32_t ld) { d.c2 = c2; d.ldc2 = ld; return *this; }
-    Gemm& a2(const float* p, int32_t channels) { d.a2 = p; d.a2_channels = channels; return *this; }
-    Gemm& batched(int32_t n, int64_t sa, int64_t sw, int64_t sc) {
-        d.batch = n; d.batch_stride_a = sa; d.batch_stride_w = sw; d.batch_stride_c = sc; return *this;
-    }
-    Gemm& work(void* ws, int64_t floats) { d.workspace = (float*)ws; d.workspace_floats = floats; return *this; }
-    int run(void* stream) { return st_conv_gemm(&d, stream); }
-};
+#include "gemm_common.h"      // struct Gemm, the descriptor builder
 
 #define ST_TRY(expr)            \
     do {                        \
         int rc__ = (expr);      \
         if (rc__) return rc__;  \
     } while (0)
-
-}  // namespace
 
 extern "C" {
 

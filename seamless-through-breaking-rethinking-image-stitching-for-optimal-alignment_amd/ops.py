@@ -210,17 +210,36 @@ def conv_gemm(x, w, out, *, geom=None, bias=None, act="none", alpha=1.0, aux0=No
         d.c2, d.ldc2 = out2.data_ptr(), _ld(out2)
     if _desc_only:
         return d
-    if batch <= 1 and split_k != 1:
-        ws = _workspace(out.device)
-        d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
+    _add_workspace(d, out.device)
     check(lib.st_conv_gemm(C.byref(d), _stream()), "st_conv_gemm")
     return out
+
+
+def _add_workspace(d, dev):
+    """the split-K slabs of a single conv_gemm (pair members never split)"""
+    if d.batch <= 1 and d.split_k != 1:
+        ws = _workspace(dev)
+        d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
 
 
 def gemm_last_plan():
     """[kernel family, tile_cfg, split_k, walk / pair flag] of this thread's last st_conv_gemm (st_gemm_last_plan, include/stitch_gfx950.h)"""
     p = (C.c_int32 * 4)()
     check(lib.st_gemm_last_plan(p), "st_gemm_last_plan")
+    return list(p)
+
+
+def gemm_plan(x, w, out, pair_with=None, **kwargs):
+    """What ``gemm_last_plan()`` reports after ``conv_gemm(x, w, out, **kwargs)`` -- or, with pair_with = (x, w, out, kwargs), after
+    ``conv_gemm_pair((x, w, out, kwargs), pair_with)`` -- without launching anything (st_gemm_plan); StitchError for a rejected descriptor."""
+    d = conv_gemm(x, w, out, _desc_only=True, **kwargs)
+    d1 = None
+    if pair_with is None:
+        _add_workspace(d, out.device)
+    else:
+        d1 = C.byref(conv_gemm(pair_with[0], pair_with[1], pair_with[2], _desc_only=True, **pair_with[3]))
+    p = (C.c_int32 * 4)()
+    check(lib.st_gemm_plan(C.byref(d), d1, p), "st_gemm_plan")
     return list(p)
 
 

@@ -28,6 +28,7 @@ act="none"; the epilogue run is compared with the epilogue evaluated in fp64 on 
 Every output is a column slice (first column 1, ldc > N) of a NaN-filled buffer whose other elements must still be NaN afterwards, and every
 case asserts the plan st_gemm_last_plan reports: [family, tile, split, walk]; family 3 = LDS-DMA, 2 = register-staged, 4 = row-streaming,
 0 = skinny, 1 = narrow."""
+import contextlib
 import math
 
 import pytest
@@ -111,11 +112,11 @@ class Problem:
         x = self.x if x is None else x
         if ws is not None:
             ws.fill_(NAN)
-            with ops.workspace_scope(ws):
-                ops.conv_gemm(x, self.w, out, **kw)
-        else:
+        with (ops.workspace_scope(ws) if ws is not None else contextlib.nullcontext()):
             ops.conv_gemm(x, self.w, out, **kw)
-        return wide, out, ops.gemm_last_plan(), wide2, out2
+            plan = ops.gemm_last_plan()
+            assert ops.gemm_plan(x, self.w, out, **kw) == plan, (kw, plan)        # the plan-only entry answers what the launch did
+        return wide, out, plan, wide2, out2
 
 
 def contraction(ops, name, p, tile, split=1, ws=None, want=None, twice=False, ref_tile=3):

@@ -17,6 +17,7 @@ Two bars per case:
     <= 1.5x + 1e-7 (the bars of test_split3_gpu.py::test_split3_conv_vs_fp32_kernel_and_fp64).
 
 Outputs are written into a column slice of a wider NaN-filled buffer: every element outside the [M, N] view must still be NaN afterwards."""
+import contextlib
 import math
 
 import pytest
@@ -110,12 +111,11 @@ def conv_case(ops, name, *, tile, B=1, H=1, W=1, Cin=32, N=64, kh=1, kw=1, sh=1,
     M = B * Ho * Wo
     wide, out = nan_wide(M, N)
     kw_ = dict(geom=geom, dil=dil)
-    if ws is not None:
-        with ops.workspace_scope(ws):
-            ops.conv_gemm(ops.split3_pack(x), ops.split3_pack(w), out, tile=tile, split_k=split, **kw_)
-    else:
-        ops.conv_gemm(ops.split3_pack(x), ops.split3_pack(w), out, tile=tile, split_k=split, **kw_)
-    plan = ops.gemm_last_plan()
+    xp, wp = ops.split3_pack(x), ops.split3_pack(w)
+    with (ops.workspace_scope(ws) if ws is not None else contextlib.nullcontext()):
+        ops.conv_gemm(xp, wp, out, tile=tile, split_k=split, **kw_)
+        plan = ops.gemm_last_plan()
+        assert ops.gemm_plan(xp, wp, out, tile=tile, split_k=split, **kw_) == plan, (name, plan)      # the plan-only entry answers what the launch did
     oe = torch.empty(M, N, device="cuda")
     ops.conv_gemm(x, w, oe, **kw_)
     torch.cuda.synchronize()
