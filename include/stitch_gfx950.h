@@ -464,13 +464,22 @@ int st_jpeg_encode_u8(const void* src, int32_t H, int32_t W, int32_t channels, i
  * the area of the four code tables, DHT payloads and histograms (9 312 bytes).  (Before the two encoders became one, optimize 0 reserved that
  * area too: the query now returns 9 312 bytes less there.)
  * ST_EINVAL before any launch for everything st_jpeg_encode_u8 rejects (with the _ex sizes), and for: a null params; quality outside 1..100;
- * sampling other than (1,1), (2,1), (2,2); one channel with sampling other than (1,1); optimize other than 0 / 1; a nonzero reserved field.
+ * sampling other than (1,1), (2,1), (2,2); one channel with sampling other than (1,1); optimize other than 0 / 1; a nonzero reserved[1..3];
+ * reserved[0] outside 0..65535.
+ * Restart intervals (csrc/jpeg_rst.hip; contract in README.md "Restart intervals", CPU restatement tests/_jpeg_rst_ref.py): reserved[0] = Ri > 0
+ * writes the file of Pillow's `save(restart_marker_blocks=Ri)` (for `restart_marker_rows=r`: Ri = min(r * MCUs per row, 65535), which
+ * ops.jpeg_encode computes), byte for byte: the segment FF DD 00 04 Ri directly in front of SOS; in front of MCU k * Ri (k >= 1) the pending
+ * bits padded with 1-bits to a byte (a padded FF is stuffed), then FF D0+((k-1)&7) unstuffed, and every DC prediction back at 0; with
+ * optimize 1 the histograms count those reset differences.  With n = ceil(MCUs / Ri) intervals st_jpeg_max_bytes_ex grows by 6 + 4 n -- the
+ * DRI segment, and per interval the two marker bytes and at most 7 padding bits, counted as one byte and doubled like every byte of the
+ * bound for stuffing -- and st_jpeg_workspace_bytes_ex by the stream's share of that and two 16-byte rounded tables of n + 1 words behind the
+ * stream (padding per interval, first byte of every interval).  reserved[0] = 0 is the call, the launches and the sizes without the field.
  * The size queries return 0 for what the entry rejects.                                                                                     */
 typedef struct st_jpeg_enc_params {
     int32_t quality;                                /* 1..100                                                                                */
     int32_t hs, vs;                                 /* luma sampling factors                                                                 */
     int32_t optimize;                               /* 0: Annex K tables; 1: tables made from the image's symbol counts                      */
-    int32_t reserved[4];                            /* 0                                                                                     */
+    int32_t reserved[4];                            /* [0]: restart interval Ri in MCUs, 0..65535, 0: none (below); [1..3]: 0                */
 } st_jpeg_enc_params;
 int st_abi_jpeg_enc_params_size(void);
 int st_jpeg_workspace_bytes_ex(int32_t H, int32_t W, int32_t channels, const st_jpeg_enc_params* params);
@@ -497,9 +506,24 @@ typedef struct st_jpeg_dec_params {
     int32_t q_off[2], dc_off[2], ac_off[2];         /* byte offsets in the file: the 64 zigzag-ordered quantiser bytes of DQT table i; the 16
                                                      * code counts of DHT table i (its values follow); -1: not defined                       */
     int32_t scan_off, scan_len;                     /* the entropy-coded bytes: behind the SOS header, up to (not including) the EOI marker  */
+    int32_t restart_interval, reserved;             /* MCUs per restart interval (the file's DRI), 0: none; reserved: 0                      */
 } st_jpeg_dec_params;
 int st_abi_jpeg_dec_params_size(void);
 int st_jpeg_dec_workspace_bytes(int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, int64_t scan_len);
+/* Restart intervals (csrc/jpeg_rst.hip; contract in README.md "Restart intervals", CPU restatement tests/_jpeg_rst_ref.py).  With
+ * restart_interval Ri in 1..65535 the scan is n = ceil(MCUs / Ri) intervals with the markers FF D0, FF D1, ... FF D7, FF D0, ... between them
+ * (ops.jpeg_probe(data, restart=True) checks their count and order on the host; nothing but the file is uploaded).  The device finds the
+ * markers, drops them while it unstuffs, and cuts EVERY INTERVAL into its own subsequences of 1024 bits: an interval's first subsequence starts
+ * from a known state (its first bit, DC next, DC predictions 0, block i * Ri * blocks per MCU), so the fixpoint of the entropy decoder runs
+ * inside an interval only and a file whose intervals are shorter than 1024 bits needs no repair at all.  *status_dev: 0, or the OR over the
+ * intervals of 1 (fewer blocks in the interval's bytes than it has) and 2 (more); coefficient writes of an interval stay inside its own
+ * blocks, so every other interval still decodes exactly.  restart_interval 0 makes exactly the launches of the table above.  ST_EINVAL before
+ * any launch for a restart_interval outside 0..65535, a nonzero reserved, and a workspace smaller than st_jpeg_dec_workspace_bytes_ex -- the
+ * workspace for these params (0 for rejected ones; with restart_interval 0 it equals st_jpeg_dec_workspace_bytes): that of the plain decode
+ * plus, with n intervals, c = ceil(scan_len / 2048) chunks and s = ceil(8 * scan_len / 1024) + n subsequences rounded up to 256, the 16-byte
+ * rounded tables 2 * 4c (counts) + 3 * 4(n + 1) (marker offsets, interval starts, first subsequences) + 4 * 4s + 4(s + 1) (states, blocks)
+ * + boundary states and flags as above.  Launches: 12 + one per 256 of those s subsequences.                                             */
+int st_jpeg_dec_workspace_bytes_ex(const st_jpeg_dec_params* params);
 int st_jpeg_decode_u8(const void* file_dev, int64_t nbytes, const st_jpeg_dec_params* params, void* out, int64_t row_stride, int32_t* status_dev,
                       void* workspace, int64_t workspace_bytes, void* stream);
 

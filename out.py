@@ -46,6 +46,10 @@ def get_config(argv=None):
     p.add_argument("--jpeg_subsampling", type=int, default=None, choices=(0, 1, 2),
                    help="chroma subsampling of the RGB result JPEGs: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (Pillow's default)")
     p.add_argument("--jpeg_optimize", action="store_true", help="write the result JPEGs with optimised Huffman tables (Pillow's optimize=True)")
+    p.add_argument("--jpeg_restart_blocks", type=int, default=None, metavar="N",
+                   help="restart interval of the result JPEGs in MCUs (Pillow's restart_marker_blocks), on either encoder")
+    p.add_argument("--jpeg_restart_rows", type=int, default=None, metavar="N",
+                   help="restart interval of the result JPEGs in MCU rows (Pillow's restart_marker_rows; wins over --jpeg_restart_blocks)")
     p.add_argument("--gpu_decode", action="store_true",
                    help="decode the input JPEGs on the GPU (Pillow's pixels, bit for bit); files outside the decoder's contract keep Pillow")
     p.add_argument("--dry-run", dest="dry_run", action="store_true",
@@ -56,7 +60,7 @@ def get_config(argv=None):
     for k, v in vars(args).items():
         if k in ("restore_ckpt", "gpu_jpeg", "gpu_decode", "jpeg_optimize") and not v:         # (a switch that is off: config.txt stays what it was before the switch existed)
             continue
-        if k in ("jpeg_quality", "jpeg_subsampling") and v is None:
+        if k in ("jpeg_quality", "jpeg_subsampling", "jpeg_restart_blocks", "jpeg_restart_rows") and v is None:
             continue
         cfg[k] = v
     cfg.TPS_PIPELINE_CONFIG = tps
@@ -99,7 +103,7 @@ def readSingleData(data_path, img1_name, img2_name):
         path = os.path.join(data_path, name)
         with open(path, "rb") as f:
             data = f.read()
-        info = stitch_amd.ops.jpeg_probe(data)
+        info = stitch_amd.ops.jpeg_probe(data, restart=True)
         if info is None:
             print(f"gpu_decode: {data_path} decoded with Pillow ({name} is outside the GPU decoder's contract)", flush=True)
             return decodeSingleData(data_path, img1_name, img2_name)
@@ -151,8 +155,10 @@ def to_pillow(t):
 
 
 def jpeg_params_of(cfg):
-    """The `save` keywords the flags --jpeg_quality / --jpeg_subsampling / --jpeg_optimize ask for; None when none is given."""
+    """The `save` keywords the flags --jpeg_quality / --jpeg_subsampling / --jpeg_optimize / --jpeg_restart_blocks / --jpeg_restart_rows ask
+    for; None when none is given."""
     kw = {k: getattr(cfg, "jpeg_" + k) for k in ("quality", "subsampling") if getattr(cfg, "jpeg_" + k, None) is not None}
+    kw.update({"restart_marker_" + k: getattr(cfg, "jpeg_restart_" + k) for k in ("blocks", "rows") if getattr(cfg, "jpeg_restart_" + k, None) is not None})
     if getattr(cfg, "jpeg_optimize", False):
         kw["optimize"] = True
     return kw or None
@@ -167,14 +173,15 @@ class _Saver:
     byte) on the caller's stream; nothing is read back until ``flush`` (the end of a pair), which reads the byte counts of all
     pending files together, copies exactly those bytes to the host in one transfer and hands the plain file writes to ``pool``.
 
-    ``jpeg_params``: Pillow's `save` keywords ``quality``, ``subsampling``, ``optimize`` for every file, on both paths (`jpeg_params_of`);
+    ``jpeg_params``: Pillow's `save` keywords ``quality``, ``subsampling``, ``optimize``, ``restart_marker_blocks``, ``restart_marker_rows`` for
+    every file, on both paths (`jpeg_params_of`);
     ``subsampling`` is never passed for an L array."""
 
     def __init__(self, pool=None, gpu_jpeg=False, jpeg_params=None):
         self.pool, self.futures, self.gpu_jpeg = pool, [], gpu_jpeg
         self.pending = []
         self.jpeg_params = dict(jpeg_params or {})
-        unknown = set(self.jpeg_params) - {"quality", "subsampling", "optimize"}
+        unknown = set(self.jpeg_params) - {"quality", "subsampling", "optimize", "restart_marker_blocks", "restart_marker_rows"}
         if unknown:
             raise ValueError(f"jpeg_params: unknown keys {sorted(unknown)}")
 

@@ -65,7 +65,8 @@ class MlpDesc(C.Structure):
 class JpegDecParams(C.Structure):
     """Mirror of ``st_jpeg_dec_params``."""
     _fields_ = ([(n, C.c_int32) for n in ("H", "W", "ncomp", "hs", "vs")] + [(n, C.c_int32 * 3) for n in ("tq", "td", "ta")]
-                + [(n, C.c_int32 * 2) for n in ("q_off", "dc_off", "ac_off")] + [("scan_off", C.c_int32), ("scan_len", C.c_int32)])
+                + [(n, C.c_int32 * 2) for n in ("q_off", "dc_off", "ac_off")]
+                + [(n, C.c_int32) for n in ("scan_off", "scan_len", "restart_interval", "reserved")])
 
 
 class JpegEncParams(C.Structure):

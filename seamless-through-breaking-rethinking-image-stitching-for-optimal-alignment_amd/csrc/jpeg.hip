@@ -27,74 +27,16 @@
 #include "jpeg_tables.h"
 #include "jpeg_huff_core.h"
 #include "jpeg_scan.h"
+#include "jpeg_enc_core.h"
+#include "jpeg_rst.h"
 #include "../../include/stitch_gfx950.h"
 
 namespace {
 
-constexpr int kDhtMax = 16 + 256;
-struct JTabs {                         // the four tables in DHT order: DC0, AC0, DC1, AC1
-    uint32_t code[4][256];             // by symbol (DC: the category): code | length << 16
-    uint8_t dht[4][kDhtMax];           // the DHT payload behind the Tc / Th byte: 16 counts, then the symbols
-    int32_t dht_len[4];
-};
-
-constexpr JTabs make_std() {           // ITU-T T.81 Annex K (csrc/jpeg_tables.h), canonical codes (Annex C)
-    JTabs t{};
-    for (int c = 0; c < 2; ++c) {
-        for (int ac = 0; ac < 2; ++ac) {
-            const int* bits = ac ? kAcBits[c] : kDcBits[c];
-            const int nsym = ac ? 162 : 12, i = 2 * c + ac;
-            uint32_t code = 0;
-            int k = 0;
-            for (int len = 1; len <= 16; ++len) {
-                t.dht[i][len - 1] = (uint8_t)bits[len - 1];
-                for (int j = 0; j < bits[len - 1]; ++j, ++k) t.code[i][ac ? kAcVals[c][k] : k] = code++ | ((uint32_t)len << 16);
-                code <<= 1;
-            }
-            for (int j = 0; j < nsym; ++j) t.dht[i][16 + j] = (uint8_t)(ac ? kAcVals[c][j] : j);
-            t.dht_len[i] = 16 + nsym;
-        }
-    }
-    return t;
-}
-
-struct JIzz {
-    uint8_t v[64];                     // natural index -> zigzag position
-};
-constexpr JIzz make_izz() {
-    JIzz z{};
-    for (int i = 0; i < 64; ++i) z.v[kZigzag[i]] = (uint8_t)i;
-    return z;
-}
-
-// SOI + APP0, DQT x n, SOF0, DHT x 2n, SOS: what write_header writes.  (All four lengths are read, needed or not: four loads in flight, where a
-// loop over the tables in use would wait for each -- in every workgroup of the stuff kernel.)
-constexpr uint32_t header_bytes(int ncomp, const JTabs& tabs) {
-    const uint32_t luma = 69u + 2 * 5u + (uint32_t)tabs.dht_len[0] + (uint32_t)tabs.dht_len[1];
-    const uint32_t chroma = 69u + 2 * 5u + (uint32_t)tabs.dht_len[2] + (uint32_t)tabs.dht_len[3];
-    return 20u + (10u + 3 * ncomp) + (8u + 2 * ncomp) + luma + (ncomp == 3 ? chroma : 0u);
-}
-
-constexpr JTabs kStdHost = make_std();
-// no table has more symbols than the Annex K ones, so no header is longer than theirs
-constexpr uint32_t kStdHeaderBytes[2] = {header_bytes(1, kStdHost), header_bytes(3, kStdHost)};
-static_assert(kStdHeaderBytes[0] == 328 && kStdHeaderBytes[1] == 623, "header sizes of the contract");
-__device__ const JTabs g_std = make_std();
 __device__ const JIzz g_izz = make_izz();
-
-struct JDev {                          // the workspace's table area (optimize only)
-    JTabs tabs;
-    uint32_t hist[4][kJhEntries];
-};
 
 struct JQuant {
     uint16_t q8[2][64];                // natural order: the divisor of the scaled-by-8 DCT output, quantiser << 3
-};
-
-struct JHeader {
-    int32_t H, W, ncomp, hs, vs;
-    uint32_t std_bytes;                // the header's length with the Annex K tables: the plain path starts without a read for it
-    uint8_t q[2][64];                  // zigzag order, as DQT lists them
 };
 
 // ---- sizes ------------------------------------------------------------------------------------------------------------------------
@@ -120,12 +62,19 @@ struct JGeom {
 
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-bool make_geom(int32_t H, int32_t W, int32_t ch, const st_jpeg_enc_params* p, JGeom& g) {
+// restart intervals (reserved[0] = Ri MCUs > 0, csrc/jpeg_rst.hip): n = ceil(MCUs / Ri) intervals.  Each adds at most 7 padding bits to the
+// stream (counted as a byte, doubled like every byte for stuffing: 2 bytes of the file) and one two-byte marker; the DRI segment is 6 bytes.
+// The workspace grows by the stream's share of that and by two tables of n + 1 words behind the stream.
+struct JRstGeom {
+    uint32_t ri, nint;
+    size_t off_pad, off_ibyte;
+};
+
+bool make_geom(int32_t H, int32_t W, int32_t ch, const st_jpeg_enc_params* p, JGeom& g, JRstGeom* rst = nullptr) {
     if (!p || (ch != 1 && ch != 3) || H < 1 || H > 65535 || W < 1 || W > 65535 || (int64_t)H * W > kMaxPixels) return false;
     if (p->quality < 1 || p->quality > 100 || (p->optimize != 0 && p->optimize != 1)) return false;
     if (!((p->hs == 1 && p->vs == 1) || (ch == 3 && p->hs == 2 && (p->vs == 1 || p->vs == 2)))) return false;
-    for (int i = 0; i < 4; ++i)
-        if (p->reserved[i]) return false;
+    if (p->reserved[0] < 0 || p->reserved[0] > 65535 || p->reserved[1] || p->reserved[2] || p->reserved[3]) return false;
     g.H = H, g.W = W, g.ch = ch, g.stride = 0;
     g.mcu_cols = (W + 8 * p->hs - 1) / (8 * p->hs), g.mcu_rows = (H + 8 * p->vs - 1) / (8 * p->vs);
     g.wib = (W + 7) / 8, g.hib = (H + 7) / 8;
@@ -138,7 +87,8 @@ bool make_geom(int32_t H, int32_t W, int32_t ch, const st_jpeg_enc_params* p, JG
         g.units = g.hib * ((g.wib + 3) / 4);
         g.nblocks = (uint32_t)g.wib * (uint32_t)g.hib;
     }
-    const uint64_t bits = (uint64_t)g.nblocks * kMaxBlockBits;
+    const uint32_t ri = (uint32_t)p->reserved[0], nmcu = g.nblocks / (uint32_t)g.nb, nint = ri ? (nmcu + ri - 1) / ri : 0u;
+    const uint64_t bits = (uint64_t)g.nblocks * kMaxBlockBits + 8u * (uint64_t)nint;
     const uint64_t bytes = (bits + 7) / 8;
     g.stream_words = (uint32_t)((bits + 31) / 32) + 4;
     g.nchunks = (uint32_t)((bytes + kChunk - 1) / kChunk);
@@ -148,7 +98,10 @@ bool make_geom(int32_t H, int32_t W, int32_t ch, const st_jpeg_enc_params* p, JG
     g.off_dev = g.off_tot + 16;
     g.off_stream = g.off_dev + (p->optimize ? align16(sizeof(JDev)) : 0);      // the plain path has no table area and reads none
     g.ws_bytes = g.off_stream + align16((size_t)g.stream_words * 4);
-    g.out_bytes = (size_t)kStdHeaderBytes[ch == 3] + 2 * (size_t)bytes + 2;
+    const size_t off_pad = g.ws_bytes, off_ibyte = off_pad + align16((size_t)(nint + 1) * 4);
+    if (ri) g.ws_bytes = off_ibyte + align16((size_t)(nint + 1) * 4);
+    if (rst) *rst = JRstGeom{ri, nint, off_pad, off_ibyte};
+    g.out_bytes = (size_t)kStdHeaderBytes[ch == 3] + (ri ? 6u : 0u) + 2 * (size_t)bytes + 2 * (size_t)nint + 2;
     return g.ws_bytes <= 0x7fffffffu && g.out_bytes <= 0x7fffffffu;
 }
 
@@ -283,62 +236,6 @@ __global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restr
 }
 
 // ---- entropy coding ---------------------------------------------------------------------------------------------------------------
-struct HuffLds {
-    uint32_t dc[2][16];
-    uint32_t ac[2][256];
-};
-
-__device__ __forceinline__ void load_huff(HuffLds& h, const JTabs* __restrict__ tabs) {
-    for (int i = threadIdx.x; i < 512; i += blockDim.x) h.ac[i >> 8][i & 255] = tabs->code[2 * (i >> 8) + 1][i & 255];
-    if (threadIdx.x < 32) h.dc[threadIdx.x >> 4][threadIdx.x & 15] = tabs->code[2 * (threadIdx.x >> 4)][threadIdx.x & 15];
-    __syncthreads();
-}
-
-// scan-order predecessor of block b inside its component (-1: none) and the block's table (0 luma, 1 chroma)
-__device__ __forceinline__ int64_t block_pred(uint32_t b, uint32_t nb, uint32_t ny, int& table) {
-    table = 0;
-    if (nb == 1) return (int64_t)b - 1;
-    const uint32_t m = b / nb, j = b - m * nb;
-    table = j >= ny;
-    if (j >= 1 && j < ny) return (int64_t)b - 1;
-    if (m == 0) return -1;
-    return (int64_t)(m - 1) * nb + (j == 0 ? ny - 1 : j);
-}
-
-__device__ __forceinline__ int coef_at(const uint4& w, int e) {      // e: constant after unrolling
-    const uint32_t d = e < 2 ? w.x : e < 4 ? w.y : e < 6 ? w.z : w.w;
-    return (int)(int16_t)((e & 1) ? (d >> 16) : (d & 0xffffu));
-}
-
-__device__ __forceinline__ int magnitude_bits(int v) { return 32 - __clz(abs(v)); }
-
-// the symbols of block b in scan order: dc(category, difference), then per nonzero coefficient zrl(k), the k >= 0 ZRL symbols (0xF0) of a run
-// above 15, and ac(run << 4 | size, value, size) with the rest of the run; EOB is ac(0x00, 0, 0)
-template <class DC, class ZRL, class AC>
-__device__ __forceinline__ void walk_block(const int16_t* __restrict__ coef, uint32_t b, int pred, DC&& dc, ZRL&& zrl, AC&& ac) {
-    const uint4* c4 = (const uint4*)(coef + (size_t)b * 64);
-    int run = 0;
-#pragma unroll 1
-    for (int q = 0; q < 8; ++q) {
-        const uint4 w = c4[q];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int v = coef_at(w, e);
-            if (q == 0 && e == 0) {
-                dc(magnitude_bits(v - pred), v - pred);
-            } else if (v == 0) {
-                ++run;
-            } else {
-                zrl(run >> 4);
-                const int n = magnitude_bits(v);
-                ac(((run & 15) << 4) | n, v, n);
-                run = 0;
-            }
-        }
-    }
-    if (run) ac(0x00, 0, 0);
-}
-
 __global__ __launch_bounds__(256) void jpeg_hist_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ hist, uint32_t nblocks, uint32_t nb, uint32_t ny) {
     __shared__ uint32_t s_hist[4 * kJhEntries];
     for (int i = threadIdx.x; i < 4 * kJhEntries; i += 256) s_hist[i] = 0u;
@@ -456,29 +353,6 @@ __global__ __launch_bounds__(256) void jpeg_zero_kernel(uint32_t* __restrict__ s
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < words; i += gridDim.x * 256) stream[i] = 0u;
 }
 
-struct BitWriter {
-    uint32_t* word;      // next word of the stream (bytes in stream order: the big-endian word, byte-swapped)
-    uint32_t* end;       // one past the stream's capacity: nothing is written from here on
-    uint64_t acc;        // pending bits in the low `n`
-    int n;
-    bool first;          // the next word is shared with the blocks before this one
-};
-
-__device__ __forceinline__ void put_bits(BitWriter& w, uint32_t v, int len) {
-    w.acc = (w.acc << len) | v;
-    w.n += len;
-    if (w.n >= 32) {
-        w.n -= 32;
-        const uint32_t word = __builtin_bswap32((uint32_t)(w.acc >> w.n));
-        if (w.word < w.end) {
-            if (w.first) atomicOr(w.word, word);
-            else *w.word = word;
-        }
-        w.first = false;
-        ++w.word;
-    }
-}
-
 __global__ __launch_bounds__(256) void jpeg_pack_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ off, const uint32_t* __restrict__ total_bits,
                                                         uint32_t* __restrict__ stream, uint32_t cap_words, const JDev* __restrict__ dev, uint32_t nblocks, uint32_t nb,
                                                         uint32_t ny) {
@@ -507,16 +381,6 @@ __global__ __launch_bounds__(256) void jpeg_pack_kernel(const int16_t* __restric
     if (w.n > 0 && w.word < w.end) atomicOr(w.word, __builtin_bswap32((uint32_t)(w.acc << (32 - w.n))));
 }
 
-__device__ __forceinline__ uint32_t ff_bytes(uint2 d, uint32_t i0, uint32_t nbytes) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t byte = ((k < 4 ? d.x : d.y) >> ((k & 3) * 8)) & 255u;
-        c += (i0 + k < nbytes && byte == 255u) ? 1u : 0u;
-    }
-    return c;
-}
-
 // chunks behind the stream get no count: jpeg_scan_kernel bounds itself with the same total_bits
 __global__ __launch_bounds__(256) void jpeg_count_kernel(const uint32_t* __restrict__ stream, const uint32_t* __restrict__ total_bits, uint32_t* __restrict__ cnt) {
     __shared__ uint32_t s_wave[4];
@@ -527,47 +391,6 @@ __global__ __launch_bounds__(256) void jpeg_count_kernel(const uint32_t* __restr
     uint32_t ex;
     const uint32_t all = block_sum_256(ff_bytes(d, i0, nbytes), ex, s_wave);
     if (threadIdx.x == 0) cnt[blockIdx.x] = all;
-}
-
-// SOI, APP0, DQT x n, SOF0, DHT x n (DC0, AC0, DC1, AC1), SOS; one workgroup
-__device__ __forceinline__ void write_header(uint8_t* __restrict__ out, const JHeader& hp, const JTabs* __restrict__ tabs) {
-    const int ntab = hp.ncomp == 3 ? 2 : 1, nc = hp.ncomp, tid = threadIdx.x;
-    uint32_t n = 0;
-    if (tid < 20) {
-        const uint32_t lo = 0xE0FFD8FFu, mid = 0x464A1000u;                      // FF D8 FF E0 | 00 10 'J' 'F'
-        const uint8_t rest[12] = {'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-        uint8_t v = 0;
-        if (tid < 4) v = (uint8_t)(lo >> (8 * tid));
-        else if (tid < 8) v = (uint8_t)(mid >> (8 * (tid - 4)));
-#pragma unroll
-        for (int k = 0; k < 12; ++k)
-            if (tid == 8 + k) v = rest[k];
-        out[tid] = v;
-    }
-    n = 20;
-    for (int c = 0; c < ntab; ++c, n += 69) {
-        if (tid < 5) out[n + tid] = tid == 0 ? 0xFF : tid == 1 ? 0xDB : tid == 2 ? 0 : tid == 3 ? 67 : (uint8_t)c;
-        if (tid < 64) out[n + 5 + tid] = hp.q[c][tid];
-    }
-    if (tid == 0) {
-        uint8_t* h = out + n;
-        h[0] = 0xFF, h[1] = 0xC0, h[2] = 0, h[3] = (uint8_t)(8 + 3 * nc), h[4] = 8;
-        h[5] = (uint8_t)(hp.H >> 8), h[6] = (uint8_t)(hp.H & 255), h[7] = (uint8_t)(hp.W >> 8), h[8] = (uint8_t)(hp.W & 255), h[9] = (uint8_t)nc;
-        for (int c = 0; c < nc; ++c) h[10 + 3 * c] = (uint8_t)(c + 1), h[11 + 3 * c] = c ? 0x11 : (uint8_t)(hp.hs << 4 | hp.vs), h[12 + 3 * c] = c ? 1 : 0;
-    }
-    n += 10 + 3 * nc;
-    for (int i = 0; i < 2 * ntab; ++i) {
-        const uint32_t len = (uint32_t)tabs->dht_len[i];
-        if (tid < 5) out[n + tid] = tid == 0 ? 0xFF : tid == 1 ? 0xC4 : tid == 2 ? (uint8_t)((len + 3) >> 8) : tid == 3 ? (uint8_t)((len + 3) & 255) : (uint8_t)((i & 1) << 4 | (i >> 1));
-        for (uint32_t k = tid; k < len; k += 256) out[n + 5 + k] = tabs->dht[i][k];
-        n += 5 + len;
-    }
-    if (tid == 0) {
-        uint8_t* h = out + n;
-        h[0] = 0xFF, h[1] = 0xDA, h[2] = 0, h[3] = (uint8_t)(6 + 2 * nc), h[4] = (uint8_t)nc;
-        for (int c = 0; c < nc; ++c) h[5 + 2 * c] = (uint8_t)(c + 1), h[6 + 2 * c] = c ? 0x11 : 0x00;
-        h[5 + 2 * nc] = 0, h[6 + 2 * nc] = 63, h[7 + 2 * nc] = 0;
-    }
 }
 
 __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint32_t* __restrict__ stream, const uint32_t* __restrict__ totals, const uint32_t* __restrict__ cnt_off,
@@ -635,7 +458,8 @@ extern "C" int st_jpeg_max_bytes_ex(int32_t H, int32_t W, int32_t channels, cons
 extern "C" int st_jpeg_encode_u8_ex(const void* src, int32_t H, int32_t W, int32_t channels, int64_t row_stride, const st_jpeg_enc_params* params, void* out,
                                     int64_t out_capacity, int32_t* out_nbytes, void* workspace, int64_t workspace_bytes, void* stream) {
     JGeom g;
-    if (!src || !out || !out_nbytes || !workspace || !make_geom(H, W, channels, params, g)) return ST_EINVAL;
+    JRstGeom rg;
+    if (!src || !out || !out_nbytes || !workspace || !make_geom(H, W, channels, params, g, &rg)) return ST_EINVAL;
     if (row_stride < (int64_t)W * channels || row_stride > 0x7fffffff || ((uintptr_t)workspace & 15)) return ST_EINVAL;
     if (out_capacity < (int64_t)g.out_bytes || workspace_bytes < (int64_t)g.ws_bytes) return ST_EINVAL;
     g.stride = (int32_t)row_stride;
@@ -667,6 +491,29 @@ extern "C" int st_jpeg_encode_u8_ex(const void* src, int32_t H, int32_t W, int32
     else
         hipLaunchKernelGGL((jpeg_blocks_kernel<3, 2, 2>), dim3(grid), dim3(256), 0, st, (const uint8_t*)src, coef, g, qt, hist);
     ST_CHECK_LAUNCH();
+    const unsigned zero_grid = (g.stream_words + 255) / 256 < 512 ? (g.stream_words + 255) / 256 : 512;
+    if (rg.ri) {                                                       // restart intervals: what differs is csrc/jpeg_rst.hip's
+        JpegRstEncode e;
+        e.coef = coef, e.len = len, e.tot = tot, e.pad = (uint32_t*)(ws + rg.off_pad), e.ibyte = (uint32_t*)(ws + rg.off_ibyte);
+        e.stream = bits, e.stream_words = g.stream_words, e.dev = dev;
+        e.nblocks = g.nblocks, e.nb = nb, e.ny = ny, e.ri = rg.ri, e.nint = rg.nint, e.nchunks = g.nchunks;
+        e.cnt = cnt, e.out = (uint8_t*)out, e.out_nbytes = out_nbytes, e.header = &hp, e.st = st;
+        int rc;
+        if (dev) {
+            if ((rc = st_jpeg_rst_hist(e)) != ST_OK) return rc;
+            hipLaunchKernelGGL(jpeg_table_kernel, dim3(channels == 3 ? 4 : 2), dim3(64), 0, st, dev);
+            ST_CHECK_LAUNCH();
+        }
+        if ((rc = st_jpeg_rst_offsets(e)) != ST_OK) return rc;
+        hipLaunchKernelGGL(jpeg_zero_kernel, dim3(zero_grid), dim3(256), 0, st, bits, (const uint32_t*)tot, g.stream_words);
+        ST_CHECK_LAUNCH();
+        if ((rc = st_jpeg_rst_pack(e)) != ST_OK) return rc;
+        hipLaunchKernelGGL(jpeg_count_kernel, dim3(g.nchunks), dim3(256), 0, st, (const uint32_t*)bits, (const uint32_t*)tot, cnt);
+        ST_CHECK_LAUNCH();
+        hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, g.nchunks, (const uint32_t*)tot, tot + 1);
+        ST_CHECK_LAUNCH();
+        return st_jpeg_rst_stuff(e);
+    }
     if (dev) {
         hipLaunchKernelGGL(jpeg_hist_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, hist, g.nblocks, nb, ny);
         ST_CHECK_LAUNCH();
@@ -677,7 +524,6 @@ extern "C" int st_jpeg_encode_u8_ex(const void* src, int32_t H, int32_t W, int32
     ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, len, g.nblocks, (const uint32_t*)nullptr, tot);
     ST_CHECK_LAUNCH();
-    const unsigned zero_grid = (g.stream_words + 255) / 256 < 512 ? (g.stream_words + 255) / 256 : 512;
     hipLaunchKernelGGL(jpeg_zero_kernel, dim3(zero_grid), dim3(256), 0, st, bits, (const uint32_t*)tot, g.stream_words);
     ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_pack_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, (const uint32_t*)len, (const uint32_t*)tot, bits, g.stream_words,

@@ -15,9 +15,13 @@
 //   jpegd_dc_kernel       one workgroup per component: prefix sum of the DC differences
 //   jpegd_idct_kernel     one wave per 8 blocks: dequantisation, column and row pass of jidctint.c through LDS, range limit -> sample planes
 //   jpegd_pixels_kernel   one thread per pixel: fancy h2v1 / h2v2 upsampling (replication at chroma width <= 2), colour conversion, HWC store
+//
+// A file with restart intervals (st_jpeg_dec_params.restart_interval > 0) takes the zero, IDCT and pixel kernels from here; everything between
+// the file's bytes and the DC-predicted coefficients is csrc/jpeg_rst.hip's (st_jpeg_rst_entropy, csrc/jpeg_rst.h).
 #include "common.h"
 #include "jpeg_dec_core.h"
 #include "jpeg_scan.h"
+#include "jpeg_rst.h"
 #include "../../include/stitch_gfx950.h"
 
 namespace {
@@ -405,6 +409,7 @@ __global__ __launch_bounds__(256) void jpegd_pixels_kernel(const uint8_t* __rest
 
 bool params_ok(const st_jpeg_dec_params* p, int64_t nbytes, DGeom& g) {
     if (nbytes < 1 || nbytes > kMaxFileBytes) return false;
+    if (p->restart_interval < 0 || p->restart_interval > 65535 || p->reserved != 0) return false;
     if (!make_geom(p->H, p->W, p->ncomp, p->hs, p->vs, p->scan_len, g)) return false;
     if (p->scan_off < 0 || (int64_t)p->scan_off + p->scan_len > nbytes) return false;
     for (int c = 0; c < p->ncomp; ++c) {
@@ -413,6 +418,11 @@ bool params_ok(const st_jpeg_dec_params* p, int64_t nbytes, DGeom& g) {
         if (q < 0 || q + 64 > nbytes || d < 0 || d + 16 > nbytes || a < 0 || a + 16 > nbytes) return false;
     }
     return true;
+}
+
+// with restart intervals: the plain layout (its stream, coefficients and planes are used), then the tables of csrc/jpeg_rst.hip
+size_t workspace_bytes(const DGeom& g, int32_t restart_interval) {
+    return g.ws_bytes + (restart_interval > 0 ? st_jpeg_rst_workspace_bytes(g.scan_len, (uint32_t)g.mcu_rows * (uint32_t)g.mcu_cols, (uint32_t)restart_interval) : 0);
 }
 
 }  // namespace
@@ -424,11 +434,20 @@ extern "C" int st_jpeg_dec_workspace_bytes(int32_t H, int32_t W, int32_t ncomp, 
     return make_geom(H, W, ncomp, hs, vs, scan_len, g) && g.ws_bytes <= 0x7fffffff ? (int)g.ws_bytes : 0;
 }
 
+extern "C" int st_jpeg_dec_workspace_bytes_ex(const st_jpeg_dec_params* p) {
+    DGeom g;
+    if (!p || p->restart_interval < 0 || p->restart_interval > 65535 || p->reserved != 0 || !make_geom(p->H, p->W, p->ncomp, p->hs, p->vs, p->scan_len, g)) return 0;
+    const size_t n = workspace_bytes(g, p->restart_interval);
+    return n <= 0x7fffffff ? (int)n : 0;
+}
+
 extern "C" int st_jpeg_decode_u8(const void* file_dev, int64_t nbytes, const st_jpeg_dec_params* params, void* out, int64_t row_stride, int32_t* status_dev,
                                  void* workspace, int64_t workspace_bytes, void* stream) {
     DGeom g;
-    if (!file_dev || !params || !out || !status_dev || !workspace || !params_ok(params, nbytes, g) || g.ws_bytes > 0x7fffffff) return ST_EINVAL;
-    if (row_stride < (int64_t)g.W * g.ncomp || row_stride > 0x7fffffff || ((uintptr_t)workspace & 15) || workspace_bytes < (int64_t)g.ws_bytes) return ST_EINVAL;
+    if (!file_dev || !params || !out || !status_dev || !workspace || !params_ok(params, nbytes, g)) return ST_EINVAL;
+    const size_t need = ::workspace_bytes(g, params->restart_interval);
+    if (need > 0x7fffffff) return ST_EINVAL;
+    if (row_stride < (int64_t)g.W * g.ncomp || row_stride > 0x7fffffff || ((uintptr_t)workspace & 15) || workspace_bytes < (int64_t)need) return ST_EINVAL;
     g.stride = (int32_t)row_stride;
     hipStream_t st = (hipStream_t)stream;
     const uint8_t* file = (const uint8_t*)file_dev;
@@ -456,28 +475,43 @@ extern "C" int st_jpeg_decode_u8(const void* file_dev, int64_t nbytes, const st_
     }
     a.nb = g.nb, a.ny = g.ny, a.scan_len = g.scan_len, a.nblocks = g.nblocks;
     const uint8_t* scan = file + params->scan_off;
-
-    hipLaunchKernelGGL(jpegd_count_kernel, dim3(g.nchunks), dim3(256), 0, st, scan, g.scan_len, cnt);
-    ST_CHECK_LAUNCH();
-    hipError_t e = st_jpeg_scan_u32(cnt, g.nchunks, tot, st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(jpegd_unstuff_kernel, dim3(g.nchunks), dim3(256), 0, st, scan, g.scan_len, (const uint32_t*)cnt, (const uint32_t*)tot, bytes);
-    ST_CHECK_LAUNCH();
-    for (uint32_t r = 0; r < g.nwg; ++r) {
-        hipLaunchKernelGGL(jpegd_sync_kernel, dim3(g.nwg), dim3(kSyncThreads), 0, st, a, (const uint32_t*)bytes, stream_words, (const uint32_t*)tot, state, cap, bnd, flags, r,
-                           g.nwg);
+    const uint32_t coef_vec = g.nblocks * 8u;                              // uint4 per block: 8
+    const uint32_t zero_wgs = (coef_vec + 255) / 256 < 1024 ? (coef_vec + 255) / 256 : 1024;
+    if (params->restart_interval > 0) {                                    // the entropy decode of csrc/jpeg_rst.hip, behind the plain layout
+        hipLaunchKernelGGL(jpegd_zero_kernel, dim3(zero_wgs), dim3(256), 0, st, (uint4*)coef, coef_vec);
+        ST_CHECK_LAUNCH();
+        JpegRstDecode d;
+        d.file = file, d.nbytes = a.nbytes;
+        for (int i = 0; i < 2; ++i) d.dc_off[i] = a.dc_off[i], d.ac_off[i] = a.ac_off[i];
+        d.nb = g.nb, d.ny = g.ny, d.td_bits = a.td_bits, d.ta_bits = a.ta_bits;
+        d.scan_off = (uint32_t)params->scan_off, d.scan_len = g.scan_len;
+        d.nmcu = (uint32_t)g.mcu_rows * (uint32_t)g.mcu_cols, d.ri = (uint32_t)params->restart_interval;
+        d.stream = bytes, d.stream_words = stream_words;
+        d.coef = coef, d.status = status_dev, d.ws = ws + g.ws_bytes, d.st = st;
+        const int rc = st_jpeg_rst_entropy(d);
+        if (rc != ST_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(jpegd_count_kernel, dim3(g.nchunks), dim3(256), 0, st, scan, g.scan_len, cnt);
+        ST_CHECK_LAUNCH();
+        hipError_t e = st_jpeg_scan_u32(cnt, g.nchunks, tot, st);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(jpegd_unstuff_kernel, dim3(g.nchunks), dim3(256), 0, st, scan, g.scan_len, (const uint32_t*)cnt, (const uint32_t*)tot, bytes);
+        ST_CHECK_LAUNCH();
+        for (uint32_t r = 0; r < g.nwg; ++r) {
+            hipLaunchKernelGGL(jpegd_sync_kernel, dim3(g.nwg), dim3(kSyncThreads), 0, st, a, (const uint32_t*)bytes, stream_words, (const uint32_t*)tot, state, cap, bnd, flags,
+                               r, g.nwg);
+            ST_CHECK_LAUNCH();
+        }
+        e = st_jpeg_scan_u32(state + 4 * (size_t)cap, cap, tot + 1, st);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(jpegd_zero_kernel, dim3(zero_wgs), dim3(256), 0, st, (uint4*)coef, coef_vec);
+        ST_CHECK_LAUNCH();
+        hipLaunchKernelGGL(jpegd_write_kernel, dim3(g.nwg), dim3(kSyncThreads), 0, st, a, (const uint32_t*)bytes, stream_words, (const uint32_t*)tot, (const uint32_t*)state, cap,
+                           coef, status_dev);
+        ST_CHECK_LAUNCH();
+        hipLaunchKernelGGL(jpegd_dc_kernel, dim3(g.ncomp), dim3(1024), 0, st, coef, (uint32_t)g.mcu_rows * (uint32_t)g.mcu_cols, g.nb, g.ny);
         ST_CHECK_LAUNCH();
     }
-    e = st_jpeg_scan_u32(state + 4 * (size_t)cap, cap, tot + 1, st);
-    if (e != hipSuccess) return (int)e;
-    const uint32_t coef_vec = g.nblocks * 8u;                              // uint4 per block: 8
-    hipLaunchKernelGGL(jpegd_zero_kernel, dim3((coef_vec + 255) / 256 < 1024 ? (coef_vec + 255) / 256 : 1024), dim3(256), 0, st, (uint4*)coef, coef_vec);
-    ST_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpegd_write_kernel, dim3(g.nwg), dim3(kSyncThreads), 0, st, a, (const uint32_t*)bytes, stream_words, (const uint32_t*)tot, (const uint32_t*)state, cap, coef,
-                       status_dev);
-    ST_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpegd_dc_kernel, dim3(g.ncomp), dim3(1024), 0, st, coef, (uint32_t)g.mcu_rows * (uint32_t)g.mcu_cols, g.nb, g.ny);
-    ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpegd_idct_kernel, dim3((g.nblocks + 31) / 32), dim3(256), 0, st, (const int16_t*)coef, file, q_off[0], q_off[1], q_off[2], planes, g);
     ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpegd_pixels_kernel, dim3((g.W + 255) / 256, g.H), dim3(256), 0, st, (const uint8_t*)planes, (uint8_t*)out, g);

@@ -58,7 +58,7 @@ def _read_jpeg_pair(paths):
     for path in paths:
         with open(path, "rb") as f:
             d = f.read()
-        i = ops.jpeg_probe(d)
+        i = ops.jpeg_probe(d, restart=True)
         if i is None:
             return None, f"{path} is outside the GPU decoder's contract"
         if i.ncomp != 3:

@@ -4,7 +4,11 @@ Taken: one SOF0 frame at 8 bits; one component, or three (YCbCr: JFIF, or no Ado
 2x2 and chroma 1x1; one interleaved scan over all 63 AC coefficients; 8-bit DQT entries; any DHT tables 0..1; no restart interval; H * W <=
 2^24; APPn / COM segments are skipped.  Everything else -- progressive, arithmetic, 12-bit, DRI, 4:4:0 and other factors, four components,
 Adobe transform 0, several scans, a marker other than FF00 inside the scan -- is unsupported: `probe` returns None and nothing touches the
-device."""
+device.
+
+`probe(data, restart=True)` also takes a file with one restart interval Ri > 0 (the last DRI in front of SOS) whose scan holds exactly
+ceil(MCUs / Ri) - 1 restart markers, RST0, RST1, ... RST7, RST0, ... in that order (csrc/jpeg_rst.hip; contract: README.md "Restart
+intervals", tests/_jpeg_rst_ref.py).  A marker without DRI, a missing one, one too many or one out of order: None."""
 from typing import NamedTuple, Tuple
 
 SAMPLINGS = ((1, 1), (2, 1), (2, 2))
@@ -29,16 +33,18 @@ class JpegInfo(NamedTuple):
     scan_off: int
     scan_len: int
     nbytes: int
+    restart_interval: int = 0        # MCUs per restart interval, 0: none
 
 
-def probe(data):
-    """JpegInfo of a file the decoder takes, or None: the file keeps the Pillow path.  `data`: bytes-like."""
+def probe(data, restart=False):
+    """JpegInfo of a file the decoder takes, or None: the file keeps the Pillow path.  `data`: bytes-like.  restart: also take a file with a
+    restart interval and the restart markers that belong to it."""
     d = bytes(data)
     n = len(d)
     if n < 4 or n > MAX_FILE_BYTES or d[0:2] != b"\xff\xd8":
         return None
     q_off, dc_off, ac_off = [-1, -1], [-1, -1], [-1, -1]
-    frame, jfif, adobe = None, False, None
+    frame, jfif, adobe, ri = None, False, None, 0
     p = 2
     while True:
         if p + 4 > n or d[p] != 0xFF:
@@ -77,7 +83,10 @@ def probe(data):
             comps = [(d[body + 6 + 3 * i], d[body + 7 + 3 * i] >> 4, d[body + 7 + 3 * i] & 15, d[body + 8 + 3 * i]) for i in range(nc)]
             frame = (H, W, comps)
         elif m == 0xDD:
-            if L != 4 or d[body] or d[body + 1]:
+            if L != 4:
+                return None
+            ri = (d[body] << 8) | d[body + 1]
+            if ri and not restart:
                 return None
         elif m == 0xE0:
             jfif = jfif or d[body:body + 5] == b"JFIF\x00"
@@ -119,6 +128,8 @@ def probe(data):
             return None
     scan_off = end
     q = scan_off
+    nrst = 0                                                         # restart markers met so far: the next one is RST(nrst & 7)
+    want_rst = -(-(-(-H // (8 * vs)) * -(-W // (8 * hs))) // ri) - 1 if ri else 0
     while True:                                                      # the scan runs to EOI, or to the end of a cut file
         q = d.find(b"\xff", q)
         if q < 0 or q + 1 >= n:
@@ -127,10 +138,14 @@ def probe(data):
         if d[q + 1] == 0:
             q += 2
             continue
-        if d[q + 1] != 0xD9:                                         # RSTn, a further scan, fill bytes
+        if d[q + 1] == 0xD0 + (nrst & 7) and nrst < want_rst:        # the restart marker that is due
+            nrst += 1
+            q += 2
+            continue
+        if d[q + 1] != 0xD9:                                         # an RSTn that is not due, a further scan, fill bytes
             return None
         scan_len = q - scan_off
         break
-    if scan_len < 1:
+    if scan_len < 1 or nrst != want_rst:
         return None
-    return JpegInfo(H, W, nc, hs, vs, tuple(tq), tuple(td), tuple(ta), tuple(q_off), tuple(dc_off), tuple(ac_off), scan_off, scan_len, n)
+    return JpegInfo(H, W, nc, hs, vs, tuple(tq), tuple(td), tuple(ta), tuple(q_off), tuple(dc_off), tuple(ac_off), scan_off, scan_len, n, ri)

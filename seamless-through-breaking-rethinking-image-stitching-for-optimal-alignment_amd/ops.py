@@ -780,10 +780,14 @@ def load_rgb8(src_u8_hwc, out=None):
 _JPEG_SAMPLING = {None: (2, 2), 2: (2, 2), 1: (2, 1), 0: (1, 1)}        # Pillow's `subsampling` -> luma sampling factors
 
 
-def _jpeg_enc_params(channels, quality, subsampling, optimize):
+def _jpeg_enc_params(channels, quality, subsampling, optimize, W=0, restart_marker_blocks=None, restart_marker_rows=None):
     """The `JpegEncParams` of Pillow's `save` keywords, or None when every keyword is at its default (`st_jpeg_encode_u8`, which fills in
-    Pillow's defaults itself)."""
-    if quality is None and subsampling is None and not optimize:
+    Pillow's defaults itself).  The restart interval in MCUs (`reserved[0]`) is libjpeg's: with `restart_marker_rows` r > 0
+    min(r * MCUs per row, 65535), rows win over blocks; otherwise `restart_marker_blocks`; 0: none."""
+    for name, v, top in (("restart_marker_blocks", restart_marker_blocks, 65535), ("restart_marker_rows", restart_marker_rows, None)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0 or (top is not None and v > top)):
+            raise ValueError(f"{name} {v!r}: an integer 0..{top if top is not None else ''} expected")
+    if quality is None and subsampling is None and not optimize and not restart_marker_blocks and not restart_marker_rows:
         return None
     if subsampling not in _JPEG_SAMPLING or isinstance(subsampling, bool):
         raise ValueError(f"subsampling {subsampling!r}: None, 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0) expected")
@@ -793,22 +797,25 @@ def _jpeg_enc_params(channels, quality, subsampling, optimize):
     if isinstance(q, bool) or not isinstance(q, int) or not 1 <= q <= 100:
         raise ValueError(f"quality {quality!r}: an integer 1..100 expected")
     hs, vs = _JPEG_SAMPLING[subsampling] if channels == 3 else (1, 1)
-    return JpegEncParams(q, hs, vs, 1 if optimize else 0)
+    prm = JpegEncParams(q, hs, vs, 1 if optimize else 0)
+    prm.reserved[0] = min(restart_marker_rows * -(-W // (8 * hs)), 65535) if restart_marker_rows else (restart_marker_blocks or 0)
+    return prm
 
 
-def jpeg_encode(u8, workspace=None, quality=None, subsampling=None, optimize=False):
+def jpeg_encode(u8, workspace=None, quality=None, subsampling=None, optimize=False, restart_marker_blocks=None, restart_marker_rows=None):
     """out.py:260-312 `Image.fromarray(arr).save(path)` on the GPU: uint8 [H,W,3] (RGB) or [H,W] (L) -> (buf, nbytes), the JPEG file Pillow
     writes, byte for byte.  buf: uint8 device tensor of the worst-case size, nbytes: device int32 [1], the file is buf[:nbytes].  Rows may be
     strided (a column slice of a wider canvas).  No host synchronisation; current stream.
     `quality` (1..100), `subsampling` (RGB only: 0 4:4:4, 1 4:2:2, 2 4:2:0) and `optimize` are Pillow's `save` keywords (`st_jpeg_encode_u8_ex`);
     with all three at their defaults the call goes to `st_jpeg_encode_u8`, the same encoder (csrc/jpeg.hip) at Pillow's defaults -- quality 75,
-    4:2:0, the Annex K tables.
+    4:2:0, the Annex K tables.  `restart_marker_blocks` (MCUs, 0..65535) and `restart_marker_rows` (MCU rows; wins) are Pillow's too: a DRI
+    segment, FF D0..D7 between the intervals, DC predictions restarting (csrc/jpeg_rst.hip); None or 0: no restart interval.
     `workspace`: a uint8 device tensor of at least `jpeg_workspace_bytes` (same keywords) to reuse (stream-ordered: same stream as its last use)."""
     if u8.dtype != torch.uint8 or not (u8.dim() == 2 or (u8.dim() == 3 and u8.shape[2] == 3)):
         raise ValueError(f"uint8 [H,W,3] or [H,W] expected, got {u8.dtype} {tuple(u8.shape)}")
     H, W = u8.shape[:2]
     ch = 3 if u8.dim() == 3 else 1
-    prm = _jpeg_enc_params(ch, quality, subsampling, optimize)
+    prm = _jpeg_enc_params(ch, quality, subsampling, optimize, W, restart_marker_blocks, restart_marker_rows)
     if (W > 1 and u8.stride(1) != ch) or (ch == 3 and u8.stride(2) != 1) or (H > 1 and u8.stride(0) < W * ch):
         u8 = u8.contiguous()
     row_stride = u8.stride(0) if H > 1 else W * ch
@@ -831,8 +838,8 @@ def jpeg_encode(u8, workspace=None, quality=None, subsampling=None, optimize=Fal
     return buf, nbytes
 
 
-def jpeg_workspace_bytes(H, W, channels, quality=None, subsampling=None, optimize=False):
-    prm = _jpeg_enc_params(channels, quality, subsampling, optimize)
+def jpeg_workspace_bytes(H, W, channels, quality=None, subsampling=None, optimize=False, restart_marker_blocks=None, restart_marker_rows=None):
+    prm = _jpeg_enc_params(channels, quality, subsampling, optimize, W, restart_marker_blocks, restart_marker_rows)
     if prm is None:
         return lib.st_jpeg_workspace_bytes(H, W, channels)
     return lib.st_jpeg_workspace_bytes_ex(H, W, channels, C.byref(prm))
@@ -844,24 +851,35 @@ def jpeg_bytes(buf, nbytes):
     return buf[:n].cpu().numpy().tobytes()
 
 
-def jpeg_probe(data):
+def jpeg_probe(data, restart=False):
     """Host-side marker parse of a JPEG file (bytes-like, or a CPU uint8 tensor): the `JpegInfo` `jpeg_decode` needs, or None when the file is
-    outside the decoder's contract (progressive, restart intervals, other sampling factors, ...: jpeg_probe.py) and keeps the Pillow path."""
+    outside the decoder's contract (progressive, restart intervals, other sampling factors, ...: jpeg_probe.py) and keeps the Pillow path.
+    restart=True also takes a file with a restart interval whose markers are all there and in order (`JpegInfo.restart_interval` > 0:
+    csrc/jpeg_rst.hip decodes its entropy-coded part)."""
     if isinstance(data, torch.Tensor):
         data = data.numpy().tobytes()
-    return _jpeg_probe(data)
+    return _jpeg_probe(data, restart=restart)
+
+
+def _jpeg_dec_params(info):
+    return JpegDecParams(info.H, info.W, info.ncomp, info.hs, info.vs, (C.c_int32 * 3)(*info.tq), (C.c_int32 * 3)(*info.td), (C.c_int32 * 3)(*info.ta),
+                         (C.c_int32 * 2)(*info.q_off), (C.c_int32 * 2)(*info.dc_off), (C.c_int32 * 2)(*info.ac_off), info.scan_off, info.scan_len,
+                         info.restart_interval, 0)
 
 
 def jpeg_dec_workspace_bytes(info):
+    if info.restart_interval:
+        return lib.st_jpeg_dec_workspace_bytes_ex(C.byref(_jpeg_dec_params(info)))
     return lib.st_jpeg_dec_workspace_bytes(info.H, info.W, info.ncomp, info.hs, info.vs, info.scan_len)
 
 
 def jpeg_decode(data, info=None, out=None, workspace=None, status=None):
     """evaluate.py / out.py `np.array(Image.open(path))` on the GPU: the file's bytes -> (uint8 [H,W,3] or [H,W,1] device tensor, status), the
     pixels Pillow returns on libjpeg-turbo, bit for bit (csrc/jpeg_dec.hip).  `data`: bytes or a CPU uint8 tensor (uploaded on the current
-    stream; `info` defaults to `jpeg_probe(data)`), or a device uint8 tensor (`info` required).  `out`: a uint8 [H,W,C] device view to decode
+    stream; `info` defaults to `jpeg_probe(data, restart=True)`), or a device uint8 tensor (`info` required).  `out`: a uint8 [H,W,C] device view to decode
     into, rows may be strided.  status: device int32 [1] (or the given one-element int32 device view): 0, or nonzero when the scan ended
-    before the frame's blocks or ran on after them (pixels then unspecified).  No host synchronisation; current stream.
+    before the frame's blocks or ran on after them (pixels then unspecified; with restart intervals: some interval's bytes did, and the MCUs of
+    every other interval are still exact).  No host synchronisation; current stream.
     `workspace`: a uint8 device tensor of at least `jpeg_dec_workspace_bytes(info)` to reuse (stream-ordered)."""
     if isinstance(data, (bytes, bytearray, memoryview)):
         data = torch.frombuffer(bytearray(data), dtype=torch.uint8)
@@ -869,7 +887,7 @@ def jpeg_decode(data, info=None, out=None, workspace=None, status=None):
         raise ValueError(f"uint8 [nbytes] expected, got {data.dtype} {tuple(data.shape)}")
     if not data.is_cuda:
         if info is None:
-            info = jpeg_probe(data)
+            info = jpeg_probe(data, restart=True)
             if info is None:
                 raise StitchErrorBase("jpeg_decode: unsupported file (jpeg_probe returned None)")
         data = data.cuda()              # a blocking copy: the host tensor may be a temporary of this call
@@ -891,8 +909,7 @@ def jpeg_decode(data, info=None, out=None, workspace=None, status=None):
         status = torch.empty((1,), device=data.device, dtype=torch.int32)
     if status.dtype != torch.int32 or status.numel() != 1:
         raise ValueError("status: one int32 element expected")
-    prm = JpegDecParams(H, W, ch, info.hs, info.vs, (C.c_int32 * 3)(*info.tq), (C.c_int32 * 3)(*info.td), (C.c_int32 * 3)(*info.ta),
-                        (C.c_int32 * 2)(*info.q_off), (C.c_int32 * 2)(*info.dc_off), (C.c_int32 * 2)(*info.ac_off), info.scan_off, info.scan_len)
+    prm = _jpeg_dec_params(info)
     check(lib.st_jpeg_decode_u8(_p(data), data.numel(), C.byref(prm), _p(out), row_stride, _p(status), _pc(workspace),
                                 workspace.numel() * workspace.element_size(), _stream()), "st_jpeg_decode_u8")
     return out, status

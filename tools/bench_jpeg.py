@@ -22,6 +22,11 @@
   defaults and at (95, 4:4:4, optimised): every sample is a fresh child process that imports one of the two trees, the two alternate for
   `--rounds` rounds; per row both versions' medians over the rounds and each version's min-max, and whether this tree's median stays within
   the other's median plus the other's own min-max spread; then one traced child per version (200 default encodes of the 548x588 canvas).
+
+    python tools/bench_jpeg.py --restart [--out profiles/jpeg_rst_enc_bench.json]
+
+* restart intervals (csrc/jpeg_rst.hip): per image Pillow on one thread and the GPU at the defaults and with `restart_marker_rows=1`, in
+  one run (the defaults against a parent checkout are `--against`'s business).
 """
 import argparse
 import contextlib
@@ -222,6 +227,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--options", action="store_true", help="the option rows -> profiles/jpeg_opts_bench.json")
+    ap.add_argument("--restart", action="store_true", help="the defaults and restart_marker_rows=1 -> profiles/jpeg_rst_enc_bench.json")
     ap.add_argument("--against", default="", help="another checkout with its library built -> profiles/jpeg_unify_bench.json")
     ap.add_argument("--against-label", default="", help="how the result file names the other checkout (default: its path)")
     ap.add_argument("--sample", action="store_true", help=argparse.SUPPRESS)
@@ -233,7 +239,7 @@ def main():
     ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--inner", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "jpeg_unify_bench.json" if a.against else "jpeg_opts_bench.json" if a.options else "jpeg_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "jpeg_rst_enc_bench.json" if a.restart else "jpeg_unify_bench.json" if a.against else "jpeg_opts_bench.json" if a.options else "jpeg_bench.json")
     imgs = images()
     if a.root:                                             # a child of --against: the package of the checkout at a.root
         sys.path.insert(0, a.root)
@@ -267,6 +273,20 @@ def main():
         for _ in range(a.inner):
             ops.jpeg_encode(x, **(OPTION_ROWS["q95_444_optimised"] if a.options else {}))
         torch.cuda.synchronize()
+        return
+    if a.restart:
+        res = {"what": "GPU JPEG encoder at the defaults and with restart_marker_rows=1 (csrc/jpeg_rst.hip) vs Pillow (one thread, same keywords), same run, one MI355X",
+               "per_image": {}}
+        for name, u8 in imgs.items():
+            res["per_image"][name] = {}
+            for row, kw in (("defaults", {}), ("restart_marker_rows_1", dict(restart_marker_rows=1))):
+                p_ms, p_bytes = pillow_ms(u8, **kw)
+                single, b2b, g_bytes = encode_times(u8, **kw)
+                assert g_bytes == p_bytes
+                res["per_image"][name][row] = dict(pillow_ms_one_thread=p_ms, gpu_ms_single_call_hip_events=single, gpu_ms_back_to_back=b2b, file_bytes=g_bytes)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
         return
     if a.options:
         res = {"what": "GPU JPEG encoder (csrc/jpeg.hip) with options vs Pillow (one thread, same keywords), same run, one MI355X; defaults_old_entry "

@@ -9,6 +9,14 @@
 * the loop: `validate_with_model` on synthetic 512x512 JPEG pairs with `gpu_decode` off and on, each run a child process, the variants
   alternating, median of the rounds: pairs/s, host CPU seconds per pair (`time.process_time`: all threads) and host-to-device bytes
   per pair.  `--parent-root` adds the loop of another checkout (the commit before the switch existed, built) to the alternation.
+
+    python tools/bench_jpeg_decode.py --restart [--out profiles/jpeg_rst_bench.json] [--no-profile]
+
+* restart intervals (csrc/jpeg_rst.hip): the same four images written without DRI, with `restart_marker_rows=1` and with
+  `restart_marker_blocks=4`: Pillow on one thread, single call and back to back, the intervals and subsequences of each file; per kernel one
+  `rocprofv3 --kernel-trace --stats` child making 200 decodes of the 512x512 quality-75 file with a row per interval, with the synchronise
+  launches that did work counted from the trace (a launch that returns at once takes a few microseconds); the evaluation loop on `--pairs`
+  synthetic pairs written with `restart_marker_rows=1`, `gpu_decode` off against on (`--pairs 0`: not run).
 """
 import argparse
 import csv
@@ -28,13 +36,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def files():
+def files(**restart):
+    """the four files; `restart`: Pillow's restart_marker_blocks / restart_marker_rows for all of them"""
     import _jpeg_ref as eref
     from PIL import Image
 
     def pil(u8, **kw):
         buf = io.BytesIO()
-        Image.fromarray(u8).save(buf, format="JPEG", **kw)
+        Image.fromarray(u8).save(buf, format="JPEG", **kw, **restart)
         return buf.getvalue()
     return {"rgb_512_q75": pil(eref._smooth(512, 512, 3, 5)), "rgb_512_q95": pil(eref._smooth(512, 512, 3, 5), quality=95),
             "rgb_1024_q75": pil(eref._smooth(1024, 1024, 3, 6)), "mask_512": pil(((eref._smooth(512, 512, 0, 7) > 127) * 255).astype(np.uint8))}
@@ -53,7 +62,7 @@ def pillow_ms(data, n=20):
 def decode_times(data, n=50):
     import torch
     from stitch_amd import ops
-    info = ops.jpeg_probe(data)
+    info = ops.jpeg_probe(data, restart=True)
     dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
     ws = torch.empty((ops.jpeg_dec_workspace_bytes(info),), dtype=torch.uint8, device="cuda")
     out = torch.empty((info.H, info.W, info.ncomp), dtype=torch.uint8, device="cuda")
@@ -77,10 +86,10 @@ def decode_times(data, n=50):
     return float(np.median(single)), e0.elapsed_time(e1) / n
 
 
-def profile_child(n):
+def profile_child(n, restart=False):
     d = tempfile.mkdtemp(prefix="jpegd_prof_")
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "jpegd", "--output-format", "csv", "--",
-           sys.executable, os.path.abspath(__file__), "--inner-profile", str(n)]
+           sys.executable, os.path.abspath(__file__), "--inner-profile", str(n)] + (["--restart"] if restart else [])
     subprocess.run(cmd, check=True, timeout=600, stdout=subprocess.DEVNULL)
     path = (glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True) or [None])[0]
     if path is None:
@@ -90,10 +99,19 @@ def profile_child(n):
         if "jpeg" in r["Name"]:
             name = re.sub(r"\(.*", "", re.sub(r"^void ", "", r["Name"]).replace("(anonymous namespace)::", ""))
             rows.append(dict(name=name, calls_per_decode=int(r["Calls"]) / n, us_per_decode=float(r["TotalDurationNs"]) / n / 1e3))
-    return sorted(rows, key=lambda r: -r["us_per_decode"])
+    rows = sorted(rows, key=lambda r: -r["us_per_decode"])
+    if restart:                                                   # synchronise launches that did work: the others return at once, in a few us
+        trace = (glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True) or [None])[0]
+        durs = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in csv.DictReader(open(trace)) if "jpegr_sync_kernel" in r.get("Kernel_Name", "")] if trace else []
+        if durs:
+            rows.append(dict(name="jpegr_sync_kernel launches above 20 us (did work)", calls_per_decode=sum(v > 20.0 for v in durs) / n,
+                             us_per_decode=sum(v for v in durs if v > 20.0) / n))
+            rows.append(dict(name="jpegr_sync_kernel launches below 20 us (returned at once)", calls_per_decode=sum(v <= 20.0 for v in durs) / n,
+                             us_per_decode=sum(v for v in durs if v <= 20.0) / n))
+    return rows
 
 
-def write_dataset(root, pairs):
+def write_dataset(root, pairs, **save_kw):
     from PIL import Image
     sys.path.insert(0, ROOT)
     from stitch_amd.data import structured_pair
@@ -104,7 +122,7 @@ def write_dataset(root, pairs):
     for i in range(pairs):
         for d, t in zip(("input1", "input2"), base[i % 8]):
             path = os.path.join(root, "testing", d, f"{i:06d}.jpg")
-            Image.fromarray(t[0].permute(1, 2, 0).numpy().astype(np.uint8)).save(path, quality=95)
+            Image.fromarray(t[0].permute(1, 2, 0).numpy().astype(np.uint8)).save(path, quality=95, **save_kw)
             nbytes += os.path.getsize(path)
     return nbytes / pairs
 
@@ -133,9 +151,9 @@ def inner_eval(root, data_dir, gpu_decode, rounds):
     print("RESULT " + json.dumps(out), flush=True)
 
 
-def loop_bench(pairs, rounds, parent_root):
+def loop_bench(pairs, rounds, parent_root, **save_kw):
     data_dir = tempfile.mkdtemp(prefix="jpegd_loop_") + "/"
-    file_bytes = write_dataset(data_dir, pairs)
+    file_bytes = write_dataset(data_dir, pairs, **save_kw)
     variants = [("gpu_decode_off", ROOT, 0), ("gpu_decode_on", ROOT, 1)] + ([("parent", parent_root, 0)] if parent_root else [])
     runs = {name: [] for name, _, _ in variants}
     for _ in range(rounds):                                       # alternating: one timed run per child, the variants in turn
@@ -151,9 +169,37 @@ def loop_bench(pairs, rounds, parent_root):
     return res
 
 
+RESTART_VARIANTS = {"no_dri": {}, "rows_1": dict(restart_marker_rows=1), "blocks_4": dict(restart_marker_blocks=4)}
+
+
+def restart_bench(no_profile, pairs, rounds):
+    import torch
+    import _jpeg_rst_ref as rst
+    res = {"device": torch.cuda.get_device_name(0), "per_file": {}}
+    for variant, kw in RESTART_VARIANTS.items():
+        for name, data in files(**kw).items():
+            single, b2b = decode_times(data)
+            info = rst.probe(data)
+            parts = rst.intervals(data, info)
+            nsub = sum(max(1, -(-n * 8 // 1024)) for _, n in parts)       # (stuffed bytes: the device cuts the unstuffed ones, a few less)
+            longest = max(-(-n * 8 // 1024) for _, n in parts)
+            enqueued = -(-(-(-info["scan_len"] * 8 // 1024) + (len(parts) if kw else 0)) // 256)          # the host's bound
+            res["per_file"][f"{name}/{variant}"] = dict(file_bytes=len(data), pillow_ms=pillow_ms(data), gpu_single_ms=single, gpu_back_to_back_ms=b2b,
+                                                        intervals=len(parts), subsequences_about=nsub, longest_interval_subsequences=longest,
+                                                        sync_launches_enqueued=enqueued, sync_launches_needed_at_most=min(enqueued, -(-longest // 256) + 1))
+            print(name, variant, res["per_file"][f"{name}/{variant}"], flush=True)
+    if not no_profile:
+        res["kernels_rgb_512_q75_rows_1"] = profile_child(200, restart=True)
+    if pairs:                                                     # the evaluation loop on inputs written with a row per interval
+        res["eval_loop_rows_1"] = loop_bench(pairs, rounds, "", restart_marker_rows=1)
+        print(json.dumps(res["eval_loop_rows_1"]), flush=True)
+    return res
+
+
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_bench.json"))
+    p.add_argument("--out", default="")
+    p.add_argument("--restart", action="store_true")
     p.add_argument("--parent-root", default="")
     p.add_argument("--pairs", type=int, default=48)
     p.add_argument("--rounds", type=int, default=5)
@@ -166,13 +212,20 @@ def main():
     sys.path.insert(0, ROOT)
     import torch
     from stitch_amd import ops
+    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_rst_bench.json" if args.restart else "jpeg_decode_bench.json")
     if args.inner_profile:
-        data = files()["rgb_512_q75"]
-        info = ops.jpeg_probe(data)
+        data = files(**(RESTART_VARIANTS["rows_1"] if args.restart else {}))["rgb_512_q75"]
+        info = ops.jpeg_probe(data, restart=True)
         dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
         for _ in range(args.inner_profile):
             ops.jpeg_decode(dev, info=info)
         torch.cuda.synchronize()
+        return None
+    if args.restart:
+        res = restart_bench(args.no_profile, args.pairs, args.rounds)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("wrote", args.out)
         return None
     import _jpeg_dec_ref as dref
     res = {"device": torch.cuda.get_device_name(0), "per_file": {}}
