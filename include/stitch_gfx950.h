@@ -466,7 +466,7 @@ int st_jpeg_encode_u8(const void* src, int32_t H, int32_t W, int32_t channels, i
  * ST_EINVAL before any launch for everything st_jpeg_encode_u8 rejects (with the _ex sizes), and for: a null params; quality outside 1..100;
  * sampling other than (1,1), (2,1), (2,2); one channel with sampling other than (1,1); optimize other than 0 / 1; a nonzero reserved[1..3];
  * reserved[0] outside 0..65535.
- * Restart intervals (csrc/jpeg_rst.hip; contract in README.md "Restart intervals", CPU restatement tests/_jpeg_rst_ref.py): reserved[0] = Ri > 0
+ * Restart intervals (the jpegr_enc_* kernels of csrc/jpeg.hip; contract in README.md "Restart intervals", CPU restatement tests/_jpeg_rst_ref.py): reserved[0] = Ri > 0
  * writes the file of Pillow's `save(restart_marker_blocks=Ri)` (for `restart_marker_rows=r`: Ri = min(r * MCUs per row, 65535), which
  * ops.jpeg_encode computes), byte for byte: the segment FF DD 00 04 Ri directly in front of SOS; in front of MCU k * Ri (k >= 1) the pending
  * bits padded with 1-bits to a byte (a padded FF is stuffed), then FF D0+((k-1)&7) unstuffed, and every DC prediction back at 0; with
@@ -510,7 +510,7 @@ typedef struct st_jpeg_dec_params {
 } st_jpeg_dec_params;
 int st_abi_jpeg_dec_params_size(void);
 int st_jpeg_dec_workspace_bytes(int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, int64_t scan_len);
-/* Restart intervals (csrc/jpeg_rst.hip; contract in README.md "Restart intervals", CPU restatement tests/_jpeg_rst_ref.py).  With
+/* Restart intervals (the jpegr_* kernels of csrc/jpeg_dec.hip; contract in README.md "Restart intervals", CPU restatement tests/_jpeg_rst_ref.py).  With
  * restart_interval Ri in 1..65535 the scan is n = ceil(MCUs / Ri) intervals with the markers FF D0, FF D1, ... FF D7, FF D0, ... between them
  * (ops.jpeg_probe(data, restart=True) checks their count and order on the host; nothing but the file is uploaded).  The device finds the
  * markers, drops them while it unstuffs, and cuts EVERY INTERVAL into its own subsequences of 1024 bits: an interval's first subsequence starts

@@ -23,15 +23,87 @@
 //   jpeg_count_kernel   0xFF bytes per 2048-byte chunk of the stream, scanned by jpeg_scan_kernel again
 //   jpeg_stuff_kernel   scatters the bytes with their 0x00 followers behind the header; the last workgroup assembles the header -- DQT from
 //                       the arguments, SOF0, the DHTs of fixed or device-computed length -- and writes EOI and the byte count
+//
+// With restart intervals (st_jpeg_enc_params.reserved[0] = Ri > 0) the file is the one Pillow's `save(restart_marker_blocks= /
+// restart_marker_rows=)` writes, byte for byte.  The block, table, zero, count and scan kernels are the ones above.  The histogram, bits, pack
+// and stuff steps are each written once, as a body on `bool RST`; the kernels of both paths are its two instantiations:
+//
+//   jpegr_enc_hist_kernel     jpeg_hist_kernel with the DC predecessor 0 for a component's first block of an interval (optimize only)
+//   jpegr_enc_bits_kernel     jpeg_bits_kernel with the same predecessor rule; jpeg_scan_kernel makes unpadded bit offsets from the lengths
+//   jpegr_enc_pad_kernel      one thread per interval: the 1-bits that round its end up to a byte; jpeg_scan_kernel sums them
+//   jpegr_enc_offsets_kernel  bit offset of every block in the padded stream, the byte every interval starts at, the padded stream's bits
+//   jpegr_enc_pack_kernel     jpeg_pack_kernel with the predecessor rule; an interval's last block appends the padding
+//   jpegr_enc_stuff_kernel    jpeg_stuff_kernel: a byte's position adds two for every interval boundary in front of it, the thread that owns an
+//                             interval's first byte writes FF D0+((k-1)&7) in front of it, unstuffed; the DRI segment goes in front of SOS
 #include "common.h"
 #include "jpeg_tables.h"
 #include "jpeg_huff_core.h"
 #include "jpeg_scan.h"
-#include "jpeg_enc_core.h"
-#include "jpeg_rst.h"
 #include "../../include/stitch_gfx950.h"
 
 namespace {
+
+// ---- code tables, header ----------------------------------------------------------------------------------------------------------
+constexpr int kDhtMax = 16 + 256;
+struct JTabs {                         // the four tables in DHT order: DC0, AC0, DC1, AC1
+    uint32_t code[4][256];             // by symbol (DC: the category): code | length << 16
+    uint8_t dht[4][kDhtMax];           // the DHT payload behind the Tc / Th byte: 16 counts, then the symbols
+    int32_t dht_len[4];
+};
+
+constexpr JTabs make_std() {           // ITU-T T.81 Annex K (csrc/jpeg_tables.h), canonical codes (Annex C)
+    JTabs t{};
+    for (int c = 0; c < 2; ++c) {
+        for (int ac = 0; ac < 2; ++ac) {
+            const int* bits = ac ? kAcBits[c] : kDcBits[c];
+            const int nsym = ac ? 162 : 12, i = 2 * c + ac;
+            uint32_t code = 0;
+            int k = 0;
+            for (int len = 1; len <= 16; ++len) {
+                t.dht[i][len - 1] = (uint8_t)bits[len - 1];
+                for (int j = 0; j < bits[len - 1]; ++j, ++k) t.code[i][ac ? kAcVals[c][k] : k] = code++ | ((uint32_t)len << 16);
+                code <<= 1;
+            }
+            for (int j = 0; j < nsym; ++j) t.dht[i][16 + j] = (uint8_t)(ac ? kAcVals[c][j] : j);
+            t.dht_len[i] = 16 + nsym;
+        }
+    }
+    return t;
+}
+
+struct JIzz {
+    uint8_t v[64];                     // natural index -> zigzag position
+};
+constexpr JIzz make_izz() {
+    JIzz z{};
+    for (int i = 0; i < 64; ++i) z.v[kZigzag[i]] = (uint8_t)i;
+    return z;
+}
+
+// SOI + APP0, DQT x n, SOF0, DHT x 2n, SOS: what write_header writes.  (All four lengths are read, needed or not: four loads in flight, where a
+// loop over the tables in use would wait for each -- in every workgroup of the stuff kernel.)
+constexpr uint32_t header_bytes(int ncomp, const JTabs& tabs) {
+    const uint32_t luma = 69u + 2 * 5u + (uint32_t)tabs.dht_len[0] + (uint32_t)tabs.dht_len[1];
+    const uint32_t chroma = 69u + 2 * 5u + (uint32_t)tabs.dht_len[2] + (uint32_t)tabs.dht_len[3];
+    return 20u + (10u + 3 * ncomp) + (8u + 2 * ncomp) + luma + (ncomp == 3 ? chroma : 0u);
+}
+
+constexpr JTabs kStdHost = make_std();
+// no table has more symbols than the Annex K ones, so no header is longer than theirs
+constexpr uint32_t kStdHeaderBytes[2] = {header_bytes(1, kStdHost), header_bytes(3, kStdHost)};
+static_assert(kStdHeaderBytes[0] == 328 && kStdHeaderBytes[1] == 623, "header sizes of the contract");
+__device__ const JTabs g_std = make_std();
+
+struct JDev {                          // the workspace's table area (optimize only)
+    JTabs tabs;
+    uint32_t hist[4][kJhEntries];
+};
+
+struct JHeader {
+    int32_t H, W, ncomp, hs, vs;
+    uint32_t std_bytes;                // the header's length with the Annex K tables: the plain path starts without a read for it
+    uint8_t q[2][64];                  // zigzag order, as DQT lists them
+};
 
 __device__ const JIzz g_izz = make_izz();
 
@@ -62,9 +134,10 @@ struct JGeom {
 
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-// restart intervals (reserved[0] = Ri MCUs > 0, csrc/jpeg_rst.hip): n = ceil(MCUs / Ri) intervals.  Each adds at most 7 padding bits to the
+// restart intervals (reserved[0] = Ri MCUs > 0): n = ceil(MCUs / Ri) intervals.  Each adds at most 7 padding bits to the
 // stream (counted as a byte, doubled like every byte for stuffing: 2 bytes of the file) and one two-byte marker; the DRI segment is 6 bytes.
-// The workspace grows by the stream's share of that and by two tables of n + 1 words behind the stream.
+// The workspace grows by the stream's share of that and by two tables of n + 1 words behind the stream.  (Kept beside JGeom and not in it:
+// JGeom is an argument of jpeg_blocks_kernel, which has no use for them.)
 struct JRstGeom {
     uint32_t ri, nint;
     size_t off_pad, off_ibyte;
@@ -236,15 +309,85 @@ __global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restr
 }
 
 // ---- entropy coding ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void jpeg_hist_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ hist, uint32_t nblocks, uint32_t nb, uint32_t ny) {
+struct HuffLds {
+    uint32_t dc[2][16];
+    uint32_t ac[2][256];
+};
+
+__device__ __forceinline__ void load_huff(HuffLds& h, const JTabs* __restrict__ tabs) {
+    for (int i = threadIdx.x; i < 512; i += blockDim.x) h.ac[i >> 8][i & 255] = tabs->code[2 * (i >> 8) + 1][i & 255];
+    if (threadIdx.x < 32) h.dc[threadIdx.x >> 4][threadIdx.x & 15] = tabs->code[2 * (threadIdx.x >> 4)][threadIdx.x & 15];
+    __syncthreads();
+}
+
+// scan-order predecessor of block b inside its component (-1: none) and the block's table (0 luma, 1 chroma)
+__device__ __forceinline__ int64_t block_pred(uint32_t b, uint32_t nb, uint32_t ny, int& table) {
+    table = 0;
+    if (nb == 1) return (int64_t)b - 1;
+    const uint32_t m = b / nb, j = b - m * nb;
+    table = j >= ny;
+    if (j >= 1 && j < ny) return (int64_t)b - 1;
+    if (m == 0) return -1;
+    return (int64_t)(m - 1) * nb + (j == 0 ? ny - 1 : j);
+}
+
+// the DC value block b is predicted from: its scan-order predecessor in the component, 0 at the start of the scan and (RST) of an interval
+template <bool RST>
+__device__ __forceinline__ int dc_pred(const int16_t* __restrict__ coef, uint32_t b, uint32_t nb, uint32_t ny, uint32_t ri, int& table) {
+    const int64_t pb = block_pred(b, nb, ny, table);
+    if constexpr (RST) {
+        if (pb < 0 || ((uint32_t)pb / nb) / ri != (b / nb) / ri) return 0;
+        return (int)coef[pb * 64];
+    } else {
+        return pb < 0 ? 0 : (int)coef[pb * 64];
+    }
+}
+
+__device__ __forceinline__ int coef_at(const uint4& w, int e) {      // e: constant after unrolling
+    const uint32_t d = e < 2 ? w.x : e < 4 ? w.y : e < 6 ? w.z : w.w;
+    return (int)(int16_t)((e & 1) ? (d >> 16) : (d & 0xffffu));
+}
+
+__device__ __forceinline__ int magnitude_bits(int v) { return 32 - __clz(abs(v)); }
+
+// the symbols of block b in scan order: dc(category, difference), then per nonzero coefficient zrl(k), the k >= 0 ZRL symbols (0xF0) of a run
+// above 15, and ac(run << 4 | size, value, size) with the rest of the run; EOB is ac(0x00, 0, 0)
+template <class DC, class ZRL, class AC>
+__device__ __forceinline__ void walk_block(const int16_t* __restrict__ coef, uint32_t b, int pred, DC&& dc, ZRL&& zrl, AC&& ac) {
+    const uint4* c4 = (const uint4*)(coef + (size_t)b * 64);
+    int run = 0;
+#pragma unroll 1
+    for (int q = 0; q < 8; ++q) {
+        const uint4 w = c4[q];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int v = coef_at(w, e);
+            if (q == 0 && e == 0) {
+                dc(magnitude_bits(v - pred), v - pred);
+            } else if (v == 0) {
+                ++run;
+            } else {
+                zrl(run >> 4);
+                const int n = magnitude_bits(v);
+                ac(((run & 15) << 4) | n, v, n);
+                run = 0;
+            }
+        }
+    }
+    if (run) ac(0x00, 0, 0);
+}
+
+// The histogram, bits, pack and stuff steps follow, each as one body for a plain file (RST false) and a file with restart intervals of
+// `ri` MCUs (RST true); what the other path's kernel has no argument for is passed as 0 / nullptr and never read.
+template <bool RST>
+__device__ __forceinline__ void hist_body(const int16_t* __restrict__ coef, uint32_t* __restrict__ hist, uint32_t nblocks, uint32_t nb, uint32_t ny, uint32_t ri) {
     __shared__ uint32_t s_hist[4 * kJhEntries];
     for (int i = threadIdx.x; i < 4 * kJhEntries; i += 256) s_hist[i] = 0u;
     __syncthreads();
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b < nblocks) {
         int t;
-        const int64_t pb = block_pred(b, nb, ny, t);
-        const int pred = pb < 0 ? 0 : (int)coef[pb * 64];
+        const int pred = dc_pred<RST>(coef, b, nb, ny, ri, t);
         uint32_t* hd = s_hist + (2 * t) * kJhEntries;
         uint32_t* ha = hd + kJhEntries;
         walk_block(
@@ -259,6 +402,15 @@ __global__ __launch_bounds__(256) void jpeg_hist_kernel(const int16_t* __restric
         const uint32_t v = s_hist[i];
         if (v) atomicAdd(hist + i, v);
     }
+}
+
+__global__ __launch_bounds__(256) void jpeg_hist_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ hist, uint32_t nblocks, uint32_t nb, uint32_t ny) {
+    hist_body<false>(coef, hist, nblocks, nb, ny, 0u);
+}
+
+__global__ __launch_bounds__(256) void jpegr_enc_hist_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ hist, uint32_t nblocks, uint32_t nb, uint32_t ny,
+                                                             uint32_t ri) {
+    hist_body<true>(coef, hist, nblocks, nb, ny, ri);
 }
 
 struct WaveTeam {
@@ -292,20 +444,30 @@ __global__ __launch_bounds__(64) void jpeg_table_kernel(JDev* __restrict__ dev) 
 }
 
 // dev: the tables the table kernel made, or nullptr for the Annex K ones (here and below)
-__global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ len, const JDev* __restrict__ dev, uint32_t nblocks,
-                                                        uint32_t nb, uint32_t ny) {
+template <bool RST>
+__device__ __forceinline__ void bits_body(const int16_t* __restrict__ coef, uint32_t* __restrict__ len, const JDev* __restrict__ dev, uint32_t nblocks, uint32_t nb,
+                                          uint32_t ny, uint32_t ri) {
     __shared__ HuffLds h;
     load_huff(h, dev ? &dev->tabs : &g_std);
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b >= nblocks) return;
     int t;
-    const int64_t pb = block_pred(b, nb, ny, t);
-    const int pred = pb < 0 ? 0 : (int)coef[pb * 64];
+    const int pred = dc_pred<RST>(coef, b, nb, ny, ri, t);
     uint32_t bits = 0;
     walk_block(
         coef, b, pred, [&](int n, int) { bits += (h.dc[t][n & 15] >> 16) + n; }, [&](int k) { bits += (uint32_t)k * (h.ac[t][0xF0] >> 16); },
         [&](int sym, int, int n) { bits += (h.ac[t][sym & 255] >> 16) + n; });
     len[b] = bits;
+}
+
+__global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ len, const JDev* __restrict__ dev, uint32_t nblocks,
+                                                        uint32_t nb, uint32_t ny) {
+    bits_body<false>(coef, len, dev, nblocks, nb, ny, 0u);
+}
+
+__global__ __launch_bounds__(256) void jpegr_enc_bits_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ len, const JDev* __restrict__ dev, uint32_t nblocks,
+                                                             uint32_t nb, uint32_t ny, uint32_t ri) {
+    bits_body<true>(coef, len, dev, nblocks, nb, ny, ri);
 }
 
 // in-place exclusive prefix sum of data[0 .. n), total -> *total.  One workgroup of 1024 threads, 4 entries per thread and tile.
@@ -353,16 +515,60 @@ __global__ __launch_bounds__(256) void jpeg_zero_kernel(uint32_t* __restrict__ s
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < words; i += gridDim.x * 256) stream[i] = 0u;
 }
 
-__global__ __launch_bounds__(256) void jpeg_pack_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ off, const uint32_t* __restrict__ total_bits,
-                                                        uint32_t* __restrict__ stream, uint32_t cap_words, const JDev* __restrict__ dev, uint32_t nblocks, uint32_t nb,
-                                                        uint32_t ny) {
+// off: the exclusive prefix sum of the blocks' bits, tot[0] their sum.  Every interval starts on a byte, so its padding is its own bits' alone.
+__global__ __launch_bounds__(256) void jpegr_enc_pad_kernel(const uint32_t* __restrict__ off, const uint32_t* __restrict__ tot, uint32_t* __restrict__ pad, uint32_t nblocks,
+                                                            uint32_t per, uint32_t nint) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nint) return;
+    const uint32_t s = i * per, e = s + per;                            // per = Ri * blocks per MCU <= 6 * 65535
+    const uint32_t bits = (e < nblocks ? off[e] : tot[0]) - off[s];
+    pad[i] = (8u - (bits & 7u)) & 7u;
+}
+
+// pad: the exclusive prefix sum of the padding bits, tot[2] their sum
+__global__ __launch_bounds__(256) void jpegr_enc_offsets_kernel(uint32_t* __restrict__ off, uint32_t* __restrict__ tot, const uint32_t* __restrict__ pad,
+                                                                uint32_t* __restrict__ ibyte, uint32_t nblocks, uint32_t per) {
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= nblocks) return;
+    const uint32_t i = b / per, o = off[b] + pad[i];
+    off[b] = o;
+    if (b == i * per) ibyte[i] = o >> 3;
+    if (b == 0) tot[0] += tot[2];                                       // (read by no other thread of this launch)
+}
+
+struct BitWriter {
+    uint32_t* word;      // next word of the stream (bytes in stream order: the big-endian word, byte-swapped)
+    uint32_t* end;       // one past the stream's capacity: nothing is written from here on
+    uint64_t acc;        // pending bits in the low `n`
+    int n;
+    bool first;          // the next word is shared with the blocks before this one
+};
+
+__device__ __forceinline__ void put_bits(BitWriter& w, uint32_t v, int len) {
+    w.acc = (w.acc << len) | v;
+    w.n += len;
+    if (w.n >= 32) {
+        w.n -= 32;
+        const uint32_t word = __builtin_bswap32((uint32_t)(w.acc >> w.n));
+        if (w.word < w.end) {
+            if (w.first) atomicOr(w.word, word);
+            else *w.word = word;
+        }
+        w.first = false;
+        ++w.word;
+    }
+}
+
+template <bool RST>
+__device__ __forceinline__ void pack_body(const int16_t* __restrict__ coef, const uint32_t* __restrict__ off, const uint32_t* __restrict__ total_bits,
+                                          uint32_t* __restrict__ stream, uint32_t cap_words, const JDev* __restrict__ dev, uint32_t nblocks, uint32_t nb, uint32_t ny,
+                                          uint32_t ri) {
     __shared__ HuffLds h;
     load_huff(h, dev ? &dev->tabs : &g_std);
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b >= nblocks) return;
     int t;
-    const int64_t pb = block_pred(b, nb, ny, t);
-    const int pred = pb < 0 ? 0 : (int)coef[pb * 64];
+    const int pred = dc_pred<RST>(coef, b, nb, ny, ri, t);
     const uint32_t o = off[b];
     BitWriter w{stream + (o >> 5), stream + cap_words, 0, (int)(o & 31u), true};
     auto put = [&](uint32_t cl, int v, int n) {
@@ -374,11 +580,39 @@ __global__ __launch_bounds__(256) void jpeg_pack_kernel(const int16_t* __restric
             for (; k > 0; --k) put(h.ac[t][0xF0], 0, 0);
         },
         [&](int sym, int v, int n) { put(h.ac[t][sym & 255], v, n); });
-    if (b == nblocks - 1) {                                           // the final partial byte is padded with 1-bits
-        const int pad = (int)((8u - (*total_bits & 7u)) & 7u);
-        put_bits(w, (1u << pad) - 1u, pad);
+    if constexpr (RST) {
+        if (b + 1 == nblocks || (b + 1) % (ri * nb) == 0) {             // the interval's final partial byte is padded with 1-bits (words are byte multiples)
+            const int pad = (8 - (w.n & 7)) & 7;
+            put_bits(w, (1u << pad) - 1u, pad);
+        }
+    } else {
+        if (b == nblocks - 1) {                                       // the final partial byte is padded with 1-bits
+            const int pad = (int)((8u - (*total_bits & 7u)) & 7u);
+            put_bits(w, (1u << pad) - 1u, pad);
+        }
     }
     if (w.n > 0 && w.word < w.end) atomicOr(w.word, __builtin_bswap32((uint32_t)(w.acc << (32 - w.n))));
+}
+
+__global__ __launch_bounds__(256) void jpeg_pack_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ off, const uint32_t* __restrict__ total_bits,
+                                                        uint32_t* __restrict__ stream, uint32_t cap_words, const JDev* __restrict__ dev, uint32_t nblocks, uint32_t nb,
+                                                        uint32_t ny) {
+    pack_body<false>(coef, off, total_bits, stream, cap_words, dev, nblocks, nb, ny, 0u);
+}
+
+__global__ __launch_bounds__(256) void jpegr_enc_pack_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ off, uint32_t* __restrict__ stream,
+                                                             uint32_t cap_words, const JDev* __restrict__ dev, uint32_t nblocks, uint32_t nb, uint32_t ny, uint32_t ri) {
+    pack_body<true>(coef, off, nullptr, stream, cap_words, dev, nblocks, nb, ny, ri);
+}
+
+__device__ __forceinline__ uint32_t ff_bytes(uint2 d, uint32_t i0, uint32_t nbytes) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t byte = ((k < 4 ? d.x : d.y) >> ((k & 3) * 8)) & 255u;
+        c += (i0 + k < nbytes && byte == 255u) ? 1u : 0u;
+    }
+    return c;
 }
 
 // chunks behind the stream get no count: jpeg_scan_kernel bounds itself with the same total_bits
@@ -393,18 +627,69 @@ __global__ __launch_bounds__(256) void jpeg_count_kernel(const uint32_t* __restr
     if (threadIdx.x == 0) cnt[blockIdx.x] = all;
 }
 
-__global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint32_t* __restrict__ stream, const uint32_t* __restrict__ totals, const uint32_t* __restrict__ cnt_off,
-                                                         uint8_t* __restrict__ out, int32_t* __restrict__ out_nbytes, const JHeader hp, const JDev* __restrict__ dev) {
+// SOI, APP0, DQT x n, SOF0, DHT x n (DC0, AC0, DC1, AC1), SOS; one workgroup
+__device__ __forceinline__ void write_header(uint8_t* __restrict__ out, const JHeader& hp, const JTabs* __restrict__ tabs) {
+    const int ntab = hp.ncomp == 3 ? 2 : 1, nc = hp.ncomp, tid = threadIdx.x;
+    uint32_t n = 0;
+    if (tid < 20) {
+        const uint32_t lo = 0xE0FFD8FFu, mid = 0x464A1000u;                      // FF D8 FF E0 | 00 10 'J' 'F'
+        const uint8_t rest[12] = {'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+        uint8_t v = 0;
+        if (tid < 4) v = (uint8_t)(lo >> (8 * tid));
+        else if (tid < 8) v = (uint8_t)(mid >> (8 * (tid - 4)));
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            if (tid == 8 + k) v = rest[k];
+        out[tid] = v;
+    }
+    n = 20;
+    for (int c = 0; c < ntab; ++c, n += 69) {
+        if (tid < 5) out[n + tid] = tid == 0 ? 0xFF : tid == 1 ? 0xDB : tid == 2 ? 0 : tid == 3 ? 67 : (uint8_t)c;
+        if (tid < 64) out[n + 5 + tid] = hp.q[c][tid];
+    }
+    if (tid == 0) {
+        uint8_t* h = out + n;
+        h[0] = 0xFF, h[1] = 0xC0, h[2] = 0, h[3] = (uint8_t)(8 + 3 * nc), h[4] = 8;
+        h[5] = (uint8_t)(hp.H >> 8), h[6] = (uint8_t)(hp.H & 255), h[7] = (uint8_t)(hp.W >> 8), h[8] = (uint8_t)(hp.W & 255), h[9] = (uint8_t)nc;
+        for (int c = 0; c < nc; ++c) h[10 + 3 * c] = (uint8_t)(c + 1), h[11 + 3 * c] = c ? 0x11 : (uint8_t)(hp.hs << 4 | hp.vs), h[12 + 3 * c] = c ? 1 : 0;
+    }
+    n += 10 + 3 * nc;
+    for (int i = 0; i < 2 * ntab; ++i) {
+        const uint32_t len = (uint32_t)tabs->dht_len[i];
+        if (tid < 5) out[n + tid] = tid == 0 ? 0xFF : tid == 1 ? 0xC4 : tid == 2 ? (uint8_t)((len + 3) >> 8) : tid == 3 ? (uint8_t)((len + 3) & 255) : (uint8_t)((i & 1) << 4 | (i >> 1));
+        for (uint32_t k = tid; k < len; k += 256) out[n + 5 + k] = tabs->dht[i][k];
+        n += 5 + len;
+    }
+    if (tid == 0) {
+        uint8_t* h = out + n;
+        h[0] = 0xFF, h[1] = 0xDA, h[2] = 0, h[3] = (uint8_t)(6 + 2 * nc), h[4] = (uint8_t)nc;
+        for (int c = 0; c < nc; ++c) h[5 + 2 * c] = (uint8_t)(c + 1), h[6 + 2 * c] = c ? 0x11 : 0x00;
+        h[5 + 2 * nc] = 0, h[6 + 2 * nc] = 63, h[7 + 2 * nc] = 0;
+    }
+}
+
+// RST: ibyte[1 .. nint - 1], the stream byte every interval starts at, is strictly increasing (an interval holds at least one block, a block at
+// least two bits, and ends on a byte)
+template <bool RST>
+__device__ __forceinline__ void stuff_body(const uint32_t* __restrict__ stream, const uint32_t* __restrict__ totals, const uint32_t* __restrict__ cnt_off,
+                                           const uint32_t* __restrict__ ibyte, uint32_t nint, uint32_t ri, uint8_t* __restrict__ out, int32_t* __restrict__ out_nbytes,
+                                           const JHeader& hp, const JDev* __restrict__ dev) {
     __shared__ uint32_t s_wave[4];
     const JTabs* tabs = dev ? &dev->tabs : &g_std;
     const uint32_t nbytes = (totals[0] + 7u) >> 3;
-    const uint32_t hdr = dev ? header_bytes(hp.ncomp, dev->tabs) : hp.std_bytes;
+    const uint32_t hdr0 = dev ? header_bytes(hp.ncomp, dev->tabs) : hp.std_bytes, hdr = RST ? hdr0 + 6u : hdr0;
     // the header is the last workgroup's: its chunk lies behind the stream unless the image fills the worst case, so the header is written
     // beside the scatter and not in front of workgroup 0's
     if (blockIdx.x == gridDim.x - 1) {
         write_header(out, hp, tabs);
         if (threadIdx.x == 0) {
-            const uint32_t end = hdr + nbytes + totals[1];
+            if constexpr (RST) {                                        // (this thread wrote SOS: it moves six bytes back, DRI takes its place)
+                const uint32_t sos = 8u + 2u * (uint32_t)hp.ncomp;
+                uint8_t* h = out + hdr0 - sos;
+                for (int k = (int)sos - 1; k >= 0; --k) h[k + 6] = h[k];
+                h[0] = 0xFF, h[1] = 0xDD, h[2] = 0, h[3] = 4, h[4] = (uint8_t)(ri >> 8), h[5] = (uint8_t)(ri & 255u);
+            }
+            const uint32_t end = hdr + nbytes + totals[1] + (RST ? 2u * (nint - 1u) : 0u);      // a marker in front of every interval but the first
             out[end] = 0xFF, out[end + 1] = 0xD9;
             *out_nbytes = (int32_t)(end + 2);
         }
@@ -414,15 +699,42 @@ __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint32_t* __restr
     const uint2 d = i0 < nbytes ? *(const uint2*)(stream + (i0 >> 2)) : make_uint2(0u, 0u);
     uint32_t ex;
     block_sum_256(ff_bytes(d, i0, nbytes), ex, s_wave);
-    uint8_t* o = out + hdr + i0 + cnt_off[blockIdx.x] + ex;
+    uint32_t m = 0;                                                     // RST: the intervals 1 .. nint - 1 that start in front of byte i0
+    if constexpr (RST) {
+        uint32_t lo = 0, hi = nint;
+        while (hi - lo > 1u) {                                          // ibyte[lo] < i0 or lo == 0; ibyte[hi] >= i0 or hi == nint
+            const uint32_t mid = lo + (hi - lo) / 2u;
+            if (ibyte[mid] < i0) lo = mid;
+            else hi = mid;
+        }
+        m = lo;
+    }
+    uint8_t* o = out + hdr + i0 + cnt_off[blockIdx.x] + ex + 2u * m;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const uint32_t byte = ((k < 4 ? d.x : d.y) >> ((k & 3) * 8)) & 255u;
         if (i0 + k < nbytes) {
+            if constexpr (RST) {
+                if (m + 1u < nint && ibyte[m + 1u] == i0 + k) {
+                    *o++ = 0xFF, *o++ = (uint8_t)(0xD0u + (m & 7u));
+                    ++m;
+                }
+            }
             *o++ = (uint8_t)byte;
             if (byte == 255u) *o++ = 0;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint32_t* __restrict__ stream, const uint32_t* __restrict__ totals, const uint32_t* __restrict__ cnt_off,
+                                                         uint8_t* __restrict__ out, int32_t* __restrict__ out_nbytes, const JHeader hp, const JDev* __restrict__ dev) {
+    stuff_body<false>(stream, totals, cnt_off, nullptr, 0u, 0u, out, out_nbytes, hp, dev);
+}
+
+__global__ __launch_bounds__(256) void jpegr_enc_stuff_kernel(const uint32_t* __restrict__ stream, const uint32_t* __restrict__ totals, const uint32_t* __restrict__ cnt_off,
+                                                              const uint32_t* __restrict__ ibyte, uint32_t nint, uint32_t ri, uint8_t* __restrict__ out,
+                                                              int32_t* __restrict__ out_nbytes, const JHeader hp, const JDev* __restrict__ dev) {
+    stuff_body<true>(stream, totals, cnt_off, ibyte, nint, ri, out, out_nbytes, hp, dev);
 }
 
 int quantiser(int table, int natural, int quality) {                 // jpeg_quality_scaling + jpeg_add_quant_table, baseline clamp
@@ -492,49 +804,49 @@ extern "C" int st_jpeg_encode_u8_ex(const void* src, int32_t H, int32_t W, int32
         hipLaunchKernelGGL((jpeg_blocks_kernel<3, 2, 2>), dim3(grid), dim3(256), 0, st, (const uint8_t*)src, coef, g, qt, hist);
     ST_CHECK_LAUNCH();
     const unsigned zero_grid = (g.stream_words + 255) / 256 < 512 ? (g.stream_words + 255) / 256 : 512;
-    if (rg.ri) {                                                       // restart intervals: what differs is csrc/jpeg_rst.hip's
-        JpegRstEncode e;
-        e.coef = coef, e.len = len, e.tot = tot, e.pad = (uint32_t*)(ws + rg.off_pad), e.ibyte = (uint32_t*)(ws + rg.off_ibyte);
-        e.stream = bits, e.stream_words = g.stream_words, e.dev = dev;
-        e.nblocks = g.nblocks, e.nb = nb, e.ny = ny, e.ri = rg.ri, e.nint = rg.nint, e.nchunks = g.nchunks;
-        e.cnt = cnt, e.out = (uint8_t*)out, e.out_nbytes = out_nbytes, e.header = &hp, e.st = st;
-        int rc;
-        if (dev) {
-            if ((rc = st_jpeg_rst_hist(e)) != ST_OK) return rc;
-            hipLaunchKernelGGL(jpeg_table_kernel, dim3(channels == 3 ? 4 : 2), dim3(64), 0, st, dev);
-            ST_CHECK_LAUNCH();
-        }
-        if ((rc = st_jpeg_rst_offsets(e)) != ST_OK) return rc;
-        hipLaunchKernelGGL(jpeg_zero_kernel, dim3(zero_grid), dim3(256), 0, st, bits, (const uint32_t*)tot, g.stream_words);
-        ST_CHECK_LAUNCH();
-        if ((rc = st_jpeg_rst_pack(e)) != ST_OK) return rc;
-        hipLaunchKernelGGL(jpeg_count_kernel, dim3(g.nchunks), dim3(256), 0, st, (const uint32_t*)bits, (const uint32_t*)tot, cnt);
-        ST_CHECK_LAUNCH();
-        hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, g.nchunks, (const uint32_t*)tot, tot + 1);
-        ST_CHECK_LAUNCH();
-        return st_jpeg_rst_stuff(e);
-    }
+    // restart intervals (ri > 0): the kernels of the RST instantiations, and between the bits and the zero step the padding of every interval
+    const uint32_t ri = rg.ri, per = ri * nb;
+    uint32_t* pad = (uint32_t*)(ws + rg.off_pad);          // [nint + 1]: padding bits behind interval i, then their exclusive prefix sum
+    uint32_t* ibyte = (uint32_t*)(ws + rg.off_ibyte);      // [nint + 1]: the stream byte interval i starts at
     if (dev) {
-        hipLaunchKernelGGL(jpeg_hist_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, hist, g.nblocks, nb, ny);
+        if (ri) hipLaunchKernelGGL(jpegr_enc_hist_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, hist, g.nblocks, nb, ny, ri);
+        else hipLaunchKernelGGL(jpeg_hist_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, hist, g.nblocks, nb, ny);
         ST_CHECK_LAUNCH();
         hipLaunchKernelGGL(jpeg_table_kernel, dim3(channels == 3 ? 4 : 2), dim3(64), 0, st, dev);
         ST_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(jpeg_bits_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, len, (const JDev*)dev, g.nblocks, nb, ny);
+    if (ri) hipLaunchKernelGGL(jpegr_enc_bits_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, len, (const JDev*)dev, g.nblocks, nb, ny, ri);
+    else hipLaunchKernelGGL(jpeg_bits_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, len, (const JDev*)dev, g.nblocks, nb, ny);
     ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, len, g.nblocks, (const uint32_t*)nullptr, tot);
     ST_CHECK_LAUNCH();
+    if (ri) {                                              // tot[2]: padding bits; tot[0] becomes the bits of the padded stream
+        hipLaunchKernelGGL(jpegr_enc_pad_kernel, dim3((rg.nint + 255) / 256), dim3(256), 0, st, (const uint32_t*)len, (const uint32_t*)tot, pad, g.nblocks, per, rg.nint);
+        ST_CHECK_LAUNCH();
+        hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, pad, rg.nint, (const uint32_t*)nullptr, tot + 2);
+        ST_CHECK_LAUNCH();
+        hipLaunchKernelGGL(jpegr_enc_offsets_kernel, dim3(per_block), dim3(256), 0, st, len, tot, (const uint32_t*)pad, ibyte, g.nblocks, per);
+        ST_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(jpeg_zero_kernel, dim3(zero_grid), dim3(256), 0, st, bits, (const uint32_t*)tot, g.stream_words);
     ST_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_pack_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, (const uint32_t*)len, (const uint32_t*)tot, bits, g.stream_words,
-                       (const JDev*)dev, g.nblocks, nb, ny);
+    if (ri)
+        hipLaunchKernelGGL(jpegr_enc_pack_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, (const uint32_t*)len, bits, g.stream_words, (const JDev*)dev,
+                           g.nblocks, nb, ny, ri);
+    else
+        hipLaunchKernelGGL(jpeg_pack_kernel, dim3(per_block), dim3(256), 0, st, (const int16_t*)coef, (const uint32_t*)len, (const uint32_t*)tot, bits, g.stream_words,
+                           (const JDev*)dev, g.nblocks, nb, ny);
     ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_count_kernel, dim3(g.nchunks), dim3(256), 0, st, (const uint32_t*)bits, (const uint32_t*)tot, cnt);
     ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, g.nchunks, (const uint32_t*)tot, tot + 1);
     ST_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3(g.nchunks), dim3(256), 0, st, (const uint32_t*)bits, (const uint32_t*)tot, (const uint32_t*)cnt, (uint8_t*)out, out_nbytes,
-                       hp, (const JDev*)dev);
+    if (ri)
+        hipLaunchKernelGGL(jpegr_enc_stuff_kernel, dim3(g.nchunks), dim3(256), 0, st, (const uint32_t*)bits, (const uint32_t*)tot, (const uint32_t*)cnt, (const uint32_t*)ibyte,
+                           rg.nint, ri, (uint8_t*)out, out_nbytes, hp, (const JDev*)dev);
+    else
+        hipLaunchKernelGGL(jpeg_stuff_kernel, dim3(g.nchunks), dim3(256), 0, st, (const uint32_t*)bits, (const uint32_t*)tot, (const uint32_t*)cnt, (uint8_t*)out, out_nbytes,
+                           hp, (const JDev*)dev);
     ST_CHECK_LAUNCH();
     return ST_OK;
 }

@@ -1,4 +1,4 @@
-// How csrc/jpeg_rst.hip cuts a scan with restart intervals into subsequences, in plain C++ so that a host program
+// How csrc/jpeg_dec.hip cuts a scan with restart intervals into subsequences, in plain C++ so that a host program
 // (tools/jpeg_rst_host_check.cpp, built with the host compiler's sanitizers) runs exactly what the kernels run.  Contract: README.md
 // "Restart intervals"; CPU restatement: tests/_jpeg_rst_ref.py.
 //

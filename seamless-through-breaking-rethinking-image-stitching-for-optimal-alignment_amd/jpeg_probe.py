@@ -7,7 +7,7 @@ Adobe transform 0, several scans, a marker other than FF00 inside the scan -- is
 device.
 
 `probe(data, restart=True)` also takes a file with one restart interval Ri > 0 (the last DRI in front of SOS) whose scan holds exactly
-ceil(MCUs / Ri) - 1 restart markers, RST0, RST1, ... RST7, RST0, ... in that order (csrc/jpeg_rst.hip; contract: README.md "Restart
+ceil(MCUs / Ri) - 1 restart markers, RST0, RST1, ... RST7, RST0, ... in that order (csrc/jpeg_dec.hip; contract: README.md "Restart
 intervals", tests/_jpeg_rst_ref.py).  A marker without DRI, a missing one, one too many or one out of order: None."""
 from typing import NamedTuple, Tuple
 

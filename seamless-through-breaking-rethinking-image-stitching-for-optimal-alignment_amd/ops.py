@@ -809,7 +809,7 @@ def jpeg_encode(u8, workspace=None, quality=None, subsampling=None, optimize=Fal
     `quality` (1..100), `subsampling` (RGB only: 0 4:4:4, 1 4:2:2, 2 4:2:0) and `optimize` are Pillow's `save` keywords (`st_jpeg_encode_u8_ex`);
     with all three at their defaults the call goes to `st_jpeg_encode_u8`, the same encoder (csrc/jpeg.hip) at Pillow's defaults -- quality 75,
     4:2:0, the Annex K tables.  `restart_marker_blocks` (MCUs, 0..65535) and `restart_marker_rows` (MCU rows; wins) are Pillow's too: a DRI
-    segment, FF D0..D7 between the intervals, DC predictions restarting (csrc/jpeg_rst.hip); None or 0: no restart interval.
+    segment, FF D0..D7 between the intervals, DC predictions restarting (the jpegr_enc_* kernels of csrc/jpeg.hip); None or 0: no restart interval.
     `workspace`: a uint8 device tensor of at least `jpeg_workspace_bytes` (same keywords) to reuse (stream-ordered: same stream as its last use)."""
     if u8.dtype != torch.uint8 or not (u8.dim() == 2 or (u8.dim() == 3 and u8.shape[2] == 3)):
         raise ValueError(f"uint8 [H,W,3] or [H,W] expected, got {u8.dtype} {tuple(u8.shape)}")
@@ -855,7 +855,7 @@ def jpeg_probe(data, restart=False):
     """Host-side marker parse of a JPEG file (bytes-like, or a CPU uint8 tensor): the `JpegInfo` `jpeg_decode` needs, or None when the file is
     outside the decoder's contract (progressive, restart intervals, other sampling factors, ...: jpeg_probe.py) and keeps the Pillow path.
     restart=True also takes a file with a restart interval whose markers are all there and in order (`JpegInfo.restart_interval` > 0:
-    csrc/jpeg_rst.hip decodes its entropy-coded part)."""
+    the jpegr_* kernels of csrc/jpeg_dec.hip decode its entropy-coded part)."""
     if isinstance(data, torch.Tensor):
         data = data.numpy().tobytes()
     return _jpeg_probe(data, restart=restart)

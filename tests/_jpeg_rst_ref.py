@@ -1,5 +1,5 @@
 """CPU restatement of JPEG restart intervals, on top of tests/_jpeg_ref.py, tests/_jpeg_opts_ref.py (encoder) and tests/_jpeg_dec_ref.py
-(decoder), which stay as they are.  csrc/jpeg_rst.hip implements the decoder side on the GPU; tests/test_jpeg_rst_cpu.py pins this file to
+(decoder), which stay as they are.  The jpegr_* kernels of csrc/jpeg_dec.hip implement the decoder side on the GPU; tests/test_jpeg_rst_cpu.py pins this file to
 Pillow on libjpeg-turbo (tests/golden/jpeg_rst_pil.npz, written by tools/make_jpeg_rst_golden.py).
 
 Encoder (libjpeg's jcmaster.c / jchuff.c as Pillow's `save(..., restart_marker_blocks=b, restart_marker_rows=r)` drives them):

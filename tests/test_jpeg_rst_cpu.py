@@ -1,7 +1,7 @@
 """The restart-interval contract, decided on the CPU: tests/_jpeg_rst_ref.py writes Pillow's files byte for byte and decodes them to Pillow's
 pixels (tests/golden/jpeg_rst_pil.npz and live Pillow), the goldens exercise every rule (a planted defect changes one), `jpeg_probe` takes a
 DRI file only with `restart=True` and only with all its markers in order, the entry and the size query reject bad arguments before any
-launch, the kernels of csrc/jpeg_rst.hip use no scratch and the LDS the README states, and their interval logic (csrc/jpeg_rst_core.h) runs
+launch, the restart kernels (jpegr_* in csrc/jpeg.hip and csrc/jpeg_dec.hip) use no scratch and the LDS the README states, and their interval logic (csrc/jpeg_rst_core.h) runs
 clean under the host compiler's address and undefined-behaviour sanitizers on golden, cut, damaged and random streams."""
 import importlib.util
 import io
@@ -226,14 +226,17 @@ def test_kernels_use_no_scratch_and_the_stated_lds():
     spec = importlib.util.spec_from_file_location("_stitch_build_jr", os.path.join(PKG, "build.py"))
     build = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build)
+    text = ""
     with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "jpeg_rst.s")
-        subprocess.check_call(build.compile_cmd("jpeg_rst.hip", out, ["-S", "--cuda-device-only"]), stderr=subprocess.DEVNULL)
-        text = open(out).read()
+        for src in ("jpeg.hip", "jpeg_dec.hip"):                              # the encoder's and the decoder's restart kernels
+            out = os.path.join(td, src.replace(".hip", ".s"))
+            subprocess.check_call(build.compile_cmd(src, out, ["-S", "--cuda-device-only"]), stderr=subprocess.DEVNULL)
+            text += open(out).read()
     rep = {}
     for m in re.finditer(r"\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+)\n.*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)",
                          text, re.S):
-        rep[m.group(2)] = dict(lds=int(m.group(1)), scratch=int(m.group(3)), vgpr=int(m.group(4)), spill=int(m.group(5)))
+        if "jpegr_" in m.group(2):                                            # (the plain kernels' rows: tests/test_jpeg_cpu.py, tests/test_jpeg_dec_cpu.py)
+            rep[m.group(2)] = dict(lds=int(m.group(1)), scratch=int(m.group(3)), vgpr=int(m.group(4)), spill=int(m.group(5)))
     lds = {"jpegr_count_kernel": 32, "jpegr_unstuff_kernel": 32, "jpegr_cut_kernel": 0, "jpegr_enc_hist_kernel": 4 * 257 * 4, "jpegr_enc_bits_kernel": ENC_TABLES,
            "jpegr_enc_pad_kernel": 0, "jpegr_enc_offsets_kernel": 0, "jpegr_enc_pack_kernel": ENC_TABLES, "jpegr_enc_stuff_kernel": 16, "jpegr_sync_kernel": LDS_TABLES + LDS_STREAM + 2048 + 8 + WGRED,       # (+ the base word, padded to 8)
            "jpegr_write_kernel": LDS_TABLES + LDS_STREAM + 4, "jpegr_dc_kernel": 132}

@@ -1,4 +1,4 @@
-"""csrc/jpeg_rst.hip on the GPU: `ops.jpeg_decode` gives Pillow's pixels bit for bit on every file of tests/golden/jpeg_rst_pil.npz, and on files
+"""The restart kernels (jpegr_* in csrc/jpeg_dec.hip and csrc/jpeg.hip) on the GPU: `ops.jpeg_decode` gives Pillow's pixels bit for bit on every file of tests/golden/jpeg_rst_pil.npz, and on files
 made here with Pillow -- one interval over three workgroups of subsequences, two long intervals, a row per interval, an MCU per interval, the
 flat image whose stream never synchronises -- the pixels of the same image's file without restart markers, which go through the existing
 path; whatever the row stride, stream or workspace history.  A damaged interval sets the status and leaves every other interval exact, a

@@ -25,7 +25,7 @@
 
     python tools/bench_jpeg.py --restart [--out profiles/jpeg_rst_enc_bench.json]
 
-* restart intervals (csrc/jpeg_rst.hip): per image Pillow on one thread and the GPU at the defaults and with `restart_marker_rows=1`, in
+* restart intervals (the jpegr_enc_* kernels of csrc/jpeg.hip): per image Pillow on one thread and the GPU at the defaults and with `restart_marker_rows=1`, in
   one run (the defaults against a parent checkout are `--against`'s business).
 """
 import argparse
@@ -275,7 +275,7 @@ def main():
         torch.cuda.synchronize()
         return
     if a.restart:
-        res = {"what": "GPU JPEG encoder at the defaults and with restart_marker_rows=1 (csrc/jpeg_rst.hip) vs Pillow (one thread, same keywords), same run, one MI355X",
+        res = {"what": "GPU JPEG encoder at the defaults and with restart_marker_rows=1 (the jpegr_enc_* kernels of csrc/jpeg.hip) vs Pillow (one thread, same keywords), same run, one MI355X",
                "per_image": {}}
         for name, u8 in imgs.items():
             res["per_image"][name] = {}

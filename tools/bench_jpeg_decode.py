@@ -12,11 +12,18 @@
 
     python tools/bench_jpeg_decode.py --restart [--out profiles/jpeg_rst_bench.json] [--no-profile]
 
-* restart intervals (csrc/jpeg_rst.hip): the same four images written without DRI, with `restart_marker_rows=1` and with
+* restart intervals (the jpegr_* kernels of csrc/jpeg_dec.hip): the same four images written without DRI, with `restart_marker_rows=1` and with
   `restart_marker_blocks=4`: Pillow on one thread, single call and back to back, the intervals and subsequences of each file; per kernel one
   `rocprofv3 --kernel-trace --stats` child making 200 decodes of the 512x512 quality-75 file with a row per interval, with the synchronise
   launches that did work counted from the trace (a launch that returns at once takes a few microseconds); the evaluation loop on `--pairs`
   synthetic pairs written with `restart_marker_rows=1`, `gpu_decode` off against on (`--pairs 0`: not run).
+
+    python tools/bench_jpeg_decode.py --against OTHER_ROOT [--rounds 7] [--out profiles/jpeg_rst_unify_bench.json]
+
+* this tree's library against the one built in another checkout (OTHER_ROOT: an exported commit with its library built), per file of the
+  three restart variants: every sample is a fresh child process that imports one of the two trees, the two alternate for `--rounds`
+  rounds; per row both versions' medians over the rounds and each version's min-max, and whether this tree's median lies inside the
+  other's own min-max.
 """
 import argparse
 import csv
@@ -196,6 +203,24 @@ def restart_bench(no_profile, pairs, rounds):
     return res
 
 
+def versions_bench(other_root, rounds):
+    roots = {"other": os.path.abspath(other_root), "this": ROOT}
+    samples = {v: [] for v in roots}
+    for _ in range(rounds):
+        for v, root in roots.items():
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--sample", "--root", root], check=True, timeout=300, stdout=subprocess.PIPE, text=True)
+            samples[v].append(json.loads(r.stdout.strip().splitlines()[-1]))
+    res = {}
+    for row in samples["this"][0]:
+        res[row] = {}
+        for key in ("single_call_us", "back_to_back_us"):
+            e = {v: dict(median=float(np.median(xs)), min=min(xs), max=max(xs)) for v in roots for xs in [[s_[row][key] for s_ in samples[v]]]}
+            e["this_median_inside_other_min_max"] = bool(e["other"]["min"] <= e["this"]["median"] <= e["other"]["max"])
+            e["this_median_not_above_other_max"] = bool(e["this"]["median"] <= e["other"]["max"])
+            res[row][key] = e
+    return res
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--out", default="")
@@ -206,13 +231,36 @@ def main():
     p.add_argument("--no-profile", action="store_true")
     p.add_argument("--inner-profile", type=int, default=0)
     p.add_argument("--inner-eval", nargs=3, default=None)
+    p.add_argument("--against", default="", help="another checkout with its library built -> profiles/jpeg_rst_unify_bench.json")
+    p.add_argument("--against-label", default="", help="how the result file names the other checkout (default: its path)")
+    p.add_argument("--sample", action="store_true", help=argparse.SUPPRESS)
+    p.add_argument("--root", default="", help=argparse.SUPPRESS)
     args = p.parse_args()
     if args.inner_eval:
         return inner_eval(args.inner_eval[0], args.inner_eval[1], int(args.inner_eval[2]), 1)
-    sys.path.insert(0, ROOT)
+    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_rst_unify_bench.json" if args.against else "jpeg_rst_bench.json" if args.restart else "jpeg_decode_bench.json")
+    if args.against:
+        res = {"what": "ops.jpeg_decode of this tree against the library of another checkout, one MI355X: HIP-event median of 50 single calls and 50 calls "
+                       "back to back per sample, every sample a fresh process, the two versions alternating",
+               "other": args.against_label or args.against, "rounds": args.rounds, "per_file": versions_bench(args.against, args.rounds)}
+        res["every_row_not_above_other_max"] = all(e[k]["this_median_not_above_other_max"] for e in res["per_file"].values() for k in e)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return None
+    sys.path.insert(0, args.root or ROOT)
     import torch
     from stitch_amd import ops
-    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_rst_bench.json" if args.restart else "jpeg_decode_bench.json")
+    if args.sample:                                                # a child of --against: the package of the checkout at args.root
+        from stitch_amd import _lib
+        assert os.path.dirname(os.path.dirname(_lib.LIB_PATH)) == args.root, _lib.LIB_PATH
+        out = {}
+        for variant, kw in RESTART_VARIANTS.items():
+            for name, data in files(**kw).items():
+                single, b2b = decode_times(data)
+                out[f"{name}/{variant}"] = dict(single_call_us=single * 1e3, back_to_back_us=b2b * 1e3)
+        print(json.dumps(out))
+        return None
     if args.inner_profile:
         data = files(**(RESTART_VARIANTS["rows_1"] if args.restart else {}))["rgb_512_q75"]
         info = ops.jpeg_probe(data, restart=True)

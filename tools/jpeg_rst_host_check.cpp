@@ -1,4 +1,4 @@
-// Runs the interval logic of csrc/jpeg_rst.hip (csrc/jpeg_rst_core.h and csrc/jpeg_dec_core.h, plain C++) on the host, stand-alone, so that the
+// Runs the interval logic of csrc/jpeg_dec.hip's restart kernels (csrc/jpeg_rst_core.h and csrc/jpeg_dec_core.h, plain C++) on the host, stand-alone, so that the
 // host compiler's sanitizers see it:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I <pkg>/csrc tools/jpeg_rst_host_check.cpp
 //

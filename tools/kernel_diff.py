@@ -1,6 +1,7 @@
 """Which GPU kernels differ between two builds of the library (no GPU needed: the ROCm LLVM tools only).
 Extracts the gfx950 code objects of both libraries and compares, per kernel symbol, the disassembly (addresses and encodings removed;
-branch targets are pc-relative, so they compare as they are) and the metadata note (register, spill, LDS, scratch, kernarg and workgroup
+branch targets are pc-relative, so they compare as they are; the pc-relative literal behind s_getpc_b64 that addresses a __device__
+variable changes with every kernel added to or taken from the translation unit, so it is masked) and the metadata note (register, spill, LDS, scratch, kernarg and workgroup
 figures).  One line per kernel that was added, lost, defined twice or changed; exit status 1 if there is any.  A refactor that moves
 kernels between translation units should print nothing; a kernel change should print only the kernels it meant to touch.
 usage: python tools/kernel_diff.py OLD/libstitch_gfx950.so NEW/libstitch_gfx950.so"""
@@ -34,6 +35,9 @@ def kernels(lib):
                 ins = [l.split("//")[0].strip() for l in m.group(2).splitlines() if l.strip()]
                 while ins and not ins[-1].startswith("s_endpgm"):
                     ins.pop()                                                                  # alignment padding behind the kernel's last instruction
+                for i in range(1, len(ins)):                                                   # the address of a __device__ variable: pc + a literal that
+                    if ins[i - 1].startswith("s_getpc_b64") and ins[i].startswith("s_add_u32"):   # says where the kernel lies in its code object, not what it does
+                        ins[i] = re.sub(r"0x[0-9a-f]+$", "<pc-relative>", ins[i])
                 if m.group(1) in out:
                     twice.add(m.group(1))
                 out[m.group(1)] = (ins, meta[m.group(1)])
