@@ -761,6 +761,24 @@ int st_tr_blend(const float* out3, const float* detail3, const float* mask, int3
 /* step 8: uint8 (x * 127.5 + 127.5).round() (halves to even) clamped to 0..255; dense, n >= 1.                                        */
 int st_tr_to_u8(const float* x, uint8_t* out, int64_t n, void* stream);
 
+/* ---- multiband_fusion: Laplacian-pyramid seam blend of the two warped images (csrc/multiband.hip; contract in README.md, CPU restatement
+ *      tests/_multiband_ref.py; this project's own contract, unpinned against OpenCV's detail::MultiBandBlender) -------------------------- */
+/* exact squared Euclidean distance transform: mask uint8 [H,W], sites = the pixels with mask == 0 and, with border_is_site != 0, the
+ * one-pixel ring round the canvas.  D int32 [H,W] = squared distance to the nearest site (INT32_MAX when there is none); index (may be
+ * NULL) int32 [H,W] = the lowest row-major index among the canvas sites at that distance, -1 when there is none or only the ring is that
+ * near.  D doubles as the scratch of the column pass.  ST_EINVAL before any launch: mask or D null, a side outside 1..4096.  Two launches. */
+int st_edt_sq_u8(const uint8_t* mask, int32_t H, int32_t W, int32_t border_is_site, int32_t* D, int32_t* index, void* stream);
+/* bytes of workspace st_multiband_blend needs; 0 for a side outside 1..4096 or levels outside 0..16.                                 */
+int st_multiband_workspace_bytes(int32_t H, int32_t W, int32_t levels);
+/* img1, img2 float32 [3,H,W] (clamped to 0..255 and truncated on load); mask1, mask2 float32 [H,W] (plane 0 of the mask tensor; set where
+ * > 0.5); levels = requested REDUCE steps (0 = hard seam along the distance partition; capped where both sides reach 1); out float32
+ * [3,H,W], 0 outside the union of the masks.  9 + 2 x (effective levels) launches on `stream`, nothing else: no synchronisation, no
+ * allocation, the workspace needs no initialisation and may be reused by the next call on the same stream.  ST_EINVAL before any
+ * launch: a null pointer, a side outside 1..4096, levels outside 0..16, a workspace smaller than st_multiband_workspace_bytes or not
+ * 16-byte aligned.                                                                                                                  */
+int st_multiband_blend(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels,
+                       float* out, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

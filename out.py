@@ -15,7 +15,8 @@ of scope) a pass-through stands in, so with the shipped configs in
 is not synthesised (with `inpaint_all_area`: no hole is); `--inf_cfg all_img1_with_inpaint_g12_cv` / `inpaint_all_area_g12_cv`
 select `cv_inpainter`, the reference's OpenCV Telea inpainter restated as GPU kernels (README.md; unpinned against OpenCV), which
 fills them; with the shipped `tps_method="opencv"` the spline is this package's own pixel-unit TPS (OpenCV is not
-installable here: unpinned against OpenCV)."""
+installable here: unpinned against OpenCV).  `--multiband_fusion` adds an eleventh file of this package's own, `multiband_fusion.jpg`: the two
+warped images blended over a Laplacian pyramid along their distance-transform seam (README.md, multiband_fusion)."""
 from __future__ import annotations
 
 import argparse
@@ -50,6 +51,9 @@ def get_config(argv=None):
                    help="restart interval of the result JPEGs in MCUs (Pillow's restart_marker_blocks), on either encoder")
     p.add_argument("--jpeg_restart_rows", type=int, default=None, metavar="N",
                    help="restart interval of the result JPEGs in MCU rows (Pillow's restart_marker_rows; wins over --jpeg_restart_blocks)")
+    p.add_argument("--multiband_fusion", action="store_true",
+                   help="also write multiband_fusion.jpg: the two warped images blended over a Laplacian pyramid along the distance-transform seam (GPU)")
+    p.add_argument("--multiband_levels", type=int, default=None, metavar="N", help="pyramid levels of --multiband_fusion (0..16; default 5)")
     p.add_argument("--gpu_decode", action="store_true",
                    help="decode the input JPEGs on the GPU (Pillow's pixels, bit for bit); files outside the decoder's contract keep Pillow")
     p.add_argument("--dry-run", dest="dry_run", action="store_true",
@@ -58,9 +62,9 @@ def get_config(argv=None):
     import stitch_amd
     cfg, tps = stitch_amd.load_inference_config(args.inf_cfg, args.model_config_name)
     for k, v in vars(args).items():
-        if k in ("restore_ckpt", "gpu_jpeg", "gpu_decode", "jpeg_optimize") and not v:         # (a switch that is off: config.txt stays what it was before the switch existed)
+        if k in ("restore_ckpt", "gpu_jpeg", "gpu_decode", "jpeg_optimize", "multiband_fusion") and not v:         # (a switch that is off: config.txt stays what it was before the switch existed)
             continue
-        if k in ("jpeg_quality", "jpeg_subsampling", "jpeg_restart_blocks", "jpeg_restart_rows") and v is None:
+        if k in ("jpeg_quality", "jpeg_subsampling", "jpeg_restart_blocks", "jpeg_restart_rows", "multiband_levels") and v is None:
             continue
         cfg[k] = v
     cfg.TPS_PIPELINE_CONFIG = tps
@@ -164,6 +168,14 @@ def jpeg_params_of(cfg):
     return kw or None
 
 
+def multiband_of(cfg):
+    """The `multiband` argument the flags --multiband_fusion / --multiband_levels ask for: None without the switch, else the level count."""
+    if not getattr(cfg, "multiband_fusion", False):
+        return None
+    levels = getattr(cfg, "multiband_levels", None)
+    return 5 if levels is None else int(levels)
+
+
 class _Saver:
     """JPEG writes of out.py:260-312.  The uint8 conversion runs on the GPU (clip + truncation, as `to_pillow_fn` does on the
     host), the bytes are copied to the host in the caller's thread, the JPEG encode + file write go to ``pool`` when one is given
@@ -256,7 +268,7 @@ def load_inpainter(name):
 
 
 def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_model=None, inpainter=None, forward=None, saver=None,
-                       gpu_jpeg=False, gpu_decode=False, jpeg_params=None):
+                       gpu_jpeg=False, gpu_decode=False, jpeg_params=None, multiband=None):
     """out.py:158-312: forward (`test_out`), TPS post-pipeline with the configured `mix_fn`, saves, composition.  The inpainter
     is the caller's, else the pass-through stand-in (`load_inpainter`: `transref_inpainter` needs its checkpoint, the diffusion one is
     out of scope): with the stand-in, in `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the
@@ -267,7 +279,10 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     launches pair i + 1's hipGraph before it finishes pair i); default = load + ``warp_model(..., type="test_out")`` here.
     ``saver``: a ``_Saver`` (JPEG encodes on a thread pool); default = write synchronously, with ``gpu_jpeg`` through the device encoder.
     ``gpu_decode``: the two input files are decoded on the device (`readSingleData`, `ops.jpeg_decode`) when this function loads them.
-    ``jpeg_params``: the `save` keywords of the default saver (`_Saver`); a caller's ``saver`` carries its own."""
+    ``jpeg_params``: the `save` keywords of the default saver (`_Saver`); a caller's ``saver`` carries its own.
+    ``multiband``: None, or the pyramid levels of an eleventh file `multiband_fusion.jpg` written after `ave_fusion.jpg`: `output1` and
+    `output2` blended by `ops.multiband_blend` under `mask1` / `mask2`, as they go to the saver (README.md, multiband_fusion); the blend is
+    returned as `multiband_image`.  This file is the package's own, not one of the reference's."""
     own_saver = saver is None
     statuses = []
     saver = saver or _Saver(gpu_jpeg=gpu_jpeg, jpeg_params=jpeg_params)
@@ -314,6 +329,10 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     for key in ("mask1", "mask2"):
         saver.array((out[key] > 0.5)[0, 0].to(torch.uint8).mul(255), result_path + key + ".jpg")
     saver.image(out["new_blend_image"].float(), result_path + "ave_fusion.jpg")
+    if multiband is not None:
+        out = dict(out, multiband_image=stitch_amd.ops.multiband_blend(out["output1"].float().contiguous(), out["output2"].float().contiguous(),
+                                                                      out["mask1"].float(), out["mask2"].float(), levels=multiband))
+        saver.image(out["multiband_image"], result_path + "multiband_fusion.jpg")
     if composition_model is not None:
         # out.py:277-312: learned seam masks + composed image from the UDIS2 composition network
         mask1, mask2 = (out["mask1"] > 0.5).float(), (out["mask2"] > 0.5).float()
@@ -330,7 +349,7 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
 
 
 def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=None, on_done=None, depth=2, gpu_jpeg=False, gpu_decode=False,
-              jpeg_params=None):
+              jpeg_params=None, multiband=None):
     """The inference loop of out.py:351-357 as a software pipeline, `depth` pairs in flight.  While pair i is finished on the host
     (canvas bounds read back, canvas kernels, TPS post-pipeline with its control-point round trips, composition, device->host copies
     of the images), the network parts of pairs i + 1 .. i + depth - 1 -- both nets at 512x512, ~1 000 launches each, replayed from a
@@ -344,7 +363,8 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
     first, at the end of the pair; the pool then only writes files.
     ``gpu_decode``: the decode threads only read and probe the files (`readSingleData`), the pixels are made on the pair's stream
     (`ops.jpeg_decode`) in front of its graph launch; the status words are checked when the pair is finished.
-    ``jpeg_params``: Pillow's `save` keywords for the result files (`_Saver`), on either encoder."""
+    ``jpeg_params``: Pillow's `save` keywords for the result files (`_Saver`), on either encoder.
+    ``multiband``: the pyramid levels of `multiband_fusion.jpg` (`inference_one_data`), blended on the pair's stream; None: not written."""
     from concurrent.futures import ThreadPoolExecutor
     if not todo:
         return []
@@ -380,7 +400,7 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
             g, handle, st, statuses = inflight.pop(0)
             with torch.cuda.stream(st):
                 out, rp = inference_one_data(cfg, dd, save_root, model, composition_model, inpainter,
-                                             forward=lambda: g.finish(handle), saver=saver)
+                                             forward=lambda: g.finish(handle), saver=saver, multiband=multiband)
                 check_decode(statuses)
             # no host wait here: the graph of this slot is launched again on the SAME stream (pair j + depth), i.e. after everything
             # that reads this pair's static buffers
@@ -446,7 +466,7 @@ def main(argv=None):
             continue
         todo.append(dd)
     run_pairs(cfg, todo, save_root, model, composition_model, inpainter, gpu_jpeg=bool(getattr(cfg, "gpu_jpeg", False)),
-              gpu_decode=bool(getattr(cfg, "gpu_decode", False)), jpeg_params=jpeg_params_of(cfg))
+              gpu_decode=bool(getattr(cfg, "gpu_decode", False)), jpeg_params=jpeg_params_of(cfg), multiband=multiband_of(cfg))
     if world > 1:
         import torch.distributed as tdist
         tdist.barrier()

@@ -1351,3 +1351,57 @@ def tr_blend(out3, detail3, mask, fake3):
 def tr_to_u8(x, out):
     check(lib.st_tr_to_u8(_pc(x), _pc(out), x.numel(), _stream()), "st_tr_to_u8")
     return out
+
+
+# ---- multiband_fusion: Laplacian-pyramid seam blend (csrc/multiband.hip; README.md, multiband_fusion) ------------------------------
+MULTIBAND_MAX_SIDE = 4096
+MULTIBAND_MAX_LEVELS = 16
+
+
+def edt_sq(mask, border_is_site=True, return_index=False):
+    """Exact squared Euclidean distance transform on the GPU: mask [H,W] (bool, or any dtype: nonzero = inside) -> int32 [H,W], the squared
+    distance of every pixel to the nearest pixel with mask == 0; with ``border_is_site`` the one-pixel ring round the canvas counts as
+    zero too.  Without any site the distance is INT32_MAX.  ``return_index``: also int32 [H,W], the lowest row-major index among the
+    canvas pixels at that distance (-1 when there is none, or when only the ring is that near)."""
+    if mask.dim() != 2:
+        raise ValueError(f"mask [H,W] expected, got {tuple(mask.shape)}")
+    H, W = mask.shape
+    if not (1 <= H <= MULTIBAND_MAX_SIDE and 1 <= W <= MULTIBAND_MAX_SIDE):
+        raise ValueError(f"sides must be in 1..{MULTIBAND_MAX_SIDE}, got {H} x {W}")
+    m = (mask != 0).to(torch.uint8).contiguous()
+    D = torch.empty((H, W), dtype=torch.int32, device=mask.device)
+    idx = torch.empty((H, W), dtype=torch.int32, device=mask.device) if return_index else None
+    check(lib.st_edt_sq_u8(_pc(m), H, W, int(bool(border_is_site)), _p(D), _p(idx), _stream()), "st_edt_sq_u8")
+    return (D, idx) if return_index else D
+
+
+def multiband_workspace_bytes(H, W, levels):
+    """bytes of workspace `multiband_blend` needs for an H x W canvas; 0 for a shape or level count outside the contract"""
+    return int(lib.st_multiband_workspace_bytes(int(H), int(W), int(levels)))
+
+
+def multiband_blend(img1, img2, mask1, mask2, levels=5, workspace=None):
+    """Multi-band (Laplacian pyramid) blend of two warped images along the distance-transform seam of their masks (README.md,
+    multiband_fusion): img1, img2 fp32 [1,3,H,W] (clamped to 0..255 and truncated, as the saver does), mask1, mask2 fp32 [1,1,H,W] or
+    [1,3,H,W] (channel 0 > 0.5) -> fp32 [1,3,H,W], 0 outside the union.  ``levels`` = REDUCE steps (0 = hard seam).  ``workspace``: a
+    uint8 device tensor of at least `multiband_workspace_bytes` bytes, 16-byte aligned (default: allocated here); all launches go to the
+    current stream and nothing is read back."""
+    if img1.dim() != 4 or img1.shape[0] != 1 or img1.shape[1] != 3 or img2.shape != img1.shape:
+        raise ValueError(f"img1, img2 [1,3,H,W] expected, got {tuple(img1.shape)} and {tuple(img2.shape)}")
+    H, W = img1.shape[2:]
+    for m in (mask1, mask2):
+        if m.dim() != 4 or m.shape[0] != 1 or m.shape[1] not in (1, 3) or tuple(m.shape[2:]) != (H, W):
+            raise ValueError(f"mask [1,1,{H},{W}] or [1,3,{H},{W}] expected, got {tuple(m.shape)}")
+    for t in (img1, img2, mask1, mask2):
+        if t.dtype != torch.float32:
+            raise ValueError(f"float32 tensors expected, got {t.dtype}")
+    need = multiband_workspace_bytes(H, W, levels)
+    if need == 0:
+        raise ValueError(f"sides must be in 1..{MULTIBAND_MAX_SIDE} and levels in 0..{MULTIBAND_MAX_LEVELS}, got {H} x {W}, levels {levels}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=img1.device)
+    out = torch.empty_like(img1, memory_format=torch.contiguous_format)
+    mask1, mask2 = mask1[:, :1].contiguous(), mask2[:, :1].contiguous()         # channel 0 (no copy unless the mask is a strided view)
+    check(lib.st_multiband_blend(_pc(img1), _pc(img2), _pc(mask1), _pc(mask2), H, W, int(levels), _p(out), _p(workspace),
+                                 workspace.numel() * workspace.element_size(), _stream()), "st_multiband_blend")
+    return out
