@@ -249,7 +249,9 @@ int st_layernorm(const float* x, int32_t ldx, const float* w, const float* b, fl
 int st_softmax_rows(float* x, int32_t ld, int32_t rows, int32_t C, void* stream);
 /* F.normalize(p=2, dim=C) on NHWC rows (core/UDIS2/Homography/network.py:150-151).                  */
 int st_l2norm_rows(const float* x, float* out, int32_t rows, int32_t C, void* stream);
-/* nn.MaxPool2d on NHWC (network.py:22,28,34; torchvision resnet maxpool 3/2/1).                     */
+/* nn.MaxPool2d on NHWC (network.py:22,28,34; torchvision resnet maxpool 3/2/1).  torch's limits hold:
+ * 0 <= 2 p <= k and H + 2 p >= k, W + 2 p >= k (ST_EINVAL otherwise); out [B, Ho, Wo, C],
+ * Ho = floor((H + 2 p - k) / s) + 1.                                                                  */
 int st_maxpool_nhwc(const float* x, float* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
                     int32_t s, int32_t p, void* stream);
 /* PEG PosConv: depthwise 3x3 + bias + identity (twins.py:793-808); w [9, C].                        */

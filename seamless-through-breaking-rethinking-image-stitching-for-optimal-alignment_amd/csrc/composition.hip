@@ -21,7 +21,8 @@ __global__ __launch_bounds__(256) void resize_nearest_rows_kernel(const float* _
 
 extern "C" int st_resize_nearest_rows(const float* x, int32_t ldx, float* out, int32_t ldo, int32_t B, int32_t H, int32_t W,
                                       int32_t C, int32_t oh, int32_t ow, void* stream) {
-    if (!x || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || (ldx & 3) || (ldo & 3) || oh <= 0 || ow <= 0) return ST_EINVAL;
+    if (!x || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || (ldx & 3) || (ldo & 3) || ldx < C || ldo < C || oh <= 0 || ow <= 0)
+        return ST_EINVAL;
     const size_t total = (size_t)B * oh * ow * (C / 4);
     hipLaunchKernelGGL(resize_nearest_rows_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, ldx, out, ldo, B,
                        H, W, C / 4, oh, ow, (float)H / (float)oh, (float)W / (float)ow);
@@ -42,7 +43,8 @@ __global__ __launch_bounds__(256) void sub_rows_kernel(const float* __restrict__
 
 extern "C" int st_sub_rows(const float* a, int32_t lda, const float* b, int32_t ldb, float* out, int32_t ldo, int64_t rows, int32_t C,
                            void* stream) {
-    if (!a || !b || !out || rows <= 0 || C <= 0 || (C & 3) || (lda & 3) || (ldb & 3) || (ldo & 3)) return ST_EINVAL;
+    if (!a || !b || !out || rows <= 0 || C <= 0 || (C & 3) || (lda & 3) || (ldb & 3) || (ldo & 3) || lda < C || ldb < C || ldo < C)
+        return ST_EINVAL;
     const size_t total = (size_t)rows * (C / 4);
     hipLaunchKernelGGL(sub_rows_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb, out, ldo,
                        (size_t)rows, C / 4);
@@ -69,7 +71,7 @@ __global__ __launch_bounds__(256) void compose_blend_kernel(const float* __restr
 extern "C" int st_compose_blend(const float* warp1, const float* warp2, const float* mask1, const float* mask2, const float* net_out,
                                 int32_t ld_net, float* learned_mask1, float* learned_mask2, float* stitched, int32_t B, int32_t H,
                                 int32_t W, void* stream) {
-    if (!warp1 || !warp2 || !mask1 || !mask2 || !net_out || !learned_mask1 || !learned_mask2 || !stitched || B <= 0 || H <= 0 || W <= 0)
+    if (!warp1 || !warp2 || !mask1 || !mask2 || !net_out || !learned_mask1 || !learned_mask2 || !stitched || ld_net <= 0 || B <= 0 || H <= 0 || W <= 0)
         return ST_EINVAL;
     const size_t total = (size_t)B * 3 * H * W;
     hipLaunchKernelGGL(compose_blend_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, warp1, warp2, mask1, mask2,

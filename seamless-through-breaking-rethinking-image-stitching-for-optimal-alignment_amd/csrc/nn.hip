@@ -172,6 +172,9 @@ __global__ void maxpool_kernel(const float* __restrict__ x, float* __restrict__ 
 extern "C" int st_maxpool_nhwc(const float* x, float* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
                                int32_t s, int32_t p, void* stream) {
     if (!x || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || s <= 0) return ST_EINVAL;
+    // nn.MaxPool2d's own limits: pad at most half the window, and a padded input that holds one whole window (with them the C division
+    // below is the floor of the definition, and every window holds at least one input pixel)
+    if (p < 0 || 2 * p > k || H + 2 * p < k || W + 2 * p < k) return ST_EINVAL;
     const int Ho = (H + 2 * p - k) / s + 1, Wo = (W + 2 * p - k) / s + 1;
     const size_t total = (size_t)B * Ho * Wo * C;
     hipLaunchKernelGGL(maxpool_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W, C, k,
@@ -219,7 +222,7 @@ __global__ void dwconv3x3_kernel(const float* __restrict__ x, const float* __res
 
 extern "C" int st_dwconv3x3_residual(const float* x, const float* w, const float* bias, float* out, int32_t B, int32_t H,
                                      int32_t W, int32_t C, void* stream) {
-    if (!x || !w || !bias || !out || C % 4) return ST_EINVAL;
+    if (!x || !w || !bias || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4) return ST_EINVAL;
     const size_t total = (size_t)B * H * W * (C / 4);
     hipLaunchKernelGGL(dwconv3x3_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, B,
                        H, W, C);
@@ -262,7 +265,7 @@ __global__ void sine_pe_kernel(float* __restrict__ out, int ld, int rows, int di
 
 extern "C" int st_sine_pe(float* out, int32_t ld, int32_t rows, int32_t dim, const float* coords, int32_t ldc, int32_t Wg,
                           int32_t ws, int32_t period, float cscale, float coff, int32_t accumulate, void* stream) {
-    if (!out || rows <= 0 || dim <= 0 || dim % 4 || (!coords && Wg <= 0)) return ST_EINVAL;
+    if (!out || rows <= 0 || dim <= 0 || dim % 4 || ld < dim || (coords ? ldc < 2 : Wg <= 0) || ws < 0 || period < 0 || accumulate < 0) return ST_EINVAL;
     const size_t total = (size_t)rows * (dim / 4);
     hipLaunchKernelGGL(sine_pe_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, ld, rows, dim,
                        coords, ldc, Wg, ws, period, cscale, coff, accumulate);
@@ -916,7 +919,7 @@ __global__ void copy2d_kernel(const float* __restrict__ src, int lds_, float* __
 }
 
 extern "C" int st_copy2d(const float* src, int32_t lds_, float* dst, int32_t ldd, int32_t rows, int32_t cols, void* stream) {
-    if (!src || !dst || rows <= 0 || cols <= 0) return ST_EINVAL;
+    if (!src || !dst || rows <= 0 || cols <= 0 || lds_ < cols || ldd < cols) return ST_EINVAL;
     const size_t total = (size_t)rows * cols;
     hipLaunchKernelGGL(copy2d_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, lds_, dst, ldd, rows,
                        cols);
@@ -942,7 +945,7 @@ __global__ void prep_image_kernel(const float* __restrict__ src, float* __restri
 
 extern "C" int st_prep_image(const float* src, float* dst, int32_t B, int32_t C, int32_t H, int32_t W, int32_t ldo,
                              float mul, float div, float sub, void* stream) {
-    if (!src || !dst || ldo < C) return ST_EINVAL;
+    if (!src || !dst || B <= 0 || C <= 0 || H <= 0 || W <= 0 || ldo < C) return ST_EINVAL;
     const size_t total = (size_t)B * H * W;
     hipLaunchKernelGGL(prep_image_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, dst, B, C, H, W,
                        ldo, mul, div, sub);

@@ -40,8 +40,10 @@ int st_morph_open19(const float* mask, float* out, void* scratch_u8x2, int32_t N
 int st_patch_embed(const float* cost_maps, const float* const* weights, int32_t ld_f0, const float* pe_bias, float* s1,
                    float* s2, float* s3, float* s4, float* tokens, int32_t M, int32_t H, int32_t W, void* workspace,
                    int64_t workspace_floats, void* stream) {
-    if (!cost_maps || !weights || !pe_bias || !s2 || !s3 || !s4 || !tokens || M <= 0 || H <= 0 || W <= 0)
+    if (!cost_maps || !weights || !pe_bias || !s2 || !s3 || !s4 || !tokens || M <= 0 || H <= 0 || W <= 0 || ld_f0 < 64)
         return ST_EINVAL;
+    for (int i = 0; i < 11; ++i)
+        if (!weights[i]) return ST_EINVAL;
     const int Hp = (H + 7) / 8 * 8, Wp = (W + 7) / 8 * 8;      // zero pad to the patch size (encoder.py:63-66)
     const int H1 = Hp / 2, W1 = Wp / 2, H2 = Hp / 4, W2 = Wp / 4, H3 = Hp / 8, W3 = Wp / 8, P = H3 * W3;
     // the first two convs of a 64x64 map in one launch, s1 kept on the CU (csrc/patchembed.hip; bit-identical)
@@ -75,6 +77,9 @@ int st_patch_embed_split3(const float* cost_maps, const float* const* weights, i
                           int64_t s2_pstride, const void* c4_w_planes, int64_t c4_w_pstride, float* s3, float* s4, float* tokens, int32_t M,
                           int32_t H, int32_t W, const void* tail_image, int64_t tail_image_bytes, void* workspace, int64_t workspace_floats, void* stream) {
     if (!cost_maps || !weights || !pe_bias || !s2_planes || !c4_w_planes || !s3 || (!s4 && !tail_image) || !tokens || M <= 0 || H != 64 || W != 64) return ST_EINVAL;
+    if (!tail_image && ld_f0 < 64) return ST_EINVAL;
+    for (int i = 0; i < 11; ++i)
+        if (!weights[i]) return ST_EINVAL;
     const int H2 = 16, W2 = 16, H3 = 8, W3 = 8, P = 64;
     ST_TRY(st_patch_conv12_planes(cost_maps, weights[0], weights[1], weights[2], weights[3], s2_planes, s2_pstride, M, H, W, stream));
     {

@@ -529,6 +529,13 @@ def patch_conv12(maps, c0_w, c0_b, c2_w, c2_b, out, M, H=64, W=64):
     return out
 
 
+def patch_conv12_planes(maps, c0_w, c0_b, c2_w, c2_b, planes, M, H=64, W=64):
+    """patch_conv12 whose result leaves as the bf16 planes of ``planes`` = Planes(rows >= M*256, 32) (st_patch_conv12_planes)"""
+    check(lib.st_patch_conv12_planes(_pc(maps), _pc(c0_w), _pc(c0_b), _pc(c2_w), _pc(c2_b), C.c_void_p(planes.ptr()), planes.pstride, M, H, W, _stream()),
+          "st_patch_conv12_planes")
+    return planes
+
+
 def cost_lookup9x9(maps, coords, out, Nq, H2, W2):
     check(lib.st_cost_lookup9x9(_p(maps), _pc(coords), _p(out), _ld(out), Nq, H2, W2, _stream()), "st_cost_lookup9x9")
     return out
