@@ -781,6 +781,35 @@ int st_multiband_workspace_bytes(int32_t H, int32_t W, int32_t levels);
 int st_multiband_blend(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels,
                        float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- exposure compensation: overlap gains of the two warped images in front of st_multiband_blend (csrc/exposure.hip; contract in
+ *      README.md, CPU restatement tests/_exposure_ref.py; this project's own contract, unpinned against OpenCV's detail::GainCompensator /
+ *      BlocksGainCompensator).  Operands as st_multiband_blend: img float32 [3,H,W] (clamped to 0..255 and truncated on load), mask float32
+ *      [H,W] (set where > 0.5); block in {8, 16, 32, 64}; the tile grid is Th = ceil(H / block) by Tw = ceil(W / block). ------------------- */
+/* bytes of workspace st_exposure_compensate needs; 0 for a side outside 1..4096 or a block outside the list.                          */
+int st_exposure_workspace_bytes(int32_t H, int32_t W, int32_t block);
+/* the first kernel alone: records int32 [Th,Tw,9] = per tile N, S1[R,G,B,Y], S2[R,G,B,Y] over the overlap.  ST_EINVAL before the launch: a
+ * null pointer, a side outside 1..4096, a block outside the list.                                                                     */
+int st_exposure_stats(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t block,
+                      int32_t* records, void* stream);
+/* the last kernel alone on the caller's tables: float32 [sets,2,Th,Tw], sets = 3 with channels != 0 (R, G, B) else 1, (image 1, image 2),
+ * any Th, Tw in 1..4096 (indices are clamped to the table).  out = min(floor(p g + 0.5), 255), g = the table interpolated bilinearly at
+ * the pixel (tile centres at (t + 0.5) block - 0.5).  out may be its own img (in place).  ST_EINVAL before the launch: a null pointer, a
+ * side or table side outside 1..4096, a block outside the list, an out that overlaps anything but its own img exactly.                */
+int st_exposure_apply(const float* img1, const float* img2, const float* tables, int32_t Th, int32_t Tw, int32_t H, int32_t W, int32_t block,
+                      int32_t channels, float* out1, float* out2, void* stream);
+/* mode 0 "gain": one pair of gains from the global overlap sums; mode 1 "blocks": a pair per tile with the global pair as prior (tiles with
+ * N < min_count keep it), smoothed `smooth` (0..8) times with (0.25, 0.5, 0.25).  channels != 0: R, G, B each get their own gains, else the
+ * integer luma's serve all three.  sigma_n, sigma_g: the weights 1 / sigma^2 of the data and the prior term.  out1, out2 float32 [3,H,W],
+ * integer-valued, every pixel written; gains_out (may be NULL) float32 [sets,2,Th,Tw] ([sets,2,1,1] in mode 0): the tables the apply step
+ * read.  3 (mode 0) or 4 + smooth (mode 1) launches on `stream`, nothing else: no synchronisation, no allocation, the workspace needs no
+ * initialisation and may be reused by the next call on the same stream.  ST_EINVAL before any launch: a null pointer (but gains_out), a side
+ * outside 1..4096, a block outside the list, a mode outside 0..1, smooth outside 0..8, a negative min_count, a sigma that is not positive and
+ * finite (or whose 1 / sigma^2 is not), a workspace smaller than st_exposure_workspace_bytes or not 16-byte aligned, an out that overlaps
+ * anything but its own img exactly.                                                                                                   */
+int st_exposure_compensate(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t mode,
+                           int32_t block, int32_t channels, int32_t min_count, int32_t smooth, double sigma_n, double sigma_g, float* out1,
+                           float* out2, float* gains_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libstitch_gfx950.so")
 HEADER = os.path.join(HERE, "..", "include", "stitch_gfx950.h")
 
-_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "int": C.c_int}
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "int": C.c_int}
 
 
 class GemmDesc(C.Structure):

@@ -1412,3 +1412,94 @@ def multiband_blend(img1, img2, mask1, mask2, levels=5, workspace=None):
     check(lib.st_multiband_blend(_pc(img1), _pc(img2), _pc(mask1), _pc(mask2), H, W, int(levels), _p(out), _p(workspace),
                                  workspace.numel() * workspace.element_size(), _stream()), "st_multiband_blend")
     return out
+
+
+# ---- exposure compensation: overlap gains in front of multiband_blend (csrc/exposure.hip; README.md, exposure compensation) ---------
+EXPOSURE_BLOCKS = (8, 16, 32, 64)
+EXPOSURE_MODES = dict(gain=0, blocks=1)
+EXPOSURE_MAX_SMOOTH = 8
+
+
+def _exposure_operands(img1, img2, mask1, mask2, block):
+    """the checks of `multiband_blend` on the shared operands; returns H, W and the masks' channel 0 as dense planes"""
+    if img1.dim() != 4 or img1.shape[0] != 1 or img1.shape[1] != 3 or img2.shape != img1.shape:
+        raise ValueError(f"img1, img2 [1,3,H,W] expected, got {tuple(img1.shape)} and {tuple(img2.shape)}")
+    H, W = img1.shape[2:]
+    masks = [m for m in (mask1, mask2) if m is not None]
+    for m in masks:
+        if m.dim() != 4 or m.shape[0] != 1 or m.shape[1] not in (1, 3) or tuple(m.shape[2:]) != (H, W):
+            raise ValueError(f"mask [1,1,{H},{W}] or [1,3,{H},{W}] expected, got {tuple(m.shape)}")
+    for t in [img1, img2] + masks:
+        if t.dtype != torch.float32:
+            raise ValueError(f"float32 tensors expected, got {t.dtype}")
+    if block not in EXPOSURE_BLOCKS:
+        raise ValueError(f"block must be one of {EXPOSURE_BLOCKS}, got {block}")
+    if not (1 <= H <= MULTIBAND_MAX_SIDE and 1 <= W <= MULTIBAND_MAX_SIDE):
+        raise ValueError(f"sides must be in 1..{MULTIBAND_MAX_SIDE}, got {H} x {W}")
+    return H, W, [m[:, :1].contiguous() for m in masks]         # channel 0 (no copy unless the mask is a strided view)
+
+
+def exposure_workspace_bytes(H, W, block=32):
+    """bytes of workspace `exposure_compensate` needs for an H x W canvas; 0 for a shape or block outside the contract"""
+    return int(lib.st_exposure_workspace_bytes(int(H), int(W), int(block)))
+
+
+def exposure_stats(img1, img2, mask1, mask2, block=32):
+    """The tile statistics of `exposure_compensate` alone: int32 [Th,Tw,9] = per `block` x `block` tile N, S1[R,G,B,Y], S2[R,G,B,Y] over
+    the overlap (mask1 > 0.5 and mask2 > 0.5) of the truncated pixels; Y = (19595 R + 38470 G + 7471 B + 0x8000) >> 16."""
+    H, W, (k1, k2) = _exposure_operands(img1, img2, mask1, mask2, block)
+    rec = torch.empty((-(-H // block), -(-W // block), 9), dtype=torch.int32, device=img1.device)
+    check(lib.st_exposure_stats(_pc(img1), _pc(img2), _pc(k1), _pc(k2), H, W, int(block), _p(rec), _stream()), "st_exposure_stats")
+    return rec
+
+
+def exposure_apply(img1, img2, tables, block=32, channels=False, out=None):
+    """The apply step of `exposure_compensate` alone on caller-given gain tables: fp32 [1,2,Th,Tw] (``channels=False``) or [3,2,Th,Tw]
+    (R, G, B), second axis = (image 1, image 2), any Th, Tw >= 1 (indices are clamped to the table) -> (out1, out2), fp32 [1,3,H,W],
+    min(floor(p g + 0.5), 255) with g interpolated bilinearly between the tile centres.  ``out``: a pair of tensors to write (each may be
+    its own input: in place)."""
+    H, W, _ = _exposure_operands(img1, img2, None, None, block)
+    sets = 3 if channels else 1
+    if tables.dim() != 4 or tables.shape[0] != sets or tables.shape[1] != 2 or tables.dtype != torch.float32:
+        raise ValueError(f"tables float32 [{sets},2,Th,Tw] expected, got {tables.dtype} {tuple(tables.shape)}")
+    out1, out2 = out if out is not None else (torch.empty_like(img1, memory_format=torch.contiguous_format),
+                                              torch.empty_like(img2, memory_format=torch.contiguous_format))
+    check(lib.st_exposure_apply(_pc(img1), _pc(img2), _pc(tables), tables.shape[2], tables.shape[3], H, W, int(block), int(bool(channels)),
+                                _pc(out1), _pc(out2), _stream()), "st_exposure_apply")
+    return out1, out2
+
+
+def exposure_compensate(img1, img2, mask1, mask2, mode="gain", block=32, channels=False, min_count=None, smooth=2, sigma_n=10.0, sigma_g=0.1,
+                        workspace=None, return_gains=False, out=None):
+    """Gain compensation of two warped images from their overlap (README.md, exposure compensation), for the operands of
+    `multiband_blend`: img1, img2 fp32 [1,3,H,W] (clamped to 0..255 and truncated, as the saver does), mask1, mask2 fp32 [1,1,H,W] or
+    [1,3,H,W] (channel 0 > 0.5) -> (out1, out2), fp32 [1,3,H,W], integer-valued, every pixel written.  ``mode``: "gain" = one pair of gains
+    from the global overlap sums, "blocks" = a pair per ``block`` x ``block`` tile with the global pair as prior (tiles with fewer than
+    ``min_count`` overlap pixels, default block^2 / 8, keep it), smoothed ``smooth`` times.  ``channels``: gains per R, G, B instead of
+    one from the integer luma.  ``return_gains``: also the tables the apply step read, fp32 [sets,2,Th,Tw] ([sets,2,1,1] in "gain").
+    ``workspace``: a uint8 device tensor of at least `exposure_workspace_bytes` bytes, 16-byte aligned (default: allocated here);
+    ``out``: a pair of tensors to write (each may be its own input).  All launches go to the current stream and nothing is read back."""
+    H, W, (k1, k2) = _exposure_operands(img1, img2, mask1, mask2, block)
+    if mode not in EXPOSURE_MODES:
+        raise ValueError(f"mode must be one of {tuple(EXPOSURE_MODES)}, got {mode!r}")
+    if not 0 <= smooth <= EXPOSURE_MAX_SMOOTH:
+        raise ValueError(f"smooth must be in 0..{EXPOSURE_MAX_SMOOTH}, got {smooth}")
+    if min_count is None:
+        min_count = block * block // 8
+    if min_count < 0:
+        raise ValueError(f"min_count must not be negative, got {min_count}")
+    for name, v in (("sigma_n", sigma_n), ("sigma_g", sigma_g)):
+        if not (v > 0 and v < float("inf")):
+            raise ValueError(f"{name} must be positive and finite, got {v}")
+    need = exposure_workspace_bytes(H, W, block)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=img1.device)
+    out1, out2 = out if out is not None else (torch.empty_like(img1, memory_format=torch.contiguous_format),
+                                              torch.empty_like(img2, memory_format=torch.contiguous_format))
+    sets = 3 if channels else 1
+    th, tw = (-(-H // block), -(-W // block)) if mode == "blocks" else (1, 1)
+    gains = torch.empty((sets, 2, th, tw), dtype=torch.float32, device=img1.device) if return_gains else None
+    check(lib.st_exposure_compensate(_pc(img1), _pc(img2), _pc(k1), _pc(k2), H, W, EXPOSURE_MODES[mode], int(block), int(bool(channels)), int(min_count),
+                                     int(smooth), float(sigma_n), float(sigma_g), _pc(out1), _pc(out2), _p(gains), _p(workspace),
+                                     workspace.numel() * workspace.element_size(), _stream()), "st_exposure_compensate")
+    return (out1, out2, gains) if return_gains else (out1, out2)
