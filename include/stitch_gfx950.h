@@ -810,6 +810,33 @@ int st_exposure_compensate(const float* img1, const float* img2, const float* ma
                            int32_t block, int32_t channels, int32_t min_count, int32_t smooth, double sigma_n, double sigma_g, float* out1,
                            float* out2, float* gains_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- seam_dp: a minimum-difference seam through the overlap, between st_exposure_compensate and the blend (csrc/seam.hip; contract in
+ *      README.md, seam_dp; CPU restatement tests/_seam_ref.py; this project's own contract, unpinned against OpenCV's detail::DpSeamFinder /
+ *      GraphCutSeamFinder).  Operands as st_multiband_blend.  All integers: p = trunc(clamp(x, 0, 255)), m = mask > 0.5, O = m1 and m2,
+ *      E1 / E2 = the exclusive regions.  Cost e int32: in O 1 + sum_c |p1 - p2|, outside m1 or m2 1, in E1 or E2 2^18.  orientation: 0 auto,
+ *      1 vertical (lines are rows, one column per row), 2 horizontal (lines are columns); first: 0 auto, 1 or 2 = the image that owns the
+ *      low-coordinate side.  Auto, from N_i = |E_i| and the coordinate sums Sx_i, Sy_i: A = Sx1 N2 - Sx2 N1, B = Sy1 N2 - Sy2 N1; vertical iff
+ *      |A| >= |B|; first = 1 iff (vertical ? A : B) <= 0.  M(0, k) = e, M(l, k) = e + min over the predecessors k, k - 1, k + 1 inside the
+ *      line, in that order with strict <; the path ends at the lowest index among the minima of the last line.  ------------------------- */
+/* bytes of workspace st_seam_dp needs; 0 for a side outside 1..4096.                                                                  */
+int st_seam_workspace_bytes(int32_t H, int32_t W);
+/* the cost plane alone, int32 [H,W] (canvas layout).  ST_EINVAL before the launch: a null pointer, a side outside 1..4096.            */
+int st_seam_cost(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t* cost, void* stream);
+/* side_out uint8 [H,W]: 1 iff (position <= s[line]) == (first == 1), for every canvas pixel; all ones when info[0] == 0.  path_out (may be
+ * NULL) int32 [max(H,W)]: s[l] for the lines of the decided orientation, -1 behind them.  info_out int32 [4]: valid, orientation (1 / 2),
+ * first (1 / 2), path cost; valid = 0 when O is empty, or when an argument is auto and E1 or E2 is empty (orientation, first, the path and
+ * its cost are reported all the same).  6 launches on `stream` whose grids depend on H and W alone, nothing else: no synchronisation, no
+ * allocation, no atomics; the workspace needs no initialisation and may be reused by the next call on the same stream.  ST_EINVAL before any
+ * launch: a null pointer (but path_out), a side outside 1..4096, orientation or first outside 0..2, a workspace smaller than
+ * st_seam_workspace_bytes or not 16-byte aligned.                                                                                     */
+int st_seam_dp(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t orientation,
+               int32_t first, uint8_t* side_out, int32_t* path_out, int32_t* info_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* st_multiband_blend with the ownership of the overlap taken from a seam: W1 = m1 and (not m2 or side) where info[0] != 0, else the distance
+ * rule, decided on the device.  side uint8 [H,W], info int32 [4] as st_seam_dp wrote them (device pointers).  Everything else, the
+ * workspace (st_multiband_workspace_bytes) and the rejections as st_multiband_blend; a null side or info is rejected too.             */
+int st_multiband_blend_seam(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels,
+                            const uint8_t* side, const int32_t* info, float* out, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,8 @@ select `cv_inpainter`, the reference's OpenCV Telea inpainter restated as GPU ke
 fills them; with the shipped `tps_method="opencv"` the spline is this package's own pixel-unit TPS (OpenCV is not
 installable here: unpinned against OpenCV).  `--multiband_fusion` adds an eleventh file of this package's own, `multiband_fusion.jpg`: the two
 warped images blended over a Laplacian pyramid along their distance-transform seam (README.md, multiband_fusion); `--exposure_compensation
-{gain,blocks}` equalises the two images' brightness from their overlap in front of that blend (README.md, exposure compensation)."""
+{gain,blocks}` equalises the two images' brightness from their overlap in front of that blend (README.md, exposure compensation); `--seam dp`
+moves the blend's seam from the distance transforms' to a minimum-difference path through the overlap (README.md, seam_dp)."""
 from __future__ import annotations
 
 import argparse
@@ -58,6 +59,8 @@ def get_config(argv=None):
     p.add_argument("--exposure_compensation", choices=("gain", "blocks"), default=None,
                    help="with --multiband_fusion: gain-compensate the two warped images from their overlap before the blend (one pair of gains, or one per tile)")
     p.add_argument("--exposure_block", type=int, default=None, metavar="N", help="tile side of --exposure_compensation (8, 16, 32 or 64; default 32)")
+    p.add_argument("--seam", choices=("dp",), default=None,
+                   help="with --multiband_fusion: blend along a minimum-difference seam through the overlap (dynamic programming, GPU) instead of the distance-transform seam")
     p.add_argument("--gpu_decode", action="store_true",
                    help="decode the input JPEGs on the GPU (Pillow's pixels, bit for bit); files outside the decoder's contract keep Pillow")
     p.add_argument("--dry-run", dest="dry_run", action="store_true",
@@ -65,6 +68,8 @@ def get_config(argv=None):
     args = p.parse_args(argv)
     if args.exposure_compensation is not None and not args.multiband_fusion:
         p.error("--exposure_compensation applies to the operands of --multiband_fusion: give that switch too")
+    if args.seam is not None and not args.multiband_fusion:
+        p.error("--seam decides the ownership of --multiband_fusion: give that switch too")
     if args.exposure_block is not None and args.exposure_compensation is None:
         p.error("--exposure_block needs --exposure_compensation")
     if args.exposure_block is not None and args.exposure_block not in (8, 16, 32, 64):
@@ -74,7 +79,7 @@ def get_config(argv=None):
     for k, v in vars(args).items():
         if k in ("restore_ckpt", "gpu_jpeg", "gpu_decode", "jpeg_optimize", "multiband_fusion") and not v:         # (a switch that is off: config.txt stays what it was before the switch existed)
             continue
-        if k in ("jpeg_quality", "jpeg_subsampling", "jpeg_restart_blocks", "jpeg_restart_rows", "multiband_levels", "exposure_compensation", "exposure_block") and v is None:
+        if k in ("jpeg_quality", "jpeg_subsampling", "jpeg_restart_blocks", "jpeg_restart_rows", "multiband_levels", "exposure_compensation", "exposure_block", "seam") and v is None:
             continue
         cfg[k] = v
     cfg.TPS_PIPELINE_CONFIG = tps
@@ -195,6 +200,11 @@ def exposure_of(cfg):
     return mode, 32 if block is None else int(block)
 
 
+def seam_of(cfg):
+    """The `seam` argument the flag --seam asks for: None without it, else "dp"."""
+    return getattr(cfg, "seam", None)
+
+
 class _Saver:
     """JPEG writes of out.py:260-312.  The uint8 conversion runs on the GPU (clip + truncation, as `to_pillow_fn` does on the
     host), the bytes are copied to the host in the caller's thread, the JPEG encode + file write go to ``pool`` when one is given
@@ -287,7 +297,7 @@ def load_inpainter(name):
 
 
 def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_model=None, inpainter=None, forward=None, saver=None,
-                       gpu_jpeg=False, gpu_decode=False, jpeg_params=None, multiband=None, exposure=None):
+                       gpu_jpeg=False, gpu_decode=False, jpeg_params=None, multiband=None, exposure=None, seam=None):
     """out.py:158-312: forward (`test_out`), TPS post-pipeline with the configured `mix_fn`, saves, composition.  The inpainter
     is the caller's, else the pass-through stand-in (`load_inpainter`: `transref_inpainter` needs its checkpoint, the diffusion one is
     out of scope): with the stand-in, in `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the
@@ -303,9 +313,15 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     `output2` blended by `ops.multiband_blend` under `mask1` / `mask2`, as they go to the saver (README.md, multiband_fusion); the blend is
     returned as `multiband_image`.  This file is the package's own, not one of the reference's.
     ``exposure``: None, or (mode, block) of `ops.exposure_compensate`, applied to the two operands of that blend and to nothing else (needs
-    ``multiband``); the compensated pair is returned as `compensated1` / `compensated2`."""
+    ``multiband``); the compensated pair is returned as `compensated1` / `compensated2`.
+    ``seam``: None, or "dp": `ops.seam_dp` on the operands of that blend (the compensated pair when there is one) decides the ownership of the
+    overlap (needs ``multiband``); its planes are returned as `seam_side` / `seam_info`."""
     if exposure is not None and multiband is None:
         raise ValueError("exposure compensation applies to the operands of the multiband blend: multiband must be given")
+    if seam not in (None, "dp"):
+        raise ValueError(f'seam must be None or "dp", got {seam!r}')
+    if seam is not None and multiband is None:
+        raise ValueError("the seam decides the ownership of the multiband blend: multiband must be given")
     own_saver = saver is None
     statuses = []
     saver = saver or _Saver(gpu_jpeg=gpu_jpeg, jpeg_params=jpeg_params)
@@ -357,7 +373,11 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
         if exposure is not None:
             img1, img2 = stitch_amd.ops.exposure_compensate(img1, img2, k1, k2, mode=exposure[0], block=exposure[1])
             out = dict(out, compensated1=img1, compensated2=img2)
-        out = dict(out, multiband_image=stitch_amd.ops.multiband_blend(img1, img2, k1, k2, levels=multiband))
+        pair = None
+        if seam is not None:
+            pair = stitch_amd.ops.seam_dp(img1, img2, k1, k2)
+            out = dict(out, seam_side=pair[0], seam_info=pair[1])
+        out = dict(out, multiband_image=stitch_amd.ops.multiband_blend(img1, img2, k1, k2, levels=multiband, seam=pair))
         saver.image(out["multiband_image"], result_path + "multiband_fusion.jpg")
     if composition_model is not None:
         # out.py:277-312: learned seam masks + composed image from the UDIS2 composition network
@@ -375,7 +395,7 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
 
 
 def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=None, on_done=None, depth=2, gpu_jpeg=False, gpu_decode=False,
-              jpeg_params=None, multiband=None, exposure=None):
+              jpeg_params=None, multiband=None, exposure=None, seam=None):
     """The inference loop of out.py:351-357 as a software pipeline, `depth` pairs in flight.  While pair i is finished on the host
     (canvas bounds read back, canvas kernels, TPS post-pipeline with its control-point round trips, composition, device->host copies
     of the images), the network parts of pairs i + 1 .. i + depth - 1 -- both nets at 512x512, ~1 000 launches each, replayed from a
@@ -391,7 +411,8 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
     (`ops.jpeg_decode`) in front of its graph launch; the status words are checked when the pair is finished.
     ``jpeg_params``: Pillow's `save` keywords for the result files (`_Saver`), on either encoder.
     ``multiband``: the pyramid levels of `multiband_fusion.jpg` (`inference_one_data`), blended on the pair's stream; None: not written.
-    ``exposure``: (mode, block) of the gain compensation in front of that blend (`inference_one_data`); None: none."""
+    ``exposure``: (mode, block) of the gain compensation in front of that blend (`inference_one_data`); None: none.
+    ``seam``: "dp" for that blend along the minimum-difference seam (`inference_one_data`); None: the distance seam."""
     from concurrent.futures import ThreadPoolExecutor
     if not todo:
         return []
@@ -427,7 +448,7 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
             g, handle, st, statuses = inflight.pop(0)
             with torch.cuda.stream(st):
                 out, rp = inference_one_data(cfg, dd, save_root, model, composition_model, inpainter,
-                                             forward=lambda: g.finish(handle), saver=saver, multiband=multiband, exposure=exposure)
+                                             forward=lambda: g.finish(handle), saver=saver, multiband=multiband, exposure=exposure, seam=seam)
                 check_decode(statuses)
             # no host wait here: the graph of this slot is launched again on the SAME stream (pair j + depth), i.e. after everything
             # that reads this pair's static buffers
@@ -493,7 +514,8 @@ def main(argv=None):
             continue
         todo.append(dd)
     run_pairs(cfg, todo, save_root, model, composition_model, inpainter, gpu_jpeg=bool(getattr(cfg, "gpu_jpeg", False)),
-              gpu_decode=bool(getattr(cfg, "gpu_decode", False)), jpeg_params=jpeg_params_of(cfg), multiband=multiband_of(cfg), exposure=exposure_of(cfg))
+              gpu_decode=bool(getattr(cfg, "gpu_decode", False)), jpeg_params=jpeg_params_of(cfg), multiband=multiband_of(cfg), exposure=exposure_of(cfg),
+              seam=seam_of(cfg))
     if world > 1:
         import torch.distributed as tdist
         tdist.barrier()

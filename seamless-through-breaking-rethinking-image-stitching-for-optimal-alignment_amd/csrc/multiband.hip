@@ -171,18 +171,20 @@ __global__ void __launch_bounds__(256) mb_masks_kernel(const float* __restrict__
 }
 
 // level 0 of the three pyramids: planes 0-2 I1f, 3-5 I2f, 6 W.  q = the pixel itself inside U, else the nearest pixel of U (`nearest`,
-// -1 when U is empty: everything 0).  W1(q) = m1 and (not m2 or D1 >= D2); C = the owner's pixel at q.
+// -1 when U is empty: everything 0).  W1(q) = m1 and (not m2 or D1 >= D2); C = the owner's pixel at q.  With a seam (`side` != NULL and
+// info[0] != 0, read here: no host decision) the overlap follows it instead: W1(q) = m1 and (not m2 or side).
 __global__ void __launch_bounds__(256) mb_fields_kernel(const float* __restrict__ img1, const float* __restrict__ img2, const uint8_t* __restrict__ m1,
                                                         const uint8_t* __restrict__ m2, const int32_t* __restrict__ D1, const int32_t* __restrict__ D2,
-                                                        const int32_t* __restrict__ nearest, float* __restrict__ G, int n) {
+                                                        const int32_t* __restrict__ nearest, const uint8_t* __restrict__ side, const int32_t* __restrict__ info,
+                                                        float* __restrict__ G, int n) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
-    const bool a = m1[p], b = m2[p];
+    const bool a = m1[p], b = m2[p], seam = side && info[0] != 0;
     const int q = (a || b) ? p : nearest[p];
     bool w1 = false;
     float c[3] = {0.f, 0.f, 0.f};
     if (q >= 0) {
-        w1 = m1[q] && (!m2[q] || D1[q] >= D2[q]);
+        w1 = m1[q] && (!m2[q] || (seam ? side[q] != 0 : D1[q] >= D2[q]));
         const float* src = w1 ? img1 : img2;
         for (int ch = 0; ch < 3; ++ch) c[ch] = st_u8_trunc(src[(size_t)ch * n + q]);
     }
@@ -287,8 +289,9 @@ extern "C" int st_multiband_workspace_bytes(int32_t H, int32_t W, int32_t levels
     return mb_plan(H, W, levels, L) ? (int)L.total : 0;
 }
 
-extern "C" int st_multiband_blend(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels,
-                                  float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+// side, info: the seam of st_seam_dp, or both NULL (the distance seam)
+static int mb_blend(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels, const uint8_t* side,
+                    const int32_t* info, float* out, void* workspace, int64_t workspace_bytes, void* stream) {
     mb_layout L;
     if (!img1 || !img2 || !mask1 || !mask2 || !out || !workspace || !mb_plan(H, W, levels, L)) return ST_EINVAL;
     if (workspace_bytes < L.total || ((uintptr_t)workspace & 15)) return ST_EINVAL;
@@ -303,7 +306,7 @@ extern "C" int st_multiband_blend(const float* img1, const float* img2, const fl
     if ((rc = edt_launch(m1, H, W, 1, D1, nullptr, s)) != ST_OK) return rc;
     if ((rc = edt_launch(m2, H, W, 1, D2, nullptr, s)) != ST_OK) return rc;
     if ((rc = edt_launch(notu, H, W, 0, DN, nearest, s)) != ST_OK) return rc;
-    mb_fields_kernel<<<blocks, 256, 0, s>>>(img1, img2, m1, m2, D1, D2, nearest, (float*)(ws + L.G[0]), n);
+    mb_fields_kernel<<<blocks, 256, 0, s>>>(img1, img2, m1, m2, D1, D2, nearest, side, info, (float*)(ws + L.G[0]), n);
     ST_CHECK_LAUNCH();
     for (int l = 0; l < L.Le; ++l) {
         const int no = L.h[l + 1] * L.w[l + 1];
@@ -322,4 +325,15 @@ extern "C" int st_multiband_blend(const float* img1, const float* img2, const fl
         ST_CHECK_LAUNCH();
     }
     return ST_OK;
+}
+
+extern "C" int st_multiband_blend(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels,
+                                  float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+    return mb_blend(img1, img2, mask1, mask2, H, W, levels, nullptr, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int st_multiband_blend_seam(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels,
+                                       const uint8_t* side, const int32_t* info, float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!side || !info) return ST_EINVAL;
+    return mb_blend(img1, img2, mask1, mask2, H, W, levels, side, info, out, workspace, workspace_bytes, stream);
 }

@@ -1387,15 +1387,20 @@ def multiband_workspace_bytes(H, W, levels):
     return int(lib.st_multiband_workspace_bytes(int(H), int(W), int(levels)))
 
 
-def multiband_blend(img1, img2, mask1, mask2, levels=5, workspace=None):
+def multiband_blend(img1, img2, mask1, mask2, levels=5, workspace=None, seam=None):
     """Multi-band (Laplacian pyramid) blend of two warped images along the distance-transform seam of their masks (README.md,
     multiband_fusion): img1, img2 fp32 [1,3,H,W] (clamped to 0..255 and truncated, as the saver does), mask1, mask2 fp32 [1,1,H,W] or
     [1,3,H,W] (channel 0 > 0.5) -> fp32 [1,3,H,W], 0 outside the union.  ``levels`` = REDUCE steps (0 = hard seam).  ``workspace``: a
     uint8 device tensor of at least `multiband_workspace_bytes` bytes, 16-byte aligned (default: allocated here); all launches go to the
-    current stream and nothing is read back."""
+    current stream and nothing is read back.  ``seam``: the (side, info) pair of `seam_dp` on the same canvas: where info says the seam is
+    valid, the overlap belongs to image 1 where side is set, instead of where image 1's border is the farther one (decided on the device)."""
     if img1.dim() != 4 or img1.shape[0] != 1 or img1.shape[1] != 3 or img2.shape != img1.shape:
         raise ValueError(f"img1, img2 [1,3,H,W] expected, got {tuple(img1.shape)} and {tuple(img2.shape)}")
     H, W = img1.shape[2:]
+    if seam is not None:
+        side, info = seam
+        if side.dtype != torch.uint8 or tuple(side.shape) != (H, W) or info.dtype != torch.int32 or tuple(info.shape) != (4,):
+            raise ValueError(f"seam = (side uint8 [{H},{W}], info int32 [4]) expected, got {side.dtype} {tuple(side.shape)}, {info.dtype} {tuple(info.shape)}")
     for m in (mask1, mask2):
         if m.dim() != 4 or m.shape[0] != 1 or m.shape[1] not in (1, 3) or tuple(m.shape[2:]) != (H, W):
             raise ValueError(f"mask [1,1,{H},{W}] or [1,3,{H},{W}] expected, got {tuple(m.shape)}")
@@ -1409,6 +1414,10 @@ def multiband_blend(img1, img2, mask1, mask2, levels=5, workspace=None):
         workspace = torch.empty(need, dtype=torch.uint8, device=img1.device)
     out = torch.empty_like(img1, memory_format=torch.contiguous_format)
     mask1, mask2 = mask1[:, :1].contiguous(), mask2[:, :1].contiguous()         # channel 0 (no copy unless the mask is a strided view)
+    if seam is not None:
+        check(lib.st_multiband_blend_seam(_pc(img1), _pc(img2), _pc(mask1), _pc(mask2), H, W, int(levels), _pc(seam[0]), _pc(seam[1]), _p(out),
+                                          _p(workspace), workspace.numel() * workspace.element_size(), _stream()), "st_multiband_blend_seam")
+        return out
     check(lib.st_multiband_blend(_pc(img1), _pc(img2), _pc(mask1), _pc(mask2), H, W, int(levels), _p(out), _p(workspace),
                                  workspace.numel() * workspace.element_size(), _stream()), "st_multiband_blend")
     return out
@@ -1503,3 +1512,61 @@ def exposure_compensate(img1, img2, mask1, mask2, mode="gain", block=32, channel
                                      int(smooth), float(sigma_n), float(sigma_g), _pc(out1), _pc(out2), _p(gains), _p(workspace),
                                      workspace.numel() * workspace.element_size(), _stream()), "st_exposure_compensate")
     return (out1, out2, gains) if return_gains else (out1, out2)
+
+
+# ---- seam_dp: a minimum-difference seam for the ownership of multiband_blend (csrc/seam.hip; README.md, seam_dp) ---------------------
+SEAM_ORIENTATIONS = dict(auto=0, vertical=1, horizontal=2)
+SEAM_FIRST = {"auto": 0, 1: 1, 2: 2}
+
+
+def _seam_operands(img1, img2, mask1, mask2):
+    """the checks of `multiband_blend` on the shared operands; returns H, W and the masks' channel 0 as dense planes"""
+    if img1.dim() != 4 or img1.shape[0] != 1 or img1.shape[1] != 3 or img2.shape != img1.shape:
+        raise ValueError(f"img1, img2 [1,3,H,W] expected, got {tuple(img1.shape)} and {tuple(img2.shape)}")
+    H, W = img1.shape[2:]
+    for m in (mask1, mask2):
+        if m.dim() != 4 or m.shape[0] != 1 or m.shape[1] not in (1, 3) or tuple(m.shape[2:]) != (H, W):
+            raise ValueError(f"mask [1,1,{H},{W}] or [1,3,{H},{W}] expected, got {tuple(m.shape)}")
+    for t in (img1, img2, mask1, mask2):
+        if t.dtype != torch.float32:
+            raise ValueError(f"float32 tensors expected, got {t.dtype}")
+    if not (1 <= H <= MULTIBAND_MAX_SIDE and 1 <= W <= MULTIBAND_MAX_SIDE):
+        raise ValueError(f"sides must be in 1..{MULTIBAND_MAX_SIDE}, got {H} x {W}")
+    return H, W, mask1[:, :1].contiguous(), mask2[:, :1].contiguous()         # channel 0 (no copy unless the mask is a strided view)
+
+
+def seam_workspace_bytes(H, W):
+    """bytes of workspace `seam_dp` needs for an H x W canvas; 0 for a shape outside the contract"""
+    return int(lib.st_seam_workspace_bytes(int(H), int(W)))
+
+
+def seam_cost(img1, img2, mask1, mask2):
+    """The cost plane of `seam_dp` alone, int32 [H,W]: 1 + sum over R, G, B of |p1 - p2| of the truncated pixels inside the overlap, 1
+    outside both masks, 2^18 where exactly one mask is set."""
+    H, W, k1, k2 = _seam_operands(img1, img2, mask1, mask2)
+    cost = torch.empty((H, W), dtype=torch.int32, device=img1.device)
+    check(lib.st_seam_cost(_pc(img1), _pc(img2), _pc(k1), _pc(k2), H, W, _p(cost), _stream()), "st_seam_cost")
+    return cost
+
+
+def seam_dp(img1, img2, mask1, mask2, orientation="auto", first="auto", workspace=None, return_path=False):
+    """A minimum-cost monotone seam through the overlap of two warped images (README.md, seam_dp), on the operands of `multiband_blend`
+    -> (side, info[, path]).  side uint8 [H,W]: 1 where the pixel lies on image 1's side of the seam (every canvas pixel; all ones
+    without a valid seam).  info int32 [4] on the device: valid, orientation (1 vertical: one column per row; 2 horizontal), first (the
+    image that owns the low-coordinate side), path cost.  ``orientation`` "auto" / "vertical" / "horizontal" and ``first`` "auto" / 1 / 2:
+    auto decides from the centroids of the two exclusive regions.  ``return_path``: also int32 [max(H,W)], the seam position per line, -1
+    behind the last line.  ``workspace``: a uint8 device tensor of at least `seam_workspace_bytes` bytes, 16-byte aligned (default:
+    allocated here).  All launches go to the current stream and nothing is read back; (side, info) is what `multiband_blend(seam=...)` takes."""
+    H, W, k1, k2 = _seam_operands(img1, img2, mask1, mask2)
+    if orientation not in SEAM_ORIENTATIONS:
+        raise ValueError(f"orientation must be one of {tuple(SEAM_ORIENTATIONS)}, got {orientation!r}")
+    if first not in SEAM_FIRST:
+        raise ValueError(f"first must be one of {tuple(SEAM_FIRST)}, got {first!r}")
+    if workspace is None:
+        workspace = torch.empty(seam_workspace_bytes(H, W), dtype=torch.uint8, device=img1.device)
+    side = torch.empty((H, W), dtype=torch.uint8, device=img1.device)
+    info = torch.empty(4, dtype=torch.int32, device=img1.device)
+    path = torch.empty(max(H, W), dtype=torch.int32, device=img1.device) if return_path else None
+    check(lib.st_seam_dp(_pc(img1), _pc(img2), _pc(k1), _pc(k2), H, W, SEAM_ORIENTATIONS[orientation], SEAM_FIRST[first], _p(side), _p(path), _p(info),
+                         _p(workspace), workspace.numel() * workspace.element_size(), _stream()), "st_seam_dp")
+    return (side, info, path) if return_path else (side, info)
