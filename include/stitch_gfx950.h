@@ -765,10 +765,18 @@ int st_tr_to_u8(const float* x, uint8_t* out, int64_t n, void* stream);
 
 /* ---- multiband_fusion: Laplacian-pyramid seam blend of the two warped images (csrc/multiband.hip; contract in README.md, CPU restatement
  *      tests/_multiband_ref.py; this project's own contract, unpinned against OpenCV's detail::MultiBandBlender) -------------------------- */
+/* Non-finite and out-of-range values, for every entry of the blend stage (st_multiband_*, st_exposure_*, st_seam_*): a pixel is read as
+ * min(max(trunc(x), 0), 255), which takes NaN -> 0, -Inf -> 0, +Inf -> 255 and truncates any finite value toward zero and clamps it (-0.5
+ * and -0.0 -> 0, 255.999 -> 255, +-1e30 -> 255 / 0).  A mask value is set iff > 0.5: NaN, -Inf and 0.5 are unset, +Inf is set.  So a call
+ * with a non-finite pixel or mask value gives the bits of the same call with that value replaced by its rule value, and every output is
+ * finite everywhere (st_exposure_apply: for finite tables).
+ * Aliasing: inputs may overlap each other freely (they are only read).  Whatever else may overlap is said at each entry; everything that
+ * is not allowed there is rejected with ST_EINVAL before any launch, each operand taken at its full byte length.                        */
 /* exact squared Euclidean distance transform: mask uint8 [H,W], sites = the pixels with mask == 0 and, with border_is_site != 0, the
  * one-pixel ring round the canvas.  D int32 [H,W] = squared distance to the nearest site (INT32_MAX when there is none); index (may be
  * NULL) int32 [H,W] = the lowest row-major index among the canvas sites at that distance, -1 when there is none or only the ring is that
- * near.  D doubles as the scratch of the column pass.  ST_EINVAL before any launch: mask or D null, a side outside 1..4096.  Two launches. */
+ * near.  D doubles as the scratch of the column pass.  mask, D and index must not overlap one another.  ST_EINVAL before any launch: mask
+ * or D null, a side outside 1..4096, an overlap.  Two launches.                                                                       */
 int st_edt_sq_u8(const uint8_t* mask, int32_t H, int32_t W, int32_t border_is_site, int32_t* D, int32_t* index, void* stream);
 /* bytes of workspace st_multiband_blend needs; 0 for a side outside 1..4096 or levels outside 0..16.                                 */
 int st_multiband_workspace_bytes(int32_t H, int32_t W, int32_t levels);
@@ -777,7 +785,9 @@ int st_multiband_workspace_bytes(int32_t H, int32_t W, int32_t levels);
  * [3,H,W], 0 outside the union of the masks.  9 + 2 x (effective levels) launches on `stream`, nothing else: no synchronisation, no
  * allocation, the workspace needs no initialisation and may be reused by the next call on the same stream.  ST_EINVAL before any
  * launch: a null pointer, a side outside 1..4096, levels outside 0..16, a workspace smaller than st_multiband_workspace_bytes or not
- * 16-byte aligned.                                                                                                                  */
+ * 16-byte aligned, a forbidden overlap.  out may be img1 or img2 exactly (only the last launch writes out, and it reads the workspace
+ * alone); it must not overlap an image in any other way (a shifted view), a mask, or (st_multiband_blend_seam) side or info.  The
+ * workspace (its first st_multiband_workspace_bytes bytes) must not overlap any operand.                                             */
 int st_multiband_blend(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels,
                        float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
@@ -794,7 +804,8 @@ int st_exposure_stats(const float* img1, const float* img2, const float* mask1, 
 /* the last kernel alone on the caller's tables: float32 [sets,2,Th,Tw], sets = 3 with channels != 0 (R, G, B) else 1, (image 1, image 2),
  * any Th, Tw in 1..4096 (indices are clamped to the table).  out = min(floor(p g + 0.5), 255), g = the table interpolated bilinearly at
  * the pixel (tile centres at (t + 0.5) block - 0.5).  out may be its own img (in place).  ST_EINVAL before the launch: a null pointer, a
- * side or table side outside 1..4096, a block outside the list, an out that overlaps anything but its own img exactly.                */
+ * side or table side outside 1..4096, a block outside the list, an out that overlaps anything but its own img exactly -- the other
+ * image, the other out, or the tables (the [sets,2,Th,Tw] floats the call reads).                                                     */
 int st_exposure_apply(const float* img1, const float* img2, const float* tables, int32_t Th, int32_t Tw, int32_t H, int32_t W, int32_t block,
                       int32_t channels, float* out1, float* out2, void* stream);
 /* mode 0 "gain": one pair of gains from the global overlap sums; mode 1 "blocks": a pair per tile with the global pair as prior (tiles with
@@ -805,7 +816,9 @@ int st_exposure_apply(const float* img1, const float* img2, const float* tables,
  * initialisation and may be reused by the next call on the same stream.  ST_EINVAL before any launch: a null pointer (but gains_out), a side
  * outside 1..4096, a block outside the list, a mode outside 0..1, smooth outside 0..8, a negative min_count, a sigma that is not positive and
  * finite (or whose 1 / sigma^2 is not), a workspace smaller than st_exposure_workspace_bytes or not 16-byte aligned, an out that overlaps
- * anything but its own img exactly.                                                                                                   */
+ * anything but its own img exactly, a gains_out (the [sets,2,Th,Tw] floats the call writes, [sets,2,1,1] in mode 0) that overlaps an
+ * image, a mask, an out or the workspace, a workspace (its first st_exposure_workspace_bytes bytes) that overlaps an image, a mask or an
+ * out.                                                                                                                                */
 int st_exposure_compensate(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t mode,
                            int32_t block, int32_t channels, int32_t min_count, int32_t smooth, double sigma_n, double sigma_g, float* out1,
                            float* out2, float* gains_out, void* workspace, int64_t workspace_bytes, void* stream);
@@ -820,7 +833,8 @@ int st_exposure_compensate(const float* img1, const float* img2, const float* ma
  *      line, in that order with strict <; the path ends at the lowest index among the minima of the last line.  ------------------------- */
 /* bytes of workspace st_seam_dp needs; 0 for a side outside 1..4096.                                                                  */
 int st_seam_workspace_bytes(int32_t H, int32_t W);
-/* the cost plane alone, int32 [H,W] (canvas layout).  ST_EINVAL before the launch: a null pointer, a side outside 1..4096.            */
+/* the cost plane alone, int32 [H,W] (canvas layout); it must not overlap an image or a mask.  ST_EINVAL before the launch: a null
+ * pointer, a side outside 1..4096, such an overlap.                                                                                   */
 int st_seam_cost(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t* cost, void* stream);
 /* side_out uint8 [H,W]: 1 iff (position <= s[line]) == (first == 1), for every canvas pixel; all ones when info[0] == 0.  path_out (may be
  * NULL) int32 [max(H,W)]: s[l] for the lines of the decided orientation, -1 behind them.  info_out int32 [4]: valid, orientation (1 / 2),
@@ -828,7 +842,8 @@ int st_seam_cost(const float* img1, const float* img2, const float* mask1, const
  * its cost are reported all the same).  6 launches on `stream` whose grids depend on H and W alone, nothing else: no synchronisation, no
  * allocation, no atomics; the workspace needs no initialisation and may be reused by the next call on the same stream.  ST_EINVAL before any
  * launch: a null pointer (but path_out), a side outside 1..4096, orientation or first outside 0..2, a workspace smaller than
- * st_seam_workspace_bytes or not 16-byte aligned.                                                                                     */
+ * st_seam_workspace_bytes or not 16-byte aligned, an overlap: no output (side_out, path_out, info_out) may overlap an image, a mask,
+ * another output or the workspace (its first st_seam_workspace_bytes bytes), and no image or mask may lie in the workspace.            */
 int st_seam_dp(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t orientation,
                int32_t first, uint8_t* side_out, int32_t* path_out, int32_t* info_out, void* workspace, int64_t workspace_bytes, void* stream);
 /* st_multiband_blend with the ownership of the overlap taken from a seam: W1 = m1 and (not m2 or side) where info[0] != 0, else the distance

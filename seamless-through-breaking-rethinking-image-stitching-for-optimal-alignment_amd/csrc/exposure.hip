@@ -286,6 +286,12 @@ static bool ec_outputs_ok(const float* img1, const float* img2, const float* mas
     return true;
 }
 
+// the tables, which the apply step reads while it writes, overlap no output (st_exposure_compensate checks its gains_out, written before
+// the images are read, against the inputs and the workspace as well); both at the byte length the call reads or writes, [sets][2][Th][Tw]
+static bool ec_table_ok(const void* table, int64_t bytes, const float* out1, const float* out2, int64_t n) {
+    return !ec_overlap(table, bytes, out1, 12 * n) && !ec_overlap(table, bytes, out2, 12 * n);
+}
+
 static int ec_stats_launch(const float* img1, const float* img2, const float* mask1, const float* mask2, int H, int W, const ec_layout& L, uint32_t* records,
                            hipStream_t s) {
     ec_stats_kernel<<<dim3(L.Tw, L.Th), 256, 0, s>>>(img1, img2, mask1, mask2, records, H, W, L.lb);
@@ -323,6 +329,7 @@ extern "C" int st_exposure_apply(const float* img1, const float* img2, const flo
     if (!img1 || !img2 || !tables || !out1 || !out2 || !ec_plan(H, W, block, L)) return ST_EINVAL;
     if (Th < 1 || Tw < 1 || Th > EC_MAX_SIDE || Tw > EC_MAX_SIDE) return ST_EINVAL;
     if (!ec_outputs_ok(img1, img2, nullptr, nullptr, out1, out2, (int64_t)H * W)) return ST_EINVAL;
+    if (!ec_table_ok(tables, (int64_t)4 * (channels ? 3 : 1) * 2 * Th * Tw, out1, out2, (int64_t)H * W)) return ST_EINVAL;
     return ec_apply_launch(img1, img2, tables, Th, Tw, channels ? 3 : 1, H, W, L.lb, out1, out2, (hipStream_t)stream);
 }
 
@@ -335,6 +342,15 @@ extern "C" int st_exposure_compensate(const float* img1, const float* img2, cons
     if (!(sigma_n > 0.0) || !(sigma_g > 0.0) || __builtin_isinf(sigma_n) || __builtin_isinf(sigma_g)) return ST_EINVAL;
     if (workspace_bytes < L.total || ((uintptr_t)workspace & 15)) return ST_EINVAL;
     if (!ec_outputs_ok(img1, img2, mask1, mask2, out1, out2, (int64_t)H * W)) return ST_EINVAL;
+    {
+        const int64_t n = (int64_t)H * W, img = 12 * n, msk = 4 * n, gb = (int64_t)4 * (channels ? 3 : 1) * 2 * (mode == 1 ? (int64_t)L.Th * L.Tw : 1);
+        const void* ops[6] = {img1, img2, out1, out2, mask1, mask2};
+        for (int i = 0; i < 6; ++i) {
+            if (ec_overlap(workspace, L.total, ops[i], i < 4 ? img : msk)) return ST_EINVAL;
+            if (gains_out && ec_overlap(gains_out, gb, ops[i], i < 4 ? img : msk)) return ST_EINVAL;
+        }
+        if (gains_out && ec_overlap(gains_out, gb, workspace, L.total)) return ST_EINVAL;
+    }
     const double alpha = 1.0 / (sigma_n * sigma_n), beta = 1.0 / (sigma_g * sigma_g);
     if (!(alpha > 0.0) || !(beta > 0.0) || __builtin_isinf(alpha) || __builtin_isinf(beta)) return ST_EINVAL;     // a sigma whose square leaves fp64
     hipStream_t s = (hipStream_t)stream;

@@ -156,8 +156,17 @@ static int edt_launch(const uint8_t* mask, int H, int W, int border, int32_t* D,
     return ST_OK;
 }
 
+static bool mb_overlap(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+}
+
+// D is written while the mask is still being read, and index while D's row is: the three planes are disjoint
 extern "C" int st_edt_sq_u8(const uint8_t* mask, int32_t H, int32_t W, int32_t border_is_site, int32_t* D, int32_t* index, void* stream) {
     if (!mask || !D || H < 1 || W < 1 || H > MB_MAX_SIDE || W > MB_MAX_SIDE) return ST_EINVAL;
+    const int64_t n = (int64_t)H * W;
+    if (mb_overlap(D, 4 * n, mask, n)) return ST_EINVAL;
+    if (index && (mb_overlap(index, 4 * n, mask, n) || mb_overlap(index, 4 * n, D, 4 * n))) return ST_EINVAL;
     return edt_launch(mask, H, W, border_is_site != 0, D, index, (hipStream_t)stream);
 }
 
@@ -289,12 +298,30 @@ extern "C" int st_multiband_workspace_bytes(int32_t H, int32_t W, int32_t levels
     return mb_plan(H, W, levels, L) ? (int)L.total : 0;
 }
 
+// out may be img1 or img2 exactly (only the last launch writes it, and that one reads the workspace alone) and nothing else: not a shifted
+// view of an image, not a mask, side, info or the workspace; no operand may lie in the workspace
+static bool mb_out_ok(const float* img1, const float* img2, const float* mask1, const float* mask2, const uint8_t* side, const int32_t* info,
+                      const float* out, const void* workspace, int64_t ws_bytes, int64_t n) {
+    const int64_t img = 12 * n, msk = 4 * n;
+    if (out != img1 && mb_overlap(out, img, img1, img)) return false;
+    if (out != img2 && mb_overlap(out, img, img2, img)) return false;
+    if (mb_overlap(out, img, mask1, msk) || mb_overlap(out, img, mask2, msk)) return false;
+    if (side && mb_overlap(out, img, side, n)) return false;
+    if (info && mb_overlap(out, img, info, 16)) return false;
+    if (mb_overlap(workspace, ws_bytes, out, img) || mb_overlap(workspace, ws_bytes, img1, img) || mb_overlap(workspace, ws_bytes, img2, img)) return false;
+    if (mb_overlap(workspace, ws_bytes, mask1, msk) || mb_overlap(workspace, ws_bytes, mask2, msk)) return false;
+    if (side && mb_overlap(workspace, ws_bytes, side, n)) return false;
+    if (info && mb_overlap(workspace, ws_bytes, info, 16)) return false;
+    return true;
+}
+
 // side, info: the seam of st_seam_dp, or both NULL (the distance seam)
 static int mb_blend(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels, const uint8_t* side,
                     const int32_t* info, float* out, void* workspace, int64_t workspace_bytes, void* stream) {
     mb_layout L;
     if (!img1 || !img2 || !mask1 || !mask2 || !out || !workspace || !mb_plan(H, W, levels, L)) return ST_EINVAL;
     if (workspace_bytes < L.total || ((uintptr_t)workspace & 15)) return ST_EINVAL;
+    if (!mb_out_ok(img1, img2, mask1, mask2, side, info, out, workspace, L.total, (int64_t)H * W)) return ST_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     uint8_t *m1 = (uint8_t*)(ws + L.m1), *m2 = (uint8_t*)(ws + L.m2), *notu = (uint8_t*)(ws + L.notu);

@@ -353,6 +353,30 @@ static int sm_cost_launch(const float* img1, const float* img2, const float* mas
     return ST_OK;
 }
 
+static bool sm_overlap(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+}
+
+// an output overlaps nothing: no input (the kernels that write side, path and info run after others that read the images and masks, but the
+// cost plane is written while they are read), no other output, not the workspace; no input lies in the workspace.  ws may be NULL (st_seam_cost).
+static bool sm_operands_ok(const float* img1, const float* img2, const float* mask1, const float* mask2, int64_t n, const void* const* outs,
+                           const int64_t* out_bytes, int count, const void* ws, int64_t ws_bytes) {
+    const void* ins[4] = {img1, img2, mask1, mask2};
+    const int64_t in_bytes[4] = {12 * n, 12 * n, 4 * n, 4 * n};
+    for (int i = 0; i < count; ++i) {
+        if (!outs[i]) continue;
+        for (int j = 0; j < 4; ++j)
+            if (sm_overlap(outs[i], out_bytes[i], ins[j], in_bytes[j])) return false;
+        for (int j = i + 1; j < count; ++j)
+            if (outs[j] && sm_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j])) return false;
+        if (ws && sm_overlap(outs[i], out_bytes[i], ws, ws_bytes)) return false;
+    }
+    for (int j = 0; ws && j < 4; ++j)
+        if (sm_overlap(ins[j], in_bytes[j], ws, ws_bytes)) return false;
+    return true;
+}
+
 extern "C" int st_seam_workspace_bytes(int32_t H, int32_t W) {
     sm_layout L;
     return sm_plan(H, W, L) ? (int)L.total : 0;
@@ -361,6 +385,9 @@ extern "C" int st_seam_workspace_bytes(int32_t H, int32_t W) {
 extern "C" int st_seam_cost(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t* cost, void* stream) {
     sm_layout L;
     if (!img1 || !img2 || !mask1 || !mask2 || !cost || !sm_plan(H, W, L)) return ST_EINVAL;
+    const void* outs[1] = {cost};
+    const int64_t out_bytes[1] = {(int64_t)4 * H * W};
+    if (!sm_operands_ok(img1, img2, mask1, mask2, (int64_t)H * W, outs, out_bytes, 1, nullptr, 0)) return ST_EINVAL;
     return sm_cost_launch(img1, img2, mask1, mask2, nullptr, cost, H, W, (hipStream_t)stream);
 }
 
@@ -370,6 +397,9 @@ extern "C" int st_seam_dp(const float* img1, const float* img2, const float* mas
     if (!img1 || !img2 || !mask1 || !mask2 || !side_out || !info_out || !workspace || !sm_plan(H, W, L)) return ST_EINVAL;
     if (orientation < SM_AUTO || orientation > SM_HORIZONTAL || first < 0 || first > 2) return ST_EINVAL;
     if (workspace_bytes < L.total || ((uintptr_t)workspace & 15)) return ST_EINVAL;
+    const void* outs[3] = {side_out, path_out, info_out};
+    const int64_t out_bytes[3] = {(int64_t)H * W, (int64_t)4 * std::max(H, W), 16};
+    if (!sm_operands_ok(img1, img2, mask1, mask2, (int64_t)H * W, outs, out_bytes, 3, workspace, L.total)) return ST_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     uint32_t* records = (uint32_t*)(ws + L.records);

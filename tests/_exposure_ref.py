@@ -15,8 +15,9 @@ f32 = np.float32
 
 
 def to_u8(img, defects=NONE):
-    """the saver's rule: clamp to 0..255, truncate toward zero -> int64"""
-    x = np.clip(np.asarray(img, dtype=np.float64), 0, 255)
+    """the saver's rule: clamp to 0..255, truncate toward zero -> int64; NaN -> 0, -Inf -> 0, +Inf -> 255 (`st_u8_trunc`)"""
+    x = np.asarray(img, dtype=np.float64)
+    x = np.clip(np.where(np.isnan(x), 0, x), 0, 255)
     return (np.rint(x) if "round_p" in defects else np.trunc(x)).astype(np.int64)
 
 

@@ -65,8 +65,10 @@ def edt_sq(mask, border_is_site=True, return_index=False, defects=frozenset()):
 
 
 def to_u8(img, dtype=np.float32):
-    """the saver's rule (`to_pillow_fn`, `st_u8_trunc`): clamp to 0..255, truncate toward zero"""
-    return np.clip(np.trunc(np.asarray(img, dtype=np.float64)), 0, 255).astype(dtype)
+    """the saver's rule (`to_pillow_fn`, `st_u8_trunc`): clamp to 0..255, truncate toward zero; NaN -> 0, -Inf -> 0, +Inf -> 255, never -0"""
+    x = np.asarray(img, dtype=np.float64)
+    x = np.where(np.isnan(x), 0, x)
+    return (np.clip(np.trunc(x), 0, 255) + 0.0).astype(dtype)
 
 
 def fields(img1, img2, mask1, mask2, dtype=np.float32, defects=frozenset(), truncate=True):

@@ -20,8 +20,9 @@ def masks(mask1, mask2):
 
 
 def to_int(img, defects=frozenset()):
-    """p = trunc(clamp(x, 0, 255)) as int64 [3,H,W]"""
-    x = np.clip(np.asarray(img, dtype=np.float64), 0, 255)
+    """p = trunc(clamp(x, 0, 255)) as int64 [3,H,W]; NaN -> 0, -Inf -> 0, +Inf -> 255 (`st_u8_trunc`)"""
+    x = np.asarray(img, dtype=np.float64)
+    x = np.clip(np.where(np.isnan(x), 0, x), 0, 255)
     return (np.floor(x + 0.5) if "round" in defects else np.trunc(x)).astype(np.int64)
 
 
