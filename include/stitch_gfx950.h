@@ -852,6 +852,23 @@ int st_seam_dp(const float* img1, const float* img2, const float* mask1, const f
 int st_multiband_blend_seam(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels,
                             const uint8_t* side, const int32_t* info, float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- inner_crop: the largest hole-free rectangle of the stitch (csrc/crop.hip; contract in README.md, inner_crop; CPU restatement
+ *      tests/_crop_ref.py; this project's own contract, pinned against no library).  Masks as st_multiband_blend: float32 [H,W] (plane 0 of
+ *      the mask tensor), set where > 0.5 (NaN, -Inf and 0.5 unset, +Inf set); U = m1 or m2, U = m1 with mask2 NULL.  A rectangle (top, left,
+ *      h, w), h, w >= 1, is inside when every pixel of it is in U; the result is the inside rectangle with the largest area h w, then the
+ *      lowest top, then the lowest left, then the smallest h.  All integers.  ------------------------------------------------------------ */
+/* bytes of workspace st_inner_rect needs; 0 for a side outside 1..4096.                                                               */
+int st_inner_rect_workspace_bytes(int32_t H, int32_t W);
+/* info_out int32 [6]: valid, top, left, height, width, area; all zeros when U is empty.  runs_out (may be NULL) int16 [H,W]: r(y, x) = the
+ * number of consecutive pixels of U in column x ending at row y going up (0 outside U), the plane the rectangle is searched in.  3 launches
+ * on `stream` whose grids depend on H and W alone, nothing else: no synchronisation, no allocation, no atomics; the workspace needs no
+ * initialisation and may be reused by the next call on the same stream.  ST_EINVAL before any launch: a null mask1, info_out or workspace,
+ * a side outside 1..4096, a workspace smaller than st_inner_rect_workspace_bytes or not 16-byte aligned, an overlap: neither output
+ * (info_out, its 24 bytes; runs_out) may overlap a mask, the other output or the workspace (its first st_inner_rect_workspace_bytes
+ * bytes), and no mask may lie in the workspace.  mask1 and mask2 may overlap each other freely (they are only read).                     */
+int st_inner_rect(const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t* info_out, int16_t* runs_out, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,9 @@ fills them; with the shipped `tps_method="opencv"` the spline is this package's 
 installable here: unpinned against OpenCV).  `--multiband_fusion` adds an eleventh file of this package's own, `multiband_fusion.jpg`: the two
 warped images blended over a Laplacian pyramid along their distance-transform seam (README.md, multiband_fusion); `--exposure_compensation
 {gain,blocks}` equalises the two images' brightness from their overlap in front of that blend (README.md, exposure compensation); `--seam dp`
-moves the blend's seam from the distance transforms' to a minimum-difference path through the overlap (README.md, seam_dp)."""
+moves the blend's seam from the distance transforms' to a minimum-difference path through the overlap (README.md, seam_dp); `--crop inner`
+also writes `ave_fusion_crop.jpg` (and `multiband_fusion_crop.jpg`): the same canvases cut to the largest rectangle without a hole, found on
+the GPU (README.md, inner_crop)."""
 from __future__ import annotations
 
 import argparse
@@ -61,6 +63,8 @@ def get_config(argv=None):
     p.add_argument("--exposure_block", type=int, default=None, metavar="N", help="tile side of --exposure_compensation (8, 16, 32 or 64; default 32)")
     p.add_argument("--seam", choices=("dp",), default=None,
                    help="with --multiband_fusion: blend along a minimum-difference seam through the overlap (dynamic programming, GPU) instead of the distance-transform seam")
+    p.add_argument("--crop", choices=("inner",), default=None,
+                   help="also write ave_fusion_crop.jpg (and multiband_fusion_crop.jpg): the result cut to the largest rectangle inside the union of the two masks (GPU)")
     p.add_argument("--gpu_decode", action="store_true",
                    help="decode the input JPEGs on the GPU (Pillow's pixels, bit for bit); files outside the decoder's contract keep Pillow")
     p.add_argument("--dry-run", dest="dry_run", action="store_true",
@@ -79,7 +83,7 @@ def get_config(argv=None):
     for k, v in vars(args).items():
         if k in ("restore_ckpt", "gpu_jpeg", "gpu_decode", "jpeg_optimize", "multiband_fusion") and not v:         # (a switch that is off: config.txt stays what it was before the switch existed)
             continue
-        if k in ("jpeg_quality", "jpeg_subsampling", "jpeg_restart_blocks", "jpeg_restart_rows", "multiband_levels", "exposure_compensation", "exposure_block", "seam") and v is None:
+        if k in ("jpeg_quality", "jpeg_subsampling", "jpeg_restart_blocks", "jpeg_restart_rows", "multiband_levels", "exposure_compensation", "exposure_block", "seam", "crop") and v is None:
             continue
         cfg[k] = v
     cfg.TPS_PIPELINE_CONFIG = tps
@@ -205,6 +209,11 @@ def seam_of(cfg):
     return getattr(cfg, "seam", None)
 
 
+def crop_of(cfg):
+    """The `crop` argument the flag --crop asks for: None without it, else "inner"."""
+    return getattr(cfg, "crop", None)
+
+
 class _Saver:
     """JPEG writes of out.py:260-312.  The uint8 conversion runs on the GPU (clip + truncation, as `to_pillow_fn` does on the
     host), the bytes are copied to the host in the caller's thread, the JPEG encode + file write go to ``pool`` when one is given
@@ -297,7 +306,7 @@ def load_inpainter(name):
 
 
 def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_model=None, inpainter=None, forward=None, saver=None,
-                       gpu_jpeg=False, gpu_decode=False, jpeg_params=None, multiband=None, exposure=None, seam=None):
+                       gpu_jpeg=False, gpu_decode=False, jpeg_params=None, multiband=None, exposure=None, seam=None, crop=None):
     """out.py:158-312: forward (`test_out`), TPS post-pipeline with the configured `mix_fn`, saves, composition.  The inpainter
     is the caller's, else the pass-through stand-in (`load_inpainter`: `transref_inpainter` needs its checkpoint, the diffusion one is
     out of scope): with the stand-in, in `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the
@@ -315,7 +324,16 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     ``exposure``: None, or (mode, block) of `ops.exposure_compensate`, applied to the two operands of that blend and to nothing else (needs
     ``multiband``); the compensated pair is returned as `compensated1` / `compensated2`.
     ``seam``: None, or "dp": `ops.seam_dp` on the operands of that blend (the compensated pair when there is one) decides the ownership of the
-    overlap (needs ``multiband``); its planes are returned as `seam_side` / `seam_info`."""
+    overlap (needs ``multiband``); its planes are returned as `seam_side` / `seam_info`.
+    ``crop``: None, or "inner": `ops.inner_rect` on `mask1` / `mask2` as they go to the saver finds the largest rectangle inside their union
+    (README.md, inner_crop); `ave_fusion_crop.jpg` (and, with ``multiband``, `multiband_fusion_crop.jpg`) is that slice of the uncropped
+    canvas through the same saver.  The rectangle is searched directly after `ave_fusion.jpg` is queued, but the slice's size is data, so
+    the six ints are read back once per pair, after all of the pair's other launches are enqueued; the crop files are queued then, the
+    cropped `ave_fusion` first (before the saver's flush, so ``gpu_jpeg`` reads them back with the others), and none is written when the
+    union is empty.  Returned as `crop_info` (device int32 [6]) and `crop_rect` (host (top, left, h, w), or None).  The composition network's
+    files are not cropped: its canvas may be resized, so the rectangle does not apply to them."""
+    if crop not in (None, "inner"):
+        raise ValueError(f'crop must be None or "inner", got {crop!r}')
     if exposure is not None and multiband is None:
         raise ValueError("exposure compensation applies to the operands of the multiband blend: multiband must be given")
     if seam not in (None, "dp"):
@@ -368,6 +386,8 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     for key in ("mask1", "mask2"):
         saver.array((out[key] > 0.5)[0, 0].to(torch.uint8).mul(255), result_path + key + ".jpg")
     saver.image(out["new_blend_image"].float(), result_path + "ave_fusion.jpg")
+    if crop is not None:
+        out = dict(out, crop_info=stitch_amd.ops.inner_rect(out["mask1"].float(), out["mask2"].float()))
     if multiband is not None:
         img1, img2, k1, k2 = out["output1"].float().contiguous(), out["output2"].float().contiguous(), out["mask1"].float(), out["mask2"].float()
         if exposure is not None:
@@ -387,6 +407,13 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
         for key in ("learned_mask1", "learned_mask2"):
             saver.image(comp[key] * 255, result_path + key + ".jpg")
         out = dict(out, **comp)
+    if crop is not None:
+        valid, top, left, h, w, _ = out["crop_info"].tolist()          # the one read of the pair: everything else is enqueued
+        out = dict(out, crop_rect=(top, left, h, w) if valid else None)
+        if valid:
+            saver.image(out["new_blend_image"].float()[..., top:top + h, left:left + w], result_path + "ave_fusion_crop.jpg")
+            if multiband is not None:
+                saver.image(out["multiband_image"][..., top:top + h, left:left + w], result_path + "multiband_fusion_crop.jpg")
     saver.flush()
     check_decode(statuses)
     if own_saver:
@@ -395,7 +422,7 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
 
 
 def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=None, on_done=None, depth=2, gpu_jpeg=False, gpu_decode=False,
-              jpeg_params=None, multiband=None, exposure=None, seam=None):
+              jpeg_params=None, multiband=None, exposure=None, seam=None, crop=None):
     """The inference loop of out.py:351-357 as a software pipeline, `depth` pairs in flight.  While pair i is finished on the host
     (canvas bounds read back, canvas kernels, TPS post-pipeline with its control-point round trips, composition, device->host copies
     of the images), the network parts of pairs i + 1 .. i + depth - 1 -- both nets at 512x512, ~1 000 launches each, replayed from a
@@ -412,7 +439,8 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
     ``jpeg_params``: Pillow's `save` keywords for the result files (`_Saver`), on either encoder.
     ``multiband``: the pyramid levels of `multiband_fusion.jpg` (`inference_one_data`), blended on the pair's stream; None: not written.
     ``exposure``: (mode, block) of the gain compensation in front of that blend (`inference_one_data`); None: none.
-    ``seam``: "dp" for that blend along the minimum-difference seam (`inference_one_data`); None: the distance seam."""
+    ``seam``: "dp" for that blend along the minimum-difference seam (`inference_one_data`); None: the distance seam.
+    ``crop``: "inner" to write `ave_fusion_crop.jpg` / `multiband_fusion_crop.jpg` too (`inference_one_data`: one six-int read per pair); None: not written."""
     from concurrent.futures import ThreadPoolExecutor
     if not todo:
         return []
@@ -448,7 +476,7 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
             g, handle, st, statuses = inflight.pop(0)
             with torch.cuda.stream(st):
                 out, rp = inference_one_data(cfg, dd, save_root, model, composition_model, inpainter,
-                                             forward=lambda: g.finish(handle), saver=saver, multiband=multiband, exposure=exposure, seam=seam)
+                                             forward=lambda: g.finish(handle), saver=saver, multiband=multiband, exposure=exposure, seam=seam, crop=crop)
                 check_decode(statuses)
             # no host wait here: the graph of this slot is launched again on the SAME stream (pair j + depth), i.e. after everything
             # that reads this pair's static buffers
@@ -515,7 +543,7 @@ def main(argv=None):
         todo.append(dd)
     run_pairs(cfg, todo, save_root, model, composition_model, inpainter, gpu_jpeg=bool(getattr(cfg, "gpu_jpeg", False)),
               gpu_decode=bool(getattr(cfg, "gpu_decode", False)), jpeg_params=jpeg_params_of(cfg), multiband=multiband_of(cfg), exposure=exposure_of(cfg),
-              seam=seam_of(cfg))
+              seam=seam_of(cfg), crop=crop_of(cfg))
     if world > 1:
         import torch.distributed as tdist
         tdist.barrier()

@@ -1570,3 +1570,38 @@ def seam_dp(img1, img2, mask1, mask2, orientation="auto", first="auto", workspac
     check(lib.st_seam_dp(_pc(img1), _pc(img2), _pc(k1), _pc(k2), H, W, SEAM_ORIENTATIONS[orientation], SEAM_FIRST[first], _p(side), _p(path), _p(info),
                          _p(workspace), workspace.numel() * workspace.element_size(), _stream()), "st_seam_dp")
     return (side, info, path) if return_path else (side, info)
+
+
+# ---- inner_crop: the largest hole-free rectangle of the stitch (csrc/crop.hip; README.md, inner_crop) --------------------------------
+def inner_rect_workspace_bytes(H, W):
+    """bytes of workspace `inner_rect` needs for an H x W canvas; 0 for a shape outside the contract"""
+    return int(lib.st_inner_rect_workspace_bytes(int(H), int(W)))
+
+
+def inner_rect(mask1, mask2=None, workspace=None, return_runs=False):
+    """The largest axis-aligned rectangle inside the union of the masks (README.md, inner_crop): mask1, mask2 (optional) fp32 [1,1,H,W] or
+    [1,3,H,W] (channel 0 > 0.5), the mask operands of `multiband_blend` -> info int32 [6] on the device: valid, top, left, height, width,
+    area (all zeros when the union is empty); among the rectangles of the largest area the lowest top, then the lowest left, then the
+    smallest height.  ``return_runs``: also int16 [H,W], the set pixels of the union in a column ending at each row, the plane the rectangle
+    is searched in.  ``workspace``: a uint8 device tensor of at least `inner_rect_workspace_bytes` bytes, 16-byte aligned (default: allocated
+    here).  All launches go to the current stream and nothing is read back."""
+    masks = [m for m in (mask1, mask2) if m is not None]
+    if mask1 is None or mask1.dim() != 4:
+        raise ValueError(f"mask1 [1,1,H,W] or [1,3,H,W] expected, got {None if mask1 is None else tuple(mask1.shape)}")
+    H, W = mask1.shape[2:]
+    for m in masks:
+        if m.dim() != 4 or m.shape[0] != 1 or m.shape[1] not in (1, 3) or tuple(m.shape[2:]) != (H, W):
+            raise ValueError(f"mask [1,1,{H},{W}] or [1,3,{H},{W}] expected, got {tuple(m.shape)}")
+        if m.dtype != torch.float32:
+            raise ValueError(f"float32 tensors expected, got {m.dtype}")
+    if not (1 <= H <= MULTIBAND_MAX_SIDE and 1 <= W <= MULTIBAND_MAX_SIDE):
+        raise ValueError(f"sides must be in 1..{MULTIBAND_MAX_SIDE}, got {H} x {W}")
+    k1 = mask1[:, :1].contiguous()                                   # channel 0 (no copy unless the mask is a strided view)
+    k2 = mask2[:, :1].contiguous() if mask2 is not None else None
+    if workspace is None:
+        workspace = torch.empty(inner_rect_workspace_bytes(H, W), dtype=torch.uint8, device=mask1.device)
+    info = torch.empty(6, dtype=torch.int32, device=mask1.device)
+    runs = torch.empty((H, W), dtype=torch.int16, device=mask1.device) if return_runs else None
+    check(lib.st_inner_rect(_pc(k1), _pc(k2), H, W, _p(info), _p(runs), _p(workspace), workspace.numel() * workspace.element_size(), _stream()),
+          "st_inner_rect")
+    return (info, runs) if return_runs else info
