@@ -869,6 +869,28 @@ int st_inner_rect_workspace_bytes(int32_t H, int32_t W);
 int st_inner_rect(const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t* info_out, int16_t* runs_out, void* workspace,
                   int64_t workspace_bytes, void* stream);
 
+/* ---- patchmatch_inpainter: exemplar hole filling (csrc/patchmatch.hip; contract in README.md, patchmatch_inpainter; CPU restatement
+ *      tests/_patchmatch_ref.py; this project's own contract, pinned against no library).  PatchMatch (Barnes et al. 2009) inside a
+ *      coarse-to-fine vote / search loop (Wexler et al. 2007): 7x7 patches, sum of absolute differences over R, G, B, a stateless counter
+ *      hash for every random draw.  All integers.  img uint8 [H,W,3], mask uint8 [H,W] (nonzero = fill), sides 15..4096.
+ *      levels: 0 = auto (a level more while both sides of the next one are >= 32, at most 8), 1..8 = at most that many (cut where the next
+ *      level would have a side < 15).  ---------------------------------------------------------------------------------------------------- */
+/* the number of levels a call runs on; 0 for a side outside 15..4096 or levels outside 0..8.                                            */
+int st_patchmatch_levels(int32_t H, int32_t W, int32_t levels);
+/* bytes of workspace st_patchmatch_fill needs (below 2^31 for every accepted shape); 0 where st_patchmatch_levels is 0.                 */
+int st_patchmatch_workspace_bytes(int32_t H, int32_t W, int32_t levels);
+/* out uint8 [H,W,3]: the image with the hole filled, every known pixel byte for byte; the input itself when the mask is empty or level 0
+ * has no source patch.  info_out int32 [4]: valid, start level, level-0 sources, level-0 targets.  nnf_out (may be NULL) int32 [H,W,2]:
+ * the level-0 match (y, x) of every target centre after the last sweep, -1 elsewhere; sad_out (may be NULL) int32 [H,W]: its cost, -1
+ * elsewhere and everywhere with iters = 0.  iters 0..64 search sweeps per level.  2 + (6 + 2 iters) levels launches on
+ * `stream` whose grids depend on H, W, levels and iters alone, nothing else: no synchronisation, no allocation, no atomics; the workspace
+ * needs no initialisation and may be reused by the next call on the same stream.  ST_EINVAL before any launch: a null img, mask, out,
+ * info_out or workspace, a rejected shape, levels or iters, a workspace smaller than st_patchmatch_workspace_bytes or not 16-byte
+ * aligned, an overlap: no output may overlap an input, another output or the workspace (its first st_patchmatch_workspace_bytes bytes),
+ * and no input may lie in the workspace.  img and mask may overlap each other freely (they are only read).                              */
+int st_patchmatch_fill(const uint8_t* img, const uint8_t* mask, int32_t H, int32_t W, int32_t levels, int32_t iters, int32_t seed, uint8_t* out,
+                       int32_t* info_out, int32_t* nnf_out, int32_t* sad_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

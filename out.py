@@ -295,7 +295,8 @@ def load_inpainter(name):
     """out.py:341-346: `core.inference.mix_methods.utils.<name>.inpainter`.  `cv_inpainter` (the reference's OpenCV Telea
     inpainter, GPU kernels here) is shipped; `transref_inpainter` (the TransRef network, GPU kernels) is shipped but its module needs
     the reference's checkpoint `mix_methods/utils/TransRef/400_Trans.pth` and raises ImportError without it; the diffusion inpainter
-    is out of scope.  A module that cannot be imported falls back to the pass-through stand-in."""
+    is out of scope.  `patchmatch_inpainter` (exemplar hole filling on the GPU, no weights, no counterpart in the reference;
+    `inf_configs/*_pm.py`) is shipped too.  A module that cannot be imported falls back to the pass-through stand-in."""
     import importlib
     try:
         return importlib.import_module(f"stitch_amd.mix_methods.utils.{name}").inpainter
@@ -311,7 +312,8 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     is the caller's, else the pass-through stand-in (`load_inpainter`: `transref_inpainter` needs its checkpoint, the diffusion one is
     out of scope): with the stand-in, in `warp2.jpg`, `mask2.jpg`, `ave_fusion.jpg` and the
     composition inputs the holes hold what `mix_fn` fills from image 1 and the thin border region it hands to the inpainter is not
-    synthesised; `cv_inpainter` (GPU Telea inpainting, unpinned against OpenCV) fills it.
+    synthesised; `cv_inpainter` (GPU Telea inpainting, unpinned against OpenCV) fills it, and `patchmatch_inpainter` (GPU exemplar
+    fill, this project's own contract, pinned against no library) fills it with image content instead of diffused border colours.
 
     ``forward``: a callable returning the `test_out` dict of this pair whose network part is already in flight (``main``
     launches pair i + 1's hipGraph before it finishes pair i); default = load + ``warp_model(..., type="test_out")`` here.

@@ -1605,3 +1605,61 @@ def inner_rect(mask1, mask2=None, workspace=None, return_runs=False):
     check(lib.st_inner_rect(_pc(k1), _pc(k2), H, W, _p(info), _p(runs), _p(workspace), workspace.numel() * workspace.element_size(), _stream()),
           "st_inner_rect")
     return (info, runs) if return_runs else info
+
+
+# ---- patchmatch_inpainter: exemplar hole filling (csrc/patchmatch.hip; README.md, patchmatch_inpainter) -------------------------------
+PATCHMATCH_MIN_SIDE, PATCHMATCH_MAX_SIDE, PATCHMATCH_MAX_LEVELS, PATCHMATCH_MAX_ITERS = 15, 4096, 8, 64
+
+
+def _patchmatch_levels(levels):
+    if levels is None:
+        return 0
+    if not 1 <= int(levels) <= PATCHMATCH_MAX_LEVELS:
+        raise ValueError(f"levels must be None (auto) or in 1..{PATCHMATCH_MAX_LEVELS}, got {levels}")
+    return int(levels)
+
+
+def patchmatch_workspace_bytes(H, W, levels=None):
+    """bytes of workspace `inpaint_patchmatch` needs for an H x W image; 0 for a shape outside the contract"""
+    return int(lib.st_patchmatch_workspace_bytes(int(H), int(W), _patchmatch_levels(levels)))
+
+
+def patchmatch_levels(H, W, levels=None):
+    """the number of pyramid levels `inpaint_patchmatch` runs on; 0 for a shape outside the contract"""
+    return int(lib.st_patchmatch_levels(int(H), int(W), _patchmatch_levels(levels)))
+
+
+def inpaint_patchmatch(img, mask, levels=None, iters=4, seed=1, workspace=None, return_fields=False):
+    """Exemplar hole filling (README.md, patchmatch_inpainter; this project's own contract, pinned against no library): img uint8 [H,W,3],
+    mask uint8 / bool [H,W] (nonzero = fill), the operands `inpaint_prep` produces -> (out uint8 [H,W,3], info int32 [4] on the device:
+    valid, start level, level-0 sources, level-0 targets).  Known pixels come back byte for byte; with an empty mask or without a source
+    patch at level 0 the image comes back as it is and info[0] = 0.  ``levels`` None = auto, else at most that many; ``iters`` search sweeps
+    per level; ``seed`` keys every random draw.  ``return_fields``: also the level-0 match of every target centre after the last sweep
+    (int32 [H,W,2], -1 elsewhere) and its cost (int32 [H,W], -1 elsewhere and without a sweep).  ``workspace``: a uint8 device tensor of at
+    least `patchmatch_workspace_bytes` bytes, 16-byte aligned (default: allocated here).  All launches go to the current stream and nothing
+    is read back."""
+    if img.dim() != 3 or img.shape[2] != 3 or img.dtype != torch.uint8:
+        raise ValueError(f"uint8 [H,W,3] image expected, got {img.dtype} {tuple(img.shape)}")
+    H, W, _ = img.shape
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.uint8)
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W):
+        raise ValueError(f"uint8 [{H},{W}] mask expected, got {mask.dtype} {tuple(mask.shape)}")
+    if mask.device != img.device:
+        raise ValueError("image and mask must be on the same device")
+    if not (PATCHMATCH_MIN_SIDE <= H <= PATCHMATCH_MAX_SIDE and PATCHMATCH_MIN_SIDE <= W <= PATCHMATCH_MAX_SIDE):
+        raise ValueError(f"sides must be in {PATCHMATCH_MIN_SIDE}..{PATCHMATCH_MAX_SIDE}, got {H} x {W}")
+    lv = _patchmatch_levels(levels)
+    if not 0 <= int(iters) <= PATCHMATCH_MAX_ITERS:
+        raise ValueError(f"iters must be in 0..{PATCHMATCH_MAX_ITERS}, got {iters}")
+    seed = int(seed) & 0xFFFFFFFF
+    dev = img.device
+    if workspace is None:
+        workspace = torch.empty(patchmatch_workspace_bytes(H, W, levels), dtype=torch.uint8, device=dev)
+    out = torch.empty_like(img, memory_format=torch.contiguous_format)
+    info = torch.empty(4, dtype=torch.int32, device=dev)
+    nnf = torch.empty((H, W, 2), dtype=torch.int32, device=dev) if return_fields else None
+    sad = torch.empty((H, W), dtype=torch.int32, device=dev) if return_fields else None
+    check(lib.st_patchmatch_fill(_pc(img), _pc(mask), H, W, lv, int(iters), seed - (1 << 32) if seed >= 1 << 31 else seed, _p(out), _p(info), _p(nnf), _p(sad),
+                                 _p(workspace), workspace.numel() * workspace.element_size(), _stream()), "st_patchmatch_fill")
+    return (out, info, nnf, sad) if return_fields else (out, info)
