@@ -852,6 +852,34 @@ int st_seam_dp(const float* img1, const float* img2, const float* mask1, const f
 int st_multiband_blend_seam(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, int32_t levels,
                             const uint8_t* side, const int32_t* info, float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- seam_gc: a minimum cut over the overlap, for the same place as seam_dp (csrc/seam_gc.hip; contract in README.md, seam_gc; CPU
+ *      restatement tests/_seam_gc_ref.py over scipy's maximum_flow; this project's own contract, unpinned against OpenCV's
+ *      detail::GraphCutSeamFinder).  Operands, pixel and mask rules as st_seam_dp.  Nodes: the pixels of O; every 4-neighbour pair inside O
+ *      is joined by an arc in each direction of capacity e(p) + e(q), e = 1 + sum_c |p1 - p2|.  S = O with a 4-neighbour in E1 is the
+ *      source, T = O with a 4-neighbour in E2 and not in S the sink.  side = 0 exactly on the overlap pixels that can reach T along residual
+ *      arcs under a maximum flow (the smallest sink side among the minimum cuts), 1 everywhere else; all ones without both S and T.
+ *      Push-relabel with an exact global relabel per round; no atomics, one writer per word, no kernel loops on data.  The number of rounds
+ *      depends on the data, so the caller drives them: begin, then round until the status record says done, then finish.
+ *      The status record is int32 [8] at the head of the workspace: pixels with excess and a finite label, relabel still changing, rounds
+ *      done, done, source pixels with a finite label, valid (S and T non-empty), push sweeps done, label launches done.            ------- */
+/* bytes of workspace the three entries need; 0 for a side outside 1..4096.                                                            */
+int st_seam_gc_workspace_bytes(int32_t H, int32_t W);
+/* masks, seeds, capacities and the first global relabel: 12 launches on `stream`, nothing else.  The workspace needs no initialisation.
+ * ST_EINVAL before any launch: a null pointer, a side outside 1..4096, a workspace smaller than st_seam_gc_workspace_bytes or not 16-byte
+ * aligned, an image or a mask that lies in the workspace (its first st_seam_gc_workspace_bytes bytes).                                */
+int st_seam_gc_begin(const float* img1, const float* img2, const float* mask1, const float* mask2, int32_t H, int32_t W, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+/* one round on the workspace of st_seam_gc_begin with the same H and W: the sources saturate their arcs to finite-label neighbours, 32 push /
+ * gather-relabel sweeps, then 8 launches of the global relabel (64 label sweeps inside a tile each) and the status record: 73 launches.
+ * While a relabel has not reached its fixpoint (status word 1) the sweeps of a round do nothing and the round only continues the relabel;
+ * st_seam_gc_relabel is that round without the idle launches: 16 launches of the relabel and the status record, 17 launches.  After done
+ * neither changes anything.  Both count as a round in the status record.                                                            */
+int st_seam_gc_round(int32_t H, int32_t W, void* workspace, int64_t workspace_bytes, void* stream);
+int st_seam_gc_relabel(int32_t H, int32_t W, void* workspace, int64_t workspace_bytes, void* stream);
+/* side_out uint8 [H,W], info_out int32 [4] = (valid, 3, cut >> 31, cut & (2^31 - 1)); when the status record does not say done: valid =
+ * 0, cut = 0, side all ones.  2 launches.  ST_EINVAL: as above; side_out and info_out may overlap neither each other nor the workspace.  */
+int st_seam_gc_finish(int32_t H, int32_t W, uint8_t* side_out, int32_t* info_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- inner_crop: the largest hole-free rectangle of the stitch (csrc/crop.hip; contract in README.md, inner_crop; CPU restatement
  *      tests/_crop_ref.py; this project's own contract, pinned against no library).  Masks as st_multiband_blend: float32 [H,W] (plane 0 of
  *      the mask tensor), set where > 0.5 (NaN, -Inf and 0.5 unset, +Inf set); U = m1 or m2, U = m1 with mask2 NULL.  A rectangle (top, left,

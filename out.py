@@ -18,7 +18,8 @@ fills them; with the shipped `tps_method="opencv"` the spline is this package's 
 installable here: unpinned against OpenCV).  `--multiband_fusion` adds an eleventh file of this package's own, `multiband_fusion.jpg`: the two
 warped images blended over a Laplacian pyramid along their distance-transform seam (README.md, multiband_fusion); `--exposure_compensation
 {gain,blocks}` equalises the two images' brightness from their overlap in front of that blend (README.md, exposure compensation); `--seam dp`
-moves the blend's seam from the distance transforms' to a minimum-difference path through the overlap (README.md, seam_dp); `--crop inner`
+moves the blend's seam from the distance transforms' to a minimum-difference path through the overlap (README.md, seam_dp), `--seam gc` to a
+minimum cut over the overlap (README.md, seam_gc); `--crop inner`
 also writes `ave_fusion_crop.jpg` (and `multiband_fusion_crop.jpg`): the same canvases cut to the largest rectangle without a hole, found on
 the GPU (README.md, inner_crop)."""
 from __future__ import annotations
@@ -61,8 +62,9 @@ def get_config(argv=None):
     p.add_argument("--exposure_compensation", choices=("gain", "blocks"), default=None,
                    help="with --multiband_fusion: gain-compensate the two warped images from their overlap before the blend (one pair of gains, or one per tile)")
     p.add_argument("--exposure_block", type=int, default=None, metavar="N", help="tile side of --exposure_compensation (8, 16, 32 or 64; default 32)")
-    p.add_argument("--seam", choices=("dp",), default=None,
-                   help="with --multiband_fusion: blend along a minimum-difference seam through the overlap (dynamic programming, GPU) instead of the distance-transform seam")
+    p.add_argument("--seam", choices=("dp", "gc"), default=None,
+                   help="with --multiband_fusion: blend along a minimum-difference seam through the overlap instead of the distance-transform seam (GPU): "
+                        "dp a monotone path by dynamic programming, gc a minimum cut (push-relabel; synchronises with the host once per round)")
     p.add_argument("--crop", choices=("inner",), default=None,
                    help="also write ave_fusion_crop.jpg (and multiband_fusion_crop.jpg): the result cut to the largest rectangle inside the union of the two masks (GPU)")
     p.add_argument("--gpu_decode", action="store_true",
@@ -205,7 +207,7 @@ def exposure_of(cfg):
 
 
 def seam_of(cfg):
-    """The `seam` argument the flag --seam asks for: None without it, else "dp"."""
+    """The `seam` argument the flag --seam asks for: None without it, else "dp" or "gc"."""
     return getattr(cfg, "seam", None)
 
 
@@ -325,8 +327,9 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     returned as `multiband_image`.  This file is the package's own, not one of the reference's.
     ``exposure``: None, or (mode, block) of `ops.exposure_compensate`, applied to the two operands of that blend and to nothing else (needs
     ``multiband``); the compensated pair is returned as `compensated1` / `compensated2`.
-    ``seam``: None, or "dp": `ops.seam_dp` on the operands of that blend (the compensated pair when there is one) decides the ownership of the
-    overlap (needs ``multiband``); its planes are returned as `seam_side` / `seam_info`.
+    ``seam``: None, "dp" or "gc": `ops.seam_dp` / `ops.seam_gc` on the operands of that blend (the compensated pair when there is one) decides
+    the ownership of the overlap (needs ``multiband``); its planes are returned as `seam_side` / `seam_info`.  "gc" reads its status record
+    back from the device once per round (README.md, seam_gc).
     ``crop``: None, or "inner": `ops.inner_rect` on `mask1` / `mask2` as they go to the saver finds the largest rectangle inside their union
     (README.md, inner_crop); `ave_fusion_crop.jpg` (and, with ``multiband``, `multiband_fusion_crop.jpg`) is that slice of the uncropped
     canvas through the same saver.  The rectangle is searched directly after `ave_fusion.jpg` is queued, but the slice's size is data, so
@@ -338,8 +341,8 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
         raise ValueError(f'crop must be None or "inner", got {crop!r}')
     if exposure is not None and multiband is None:
         raise ValueError("exposure compensation applies to the operands of the multiband blend: multiband must be given")
-    if seam not in (None, "dp"):
-        raise ValueError(f'seam must be None or "dp", got {seam!r}')
+    if seam not in (None, "dp", "gc"):
+        raise ValueError(f'seam must be None, "dp" or "gc", got {seam!r}')
     if seam is not None and multiband is None:
         raise ValueError("the seam decides the ownership of the multiband blend: multiband must be given")
     own_saver = saver is None
@@ -397,7 +400,7 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
             out = dict(out, compensated1=img1, compensated2=img2)
         pair = None
         if seam is not None:
-            pair = stitch_amd.ops.seam_dp(img1, img2, k1, k2)
+            pair = (stitch_amd.ops.seam_gc if seam == "gc" else stitch_amd.ops.seam_dp)(img1, img2, k1, k2)
             out = dict(out, seam_side=pair[0], seam_info=pair[1])
         out = dict(out, multiband_image=stitch_amd.ops.multiband_blend(img1, img2, k1, k2, levels=multiband, seam=pair))
         saver.image(out["multiband_image"], result_path + "multiband_fusion.jpg")
@@ -441,7 +444,7 @@ def run_pairs(cfg, todo, save_root, model, composition_model=None, inpainter=Non
     ``jpeg_params``: Pillow's `save` keywords for the result files (`_Saver`), on either encoder.
     ``multiband``: the pyramid levels of `multiband_fusion.jpg` (`inference_one_data`), blended on the pair's stream; None: not written.
     ``exposure``: (mode, block) of the gain compensation in front of that blend (`inference_one_data`); None: none.
-    ``seam``: "dp" for that blend along the minimum-difference seam (`inference_one_data`); None: the distance seam.
+    ``seam``: "dp" for that blend along the minimum-difference path, "gc" along the minimum cut (`inference_one_data`); None: the distance seam.
     ``crop``: "inner" to write `ave_fusion_crop.jpg` / `multiband_fusion_crop.jpg` too (`inference_one_data`: one six-int read per pair); None: not written."""
     from concurrent.futures import ThreadPoolExecutor
     if not todo:

@@ -3,6 +3,7 @@ passes raw device pointers + sizes to libstitch_gfx950.so on torch's current HIP
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 
 import torch
 
@@ -1570,6 +1571,55 @@ def seam_dp(img1, img2, mask1, mask2, orientation="auto", first="auto", workspac
     check(lib.st_seam_dp(_pc(img1), _pc(img2), _pc(k1), _pc(k2), H, W, SEAM_ORIENTATIONS[orientation], SEAM_FIRST[first], _p(side), _p(path), _p(info),
                          _p(workspace), workspace.numel() * workspace.element_size(), _stream()), "st_seam_dp")
     return (side, info, path) if return_path else (side, info)
+
+
+# ---- seam_gc: a minimum cut over the overlap for the same place (csrc/seam_gc.hip; README.md, seam_gc) --------------------------------
+SEAM_GC_MAX_ROUNDS = 2048                    # at least 8 x the most rounds any measured scene needed (README.md, seam_gc; profiles/seam_gc_bench.json)
+SEAM_GC_PUSH_SWEEPS = 32                     # push / gather sweeps per round (csrc/seam_gc.hip)
+
+
+def seam_gc_workspace_bytes(H, W):
+    """bytes of workspace `seam_gc` needs for an H x W canvas; 0 for a shape outside the contract"""
+    return int(lib.st_seam_gc_workspace_bytes(int(H), int(W)))
+
+
+def seam_gc(img1, img2, mask1, mask2, workspace=None, max_rounds=None, return_stats=False):
+    """A minimum cut over the overlap of two warped images (README.md, seam_gc), on the operands of `multiband_blend` and `seam_dp`
+    -> (side, info[, stats]).  side uint8 [H,W]: 0 on the overlap pixels that fall to image 2 -- those that can still reach the sink under
+    a maximum flow, the smallest sink side among all minimum cuts -- and 1 at every other canvas pixel (all ones without a valid cut).  info
+    int32 [4] on the device: valid, 3, cut >> 31, cut & (2^31 - 1).  (side, info) is what `multiband_blend(seam=...)` takes.
+    ``workspace``: a uint8 device tensor of at least `seam_gc_workspace_bytes` bytes, 16-byte aligned (default: allocated here).
+    The number of push-relabel rounds depends on the data: after every round the status record (32 bytes) is read back from the device,
+    so unlike `seam_dp` the call synchronises with the host and cannot be captured into a hipGraph as a whole.  ``max_rounds`` (default
+    `SEAM_GC_MAX_ROUNDS`; 0 is allowed) bounds the rounds; when they do not suffice a warning is issued and info says not valid, with side
+    all ones, so the blend keeps its distance seam.  ``return_stats``: also a dict with `converged`, `rounds`, `sweeps` (push / gather
+    sweeps), `label_launches` and `host_reads`."""
+    H, W, k1, k2 = _seam_operands(img1, img2, mask1, mask2)
+    max_rounds = SEAM_GC_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+    if max_rounds < 0:
+        raise ValueError(f"max_rounds must be >= 0, got {max_rounds}")
+    if workspace is None:
+        workspace = torch.empty(seam_gc_workspace_bytes(H, W), dtype=torch.uint8, device=img1.device)
+    nbytes = workspace.numel() * workspace.element_size()
+    side = torch.empty((H, W), dtype=torch.uint8, device=img1.device)
+    info = torch.empty(4, dtype=torch.int32, device=img1.device)
+    check(lib.st_seam_gc_begin(_pc(img1), _pc(img2), _pc(k1), _pc(k2), H, W, _p(workspace), nbytes, _stream()), "st_seam_gc_begin")
+    record = workspace.view(torch.uint8).reshape(-1)[:32].view(torch.int32)
+    status = record.tolist()                                 # a device -> host read per round: the status record
+    reads = 1
+    while not status[3] and status[2] < max_rounds:
+        if status[1]:                                        # the global relabel has not reached its fixpoint: only that goes on
+            check(lib.st_seam_gc_relabel(H, W, _p(workspace), nbytes, _stream()), "st_seam_gc_relabel")
+        else:
+            check(lib.st_seam_gc_round(H, W, _p(workspace), nbytes, _stream()), "st_seam_gc_round")
+        status = record.tolist()
+        reads += 1
+    check(lib.st_seam_gc_finish(H, W, _p(side), _p(info), _p(workspace), nbytes, _stream()), "st_seam_gc_finish")
+    if not status[3]:
+        warnings.warn(f"seam_gc: no minimum cut after {status[2]} rounds (max_rounds = {max_rounds}); the blend keeps the distance seam")
+    if return_stats:
+        return side, info, dict(converged=bool(status[3]), rounds=status[2], sweeps=status[6], label_launches=status[7], host_reads=reads)
+    return side, info
 
 
 # ---- inner_crop: the largest hole-free rectangle of the stitch (csrc/crop.hip; README.md, inner_crop) --------------------------------
