@@ -26,8 +26,11 @@ def validate(cfg, val_dataset, batch_size=1, gpu_decode=False):
     if not (hasattr(cfg, "homo_backbone") and cfg.homo_backbone is not None):
         raise NotImplementedError
     model = stitch_amd.build_model(cfg)
-    print("[Loading ckpt from {}]".format(cfg.restore_ckpt))
-    model.load_state_dict(torch.load(cfg.restore_ckpt, map_location="cpu", weights_only=True), strict=True)
+    if model.sources() == ("features", "zero") and not os.path.exists(cfg.restore_ckpt):
+        print("[No ckpt at {}: homo_source='features' and flow_source='zero' read no network weights]".format(cfg.restore_ckpt))
+    else:
+        print("[Loading ckpt from {}]".format(cfg.restore_ckpt))
+        model.load_state_dict(torch.load(cfg.restore_ckpt, map_location="cpu", weights_only=True), strict=True)
     model = model.cuda().eval()
     return sev.validate_with_model(model, val_dataset, batch_size=batch_size, gpu_decode=gpu_decode)[0]
 

@@ -919,6 +919,42 @@ int st_patchmatch_workspace_bytes(int32_t H, int32_t W, int32_t levels);
 int st_patchmatch_fill(const uint8_t* img, const uint8_t* mask, int32_t H, int32_t W, int32_t levels, int32_t iters, int32_t seed, uint8_t* out,
                        int32_t* info_out, int32_t* nnf_out, int32_t* sad_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- feature_align: a weight-free alignment front end (csrc/features.hip; contract in README.md, feature_align; CPU restatement
+ *      tests/_features_ref.py; this project's own contract, pinned against no library).  Harris corners (k = 1/16, 7x7 window, the best 4 per
+ *      32x32 cell), upright BRIEF-256 on 5x5 box sums, mutual nearest neighbours under a ratio test, RANSAC homography in fp64.  Images
+ *      float32 [B,3,H,W], pixel = trunc(clamp(x, 0, 255)); B 1..64, sides 64..1024.  N = 4 ceil(H/32) ceil(W/32) keypoint slots per image,
+ *      slot = 4 cell + rank; keypoints int32 [B,N,2] = (x, y), (-1, -1) in an unused slot; descriptors uint32 [B,N,8].  No call
+ *      synchronises, allocates or uses atomics; the launch count and every grid depend on B, H, W and max_hyp alone; no buffer needs
+ *      initialisation.  Every entry returns ST_EINVAL before any launch for a null pointer, a rejected shape or parameter, and an output
+ *      that overlaps any other operand of the call (inputs may overlap each other freely).  -------------------------------------------- */
+/* N; 0 for a side outside 64..1024.                                                                                                     */
+int st_feature_slots(int32_t H, int32_t W);
+/* the BRIEF pattern into HOST memory, int8 [256,4] = (ax, ay, bx, by) of pair k: bit k = S(p + a) < S(p + b).                             */
+int st_feature_brief_pattern(int8_t* out_host);
+/* bytes of workspace st_feature_homography needs (below 2^31 for every accepted shape); 0 for a rejected B, H, W or max_hyp.             */
+int st_feature_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t max_hyp);
+/* the regions of that workspace, byte offsets into HOST memory int64 [10]: box uint16 [2,B,H,W], keypoints int32 [2,B,N,2], descriptors
+ * uint32 [2,B,N,8], nn int32 [2,B,N,3], matches int32 [B,N,2], count int32 [B], normalised match coordinates fp64 [B,N,4], scores int32
+ * [B,max_hyp], inlier mask uint8 [B,N], total.  After a call they hold that call's intermediate data.                                    */
+int st_feature_workspace_layout(int32_t B, int32_t H, int32_t W, int32_t max_hyp, int64_t* offsets_host);
+/* kp_out int32 [B,N,2]; box_out uint16 [B,H,W], the 5x5 box sum of the luma (terms outside the image 0).  1 launch.                      */
+int st_feature_detect(const float* img, int32_t B, int32_t H, int32_t W, int32_t* kp_out, uint16_t* box_out, void* stream);
+/* desc_out uint32 [B,N,8] from the box sums and keypoints of st_feature_detect; all zero for a slot that is not a keypoint.  1 launch.    */
+int st_feature_describe(const uint16_t* box, const int32_t* kp, int32_t B, int32_t H, int32_t W, uint32_t* desc_out, void* stream);
+/* nn_out int32 [2,B,N,3]: per direction (0: image 1 -> 2, 1: the reverse) and slot (best slot or -1, d1, d2), 257 = no such distance;
+ * matches_out int32 [B,N,2] = (slot 1, slot 2) in slot order of image 1, (-1, -1) behind the last; count_out int32 [B].  2 launches.      */
+int st_feature_match(const int32_t* kp1, const uint32_t* desc1, const int32_t* kp2, const uint32_t* desc2, int32_t B, int32_t H, int32_t W, int32_t* nn_out,
+                     int32_t* matches_out, int32_t* count_out, void* stream);
+/* motion_out float32 [B,4,2], H_out float32 [B,3,3], info_out int32 [B,8] = (valid, keypoints 1, keypoints 2, matches, winner k or -1,
+ * inliers, 0, 0), mask_out uint8 [B,N]: inlier flag of every list entry.  max_hyp 1..65536, thr finite and > 0, min_inliers >= 0.
+ * workspace: at least 32 B N + 4 B max_hyp bytes, 16-byte aligned.  3 launches.                                                          */
+int st_feature_ransac(const int32_t* kp1, const int32_t* kp2, const int32_t* matches, const int32_t* count, int32_t B, int32_t H, int32_t W, int32_t max_hyp,
+                      double thr, int32_t min_inliers, int32_t seed, float* motion_out, float* H_out, int32_t* info_out, uint8_t* mask_out, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+/* the four stages on both images inside `workspace` (st_feature_workspace_bytes, 16-byte aligned): 7 launches.                           */
+int st_feature_homography(const float* img1, const float* img2, int32_t B, int32_t H, int32_t W, int32_t max_hyp, double thr, int32_t min_inliers,
+                          int32_t seed, float* motion_out, float* H_out, int32_t* info_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

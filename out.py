@@ -366,14 +366,19 @@ def inference_one_data(cfg, data_dict, save_root_path, warp_model, composition_m
     # ---- TPS post-pipeline incl. the mix_fn plug-in (out.py:218-258, core/inference/tps_pipline.py:20-205) on the GPU
     import stitch_amd
     tpc = cfg.TPS_PIPELINE_CONFIG
-    fb = getattr(cfg, "use_fb_consistency_mask", False)
+    fb = getattr(cfg, "use_fb_consistency_mask", False) and "occlusion_mask" in out     # (flow_source="zero" computes no flow, so no consistency mask either)
+    occlusion_mask = out.get("occlusion_mask")
+    if occlusion_mask is None:
+        # no flow, nothing occluded: the mask the consistency check gives for a zero backward flow, all ones on image 1's footprint on the canvas
+        ones = torch.ones((1, 1) + tuple(out["residual_flow"].shape[2:]), device=out["output1"].device)
+        occlusion_mask = stitch_amd.ops.homo_warp(ones, out["I_mat"].view(1, 9), (out["out_height"], out["out_width"]))
     valid = out["origin_occlusion_mask"] if (fb and tpc.use_valid_on_flow) else None                      # out.py:219-222
     border_points_mask = None
     if fb and tpc.use_border_points_mask:                                                                 # out.py:224-232
         border_points_mask = out["occlusion_mask"] if tpc.use_occ_filter else (out["H_warp_mask"].mean(dim=1, keepdim=True) > 0.5).float()
     inputs = dict(output1=out["output1"], mask1=out["mask1"], H_warp=out["H_warp"], H_warp_mask=out["H_warp_mask"],
                   final_warp=out["final_warp"], mask2=out["mask2"], residual_flow=out["residual_flow"], valid=valid,
-                  occlusion_mask=out["occlusion_mask"], border_points_mask=border_points_mask)
+                  occlusion_mask=occlusion_mask, border_points_mask=border_points_mask)
     limit = dict(width_min=out["width_min"], height_min=out["height_min"], out_height=out["out_height"], out_width=out["out_width"])
     import importlib
     mix_fn = importlib.import_module(f"stitch_amd.mix_methods.{tpc.mix_method}").mix_fn                     # out.py:235

@@ -18,6 +18,10 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .feature_align import FeatureAligner
+
+HOMO_SOURCES = ("network", "features")           # cfg.homo_source: the UDIS2 regression network, or corners + BRIEF + RANSAC (feature_align.py)
+FLOW_SOURCES = ("network", "zero")               # cfg.flow_source: FlowFormer++, or no residual flow at all
 
 
 def preprocess_occlusion_mask(occlusion_mask, kernel_size=(19, 19)):
@@ -41,6 +45,7 @@ class FlowHomoAdpater(nn.Module):
         self.homo_backbone = homo_backbone
         self.flow_backbone = flow_backbone
         self._host = {}
+        self._aligner = None             # feature_align.FeatureAligner, built on first use with cfg.homo_source == "features"
         self._eval_pipeline = None       # stitch_amd.evaluate.EvalPipeline: hipGraphs of the evaluation loop, captured on first use
 
     # checkpoints saved from DataParallel carry a "module." prefix (out.py:80-85)
@@ -98,9 +103,27 @@ class FlowHomoAdpater(nn.Module):
     def _corners(self, dev, w, h):
         return self._mat(dev, ("corners", float(w), float(h)), [[0., 0.], [w, 0.], [0., h], [w, h]])
 
+    # ------------------------------------------------------------------ where the motion and the residual flow come from
+    def sources(self):
+        """(cfg.homo_source, cfg.flow_source), both "network" when the key is absent.  A different pair is a different launch sequence: the
+        graph holders key their captures by it."""
+        src = (_flag(self.cfg, "homo_source", "network"), _flag(self.cfg, "flow_source", "network"))
+        if src[0] not in HOMO_SOURCES or src[1] not in FLOW_SOURCES:
+            raise ValueError(f"homo_source must be one of {HOMO_SOURCES} and flow_source one of {FLOW_SOURCES}, got {src}")
+        return src
+
+    def feature_aligner(self):
+        """the aligner of homo_source="features"; cfg.feature_align (optional) holds FeatureAligner's keyword arguments"""
+        if self._aligner is None:
+            self._aligner = FeatureAligner(**dict(_flag(self.cfg, "feature_align", {}) or {}))
+        return self._aligner
+
     # ------------------------------------------------------------------ reference surface
     def predict_homo(self, input1_tensor, input2_tensor):
-        """[0,255] -> corner offsets [B,4,2] (flowHomoAdpater.py:53-61); x/127.5 - 1 is fused into the prep."""
+        """[0,255] -> corner offsets [B,4,2] (flowHomoAdpater.py:53-61); x/127.5 - 1 is fused into the prep.  With homo_source="features"
+        the offsets come from the pixels themselves (ops.feature_homography) and no kernel of the homography network is launched."""
+        if self.sources()[0] == "features":
+            return self.feature_aligner().motion(input1_tensor, input2_tensor)
         off = self.homo_backbone.offsets_from_images(input1_tensor, input2_tensor, 1.0, 127.5, 1.0)
         return off.reshape(-1, 4, 2)
 
@@ -189,6 +212,8 @@ class FlowHomoAdpater(nn.Module):
     # ------------------------------------------------------------------ eval @ fixed size (:83-191)
     def train_eval_foward(self, input1_tensor, input2_tensor, warm=None):
         branch = self.eval_branch()
+        if self.sources()[1] == "zero" and branch != "only_homo":
+            raise ValueError('flow_source="zero" leaves test_eval nothing to refine with: it is only accepted together with only_homo=True')
         dev = input1_tensor.device
         B, _, img_h, img_w = input1_tensor.shape
         motion = self.predict_homo(input1_tensor, input2_tensor)
@@ -233,8 +258,10 @@ class FlowHomoAdpater(nn.Module):
         """First part of test_out_forward (:204-266): both networks at 512x512, native-resolution DLT and the mesh bounds.
         No host synchronisation and a fixed launch sequence for a given input shape, so it can be replayed from a hipGraph
         (``GraphedTestOut``); everything it returns is a device tensor.  Without the consistency mask only the forward flow
-        is computed (one flow-network pass) and ``back`` is None."""
+        is computed (one flow-network pass) and ``back`` is None.  With flow_source="zero" no FlowFormer kernel is launched: the residual
+        is all zero and ``back`` is None, so the canvas part takes the blend without the consistency mask."""
         fb = self.test_out_branch() == "fb"
+        zero_flow = self.sources()[1] == "zero"
         dev = input1_tensor.device
         B, _, img_h, img_w = input1_tensor.shape
         if B != 1:
@@ -250,10 +277,13 @@ class FlowHomoAdpater(nn.Module):
         out_H = ops.homo_warp(b512, th.view(B, 9), (512, 512), n_ones=3)                               # :230
         warp2_512 = out_H[:, 0:3].contiguous()
         warp_mask_512 = ops.mean_threshold(out_H[:, 3:6].contiguous(), 0.5)                            # :233-234
-        flow512, back512 = self._flows(a512, warp2_512, fb, warm)                                      # :236 (and :326 in the same batch)
-        residual = ops.resize_bilinear(flow512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))  # :241
         back = None
-        if fb:
+        if zero_flow:
+            residual = torch.zeros((B, 2, img_h, img_w), device=dev)
+        else:
+            flow512, back512 = self._flows(a512, warp2_512, fb, warm)                                  # :236 (and :326 in the same batch)
+            residual = ops.resize_bilinear(flow512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))  # :241
+        if fb and not zero_flow:
             back = ops.resize_bilinear(back512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))
         H = torch.empty((B, 3, 3), device=dev)
         ops.dlt4(self._corners(dev, float(img_w), float(img_h)), motion, H, B, img_w / 512.0, img_h / 512.0, 1.0)  # :244-253
@@ -328,7 +358,7 @@ class GraphedTestOut:
         m = self.model
         if m.training:
             raise NotImplementedError("inference-only drop-in: call .eval() first")
-        key = (tuple(input1_tensor.shape), input1_tensor.device.index, m.test_out_branch())     # a cfg flip re-captures
+        key = (tuple(input1_tensor.shape), input1_tensor.device.index, m.test_out_branch(), m.sources())     # a cfg flip re-captures
         ent = self._graphs.get(key)
         gen = m.weights_generation()
         if ent is not None and ent[5] != gen:          # weights re-packed since the capture: the graph reads dead copies
@@ -378,7 +408,7 @@ class GraphedForward:
         self._graphs = {}
 
     def __call__(self, input1_tensor, input2_tensor):
-        key = (tuple(input1_tensor.shape), input1_tensor.device.index, self.model.eval_branch())   # a cfg flip re-captures
+        key = (tuple(input1_tensor.shape), input1_tensor.device.index, self.model.eval_branch(), self.model.sources())   # a cfg flip re-captures
         ent = self._graphs.get(key)
         if ent is not None and ent[5] != self.model.weights_generation():       # weights re-packed since the capture
             ent = None

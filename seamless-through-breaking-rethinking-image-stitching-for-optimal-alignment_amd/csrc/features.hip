@@ -1,0 +1,703 @@
+// feature_align: a weight-free alignment front end -- Harris corners, upright BRIEF-256, mutual nearest-neighbour matching, RANSAC
+// homography.  Contract in README.md, "feature_align"; CPU restatement tests/_features_ref.py.  gfx950 only.  Corners, descriptors and
+// matching are integers; the RANSAC is fp64 (this file is compiled with -ffp-contract=off: every product and sum below rounds on its own).
+// Every kernel of a call goes to the caller's stream, in order, inside the caller's buffers: no host synchronisation, no allocation, no
+// memset / memcpy, no atomics (every word has exactly one writer), and the launch count and every grid depend on B, H, W and max_hyp
+// alone, so a call captures into a hipGraph as a linear chain.  What depends on the data -- the number of keypoints, of matches, whether a
+// hypothesis is void -- is read on the device by the kernels it concerns.
+//
+//   ft_detect_kernel    one workgroup per 32x32 cell: luma tile (halo 5) -> Sobel (halo 4) -> Harris response (halo 1) in LDS, the 3x3
+//                       non-maximum suppression, the cell's best 4 corners, and the 5x5 box sum of the luma for the descriptor
+//   ft_describe_kernel  one thread per descriptor word: 32 comparisons of box sums
+//   ft_match_kernel     both directions: 1024 candidate descriptors at a time in LDS, one wave per query, (distance, slot) reduced over the wave
+//   ft_compact_kernel   ratio test, mutual check, the match list in slot order (one workgroup per item: scan)
+//   ft_norm_kernel      normalised fp64 coordinates of the matches
+//   ft_hyp_kernel       one thread per hypothesis: draw, 8x8 solve in LDS, score against the match list (1024 matches at a time in LDS)
+//   ft_refit_kernel     one workgroup per item: winner, inlier mask, two least-squares refits (four interleaved partial sums per entry), H / motion / info
+#include "common.h"
+
+#define FT_MIN_SIDE 64
+#define FT_MAX_SIDE 1024
+#define FT_MAX_BATCH 64
+#define FT_MAX_HYP 65536
+#define FT_CELL 32
+#define FT_PER_CELL 4
+#define FT_BORDER 16
+#define FT_WORDS 8
+#define FT_MAX_DIST 80                  // a match needs d1 < 80 of 256 bits ...
+#define FT_RATIO_NUM 8                  // ... and 10 d1 < 8 d2
+#define FT_RATIO_DEN 10
+#define FT_NO_DIST 257
+#define FT_MIN_MATCHES 8
+#define FT_PIVOT_MIN 1e-10
+#define FT_PATTERN_KEY 0x9E3779B9u
+#define FT_CHUNK 1024                   // candidates / matches staged in LDS at a time
+#define FT_THREADS 256
+
+__host__ __device__ constexpr uint32_t ft_fmix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x85EBCA6Bu;
+    x ^= x >> 13;
+    x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+
+// pair k compares the box sums at p + (v[4k], v[4k+1]) and p + (v[4k+2], v[4k+3]) (x, y); every offset in -12..12
+struct ft_pattern_t {
+    int8_t v[1024];
+};
+constexpr ft_pattern_t ft_make_pattern() {
+    ft_pattern_t p{};
+    for (int i = 0; i < 1024; ++i) p.v[i] = (int8_t)((int)(ft_fmix32(FT_PATTERN_KEY ^ (uint32_t)i) % 25u) - 12);
+    return p;
+}
+static constexpr ft_pattern_t ft_pattern_host = ft_make_pattern();
+__constant__ ft_pattern_t ft_pattern = ft_make_pattern();
+
+// the saver's pixel: trunc(clamp(x, 0, 255)); NaN and -Inf read 0, +Inf 255
+__device__ __forceinline__ int ft_pixel(float v) { return (int)fminf(fmaxf(v, 0.f), 255.f); }
+
+__device__ __forceinline__ long long ft_shfl_xor64(long long v, int o) {
+    const int lo = __shfl_xor((int)(v & 0xFFFFFFFFll), o, 64), hi = __shfl_xor((int)(v >> 32), o, 64);
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+// (R descending, index ascending)
+__device__ __forceinline__ bool ft_better(long long ra, int ia, long long rb, int ib) { return ra > rb || (ra == rb && ia < ib); }
+
+__global__ void __launch_bounds__(FT_THREADS) ft_detect_kernel(const float* __restrict__ img1, const float* __restrict__ img2, int B, int H, int W,
+                                                                int32_t* __restrict__ kp, uint16_t* __restrict__ box) {
+    __shared__ uint8_t sy[42][44];
+    __shared__ int16_t sgx[40][40], sgy[40][40];
+    __shared__ long long sr[34][34];
+    __shared__ long long wr[4];
+    __shared__ int wi[4];
+    const int t = threadIdx.x, z = blockIdx.z, CW = gridDim.x, N = FT_PER_CELL * gridDim.x * gridDim.y;
+    const int x0 = blockIdx.x * FT_CELL, y0 = blockIdx.y * FT_CELL;
+    const size_t hw = (size_t)H * W;
+    const float* img = (z < B ? img1 + (size_t)z * 3 * hw : img2 + (size_t)(z - B) * 3 * hw);
+    for (int e = t; e < 42 * 42; e += FT_THREADS) {
+        const int ty = e / 42, tx = e - ty * 42;
+        const int y = min(max(y0 - 5 + ty, 0), H - 1), x = min(max(x0 - 5 + tx, 0), W - 1);
+        const size_t g = (size_t)y * W + x;
+        const int r = ft_pixel(img[g]), gg = ft_pixel(img[hw + g]), b = ft_pixel(img[2 * hw + g]);
+        sy[ty][tx] = (uint8_t)((19595 * r + 38470 * gg + 7471 * b + 0x8000) >> 16);
+    }
+    __syncthreads();
+    for (int e = t; e < 40 * 40; e += FT_THREADS) {
+        const int ty = e / 40, tx = e - ty * 40;
+        const int y = y0 - 4 + ty, x = x0 - 4 + tx;
+        int gx = 0, gy = 0;
+        if (y >= 0 && y < H && x >= 0 && x < W) {
+            const int a = sy[ty][tx], b = sy[ty][tx + 1], c = sy[ty][tx + 2], d = sy[ty + 1][tx], f = sy[ty + 1][tx + 2], g = sy[ty + 2][tx], h = sy[ty + 2][tx + 1],
+                      i = sy[ty + 2][tx + 2];
+            gx = (c + 2 * f + i) - (a + 2 * d + g);
+            gy = (g + 2 * h + i) - (a + 2 * b + c);
+        }
+        sgx[ty][tx] = (int16_t)gx, sgy[ty][tx] = (int16_t)gy;
+    }
+    __syncthreads();
+    for (int e = t; e < 34 * 34; e += FT_THREADS) {
+        const int ty = e / 34, tx = e - ty * 34;
+        int a = 0, b = 0, c = 0;
+        for (int dy = 0; dy < 7; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 7; ++dx) {
+                const int gx = sgx[ty + dy][tx + dx], gy = sgy[ty + dy][tx + dx];
+                a += gx * gx, b += gy * gy, c += gx * gy;
+            }
+        const long long A = a, Bq = b, Cq = c;
+        sr[ty][tx] = 16 * (A * Bq - Cq * Cq) - (A + Bq) * (A + Bq);
+    }
+    __syncthreads();
+    long long cr[4];
+    int ci[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int p = t + FT_THREADS * j, py = p >> 5, px = p & 31, y = y0 + py, x = x0 + px;
+        cr[j] = 0, ci[j] = 0x7FFFFFFF;
+        if (y < H && x < W) {
+            int s = 0;                                       // 5x5 box sum of the luma, terms outside the image 0
+            for (int dy = -2; dy <= 2; ++dy)
+                for (int dx = -2; dx <= 2; ++dx)
+                    if (y + dy >= 0 && y + dy < H && x + dx >= 0 && x + dx < W) s += sy[py + 5 + dy][px + 5 + dx];
+            box[(size_t)z * hw + (size_t)y * W + x] = (uint16_t)s;
+            if (y >= FT_BORDER && y < H - FT_BORDER && x >= FT_BORDER && x < W - FT_BORDER) {
+                const long long r = sr[py + 1][px + 1];
+                bool ok = r > 0;
+#pragma unroll
+                for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        if (!dy && !dx) continue;
+                        const long long q = sr[py + 1 + dy][px + 1 + dx];
+                        ok = ok && ((dy < 0 || (dy == 0 && dx < 0)) ? r > q : r >= q);
+                    }
+                if (ok) cr[j] = r, ci[j] = y * W + x;
+            }
+        }
+    }
+    const int cell = blockIdx.y * CW + blockIdx.x;
+    for (int rank = 0; rank < FT_PER_CELL; ++rank) {
+        long long br = 0;
+        int bi = 0x7FFFFFFF;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (ft_better(cr[j], ci[j], br, bi)) br = cr[j], bi = ci[j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const long long qr = ft_shfl_xor64(br, o);
+            const int qi = __shfl_xor(bi, o, 64);
+            if (ft_better(qr, qi, br, bi)) br = qr, bi = qi;
+        }
+        if ((t & 63) == 0) wr[t >> 6] = br, wi[t >> 6] = bi;
+        __syncthreads();
+        br = wr[0], bi = wi[0];
+#pragma unroll
+        for (int v = 1; v < 4; ++v)
+            if (ft_better(wr[v], wi[v], br, bi)) br = wr[v], bi = wi[v];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (ci[j] == bi) cr[j] = 0, ci[j] = 0x7FFFFFFF;     // taken (no candidate has the index of "none")
+        if (t == 0) {
+            int32_t* o = kp + ((size_t)z * N + FT_PER_CELL * cell + rank) * 2;
+            o[0] = br > 0 ? bi % W : -1, o[1] = br > 0 ? bi / W : -1;
+        }
+    }
+}
+
+// n2 = number of (item, image) planes; box uint16 [n2, H, W], kp int32 [n2, N, 2] (x, y), desc uint32 [n2, N, 8]
+__global__ void __launch_bounds__(FT_THREADS) ft_describe_kernel(const uint16_t* __restrict__ box, const int32_t* __restrict__ kp, int H, int W, int N,
+                                                                  uint32_t* __restrict__ desc) {
+    const int g = blockIdx.x * FT_THREADS + threadIdx.x, z = blockIdx.y;
+    if (g >= N * FT_WORDS) return;
+    const int slot = g >> 3, word = g & 7;
+    const int x = kp[((size_t)z * N + slot) * 2], y = kp[((size_t)z * N + slot) * 2 + 1];
+    uint32_t bits = 0;
+    if (x >= FT_BORDER && x < W - FT_BORDER && y >= FT_BORDER && y < H - FT_BORDER) {          // (a valid slot always is; anything else reads nothing)
+        const uint16_t* s = box + (size_t)z * H * W;
+        for (int b = 0; b < 32; ++b) {
+            const int8_t* o = ft_pattern.v + 4 * (word * 32 + b);
+            const uint32_t sa = s[(y + o[1]) * W + x + o[0]], sb = s[(y + o[3]) * W + x + o[2]];
+            bits |= (uint32_t)(sa < sb) << b;
+        }
+    }
+    desc[((size_t)z * N + slot) * FT_WORDS + word] = bits;
+}
+
+// nn int32 [2, B, N, 3]: direction 0 = every slot of image 1 against image 2, direction 1 the reverse; (best slot or -1, d1, d2), 257 = none
+__global__ void __launch_bounds__(FT_THREADS) ft_match_kernel(const int32_t* __restrict__ kp1, const uint32_t* __restrict__ desc1, const int32_t* __restrict__ kp2,
+                                                               const uint32_t* __restrict__ desc2, int B, int N, int32_t* __restrict__ nn) {
+    __shared__ uint32_t cd[FT_WORDS][FT_CHUNK];
+    __shared__ uint8_t cv[FT_CHUNK];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, dir = blockIdx.y, b = blockIdx.z;
+    const int32_t* kq = (dir ? kp2 : kp1) + (size_t)b * N * 2;
+    const int32_t* kc = (dir ? kp1 : kp2) + (size_t)b * N * 2;
+    const uint32_t* dq = (dir ? desc2 : desc1) + (size_t)b * N * FT_WORDS;
+    const uint32_t* dc = (dir ? desc1 : desc2) + (size_t)b * N * FT_WORDS;
+    const int q0 = blockIdx.x * 32 + wave * 8;
+    uint32_t key[8], sec[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) key[u] = 0xFFFFFFFFu, sec[u] = FT_NO_DIST;
+    for (int c0 = 0; c0 < N; c0 += FT_CHUNK) {
+        __syncthreads();
+        for (int e = t; e < FT_CHUNK; e += FT_THREADS) {
+            const int j = c0 + e;
+            const bool ok = j < N && kc[2 * j] >= 0;
+            cv[e] = ok;
+#pragma unroll
+            for (int w = 0; w < FT_WORDS; ++w) cd[w][e] = ok ? dc[(size_t)j * FT_WORDS + w] : 0u;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int qi = q0 + u;
+            if (qi >= N || kq[2 * qi] < 0) continue;             // wave-uniform
+            uint32_t q[FT_WORDS];
+#pragma unroll
+            for (int w = 0; w < FT_WORDS; ++w) q[w] = dq[(size_t)qi * FT_WORDS + w];
+            for (int e = lane; e < FT_CHUNK; e += 64) {
+                if (!cv[e]) continue;
+                uint32_t d = 0;
+#pragma unroll
+                for (int w = 0; w < FT_WORDS; ++w) d += __popc(q[w] ^ cd[w][e]);
+                const uint32_t k2 = d << 16 | (uint32_t)(c0 + e);
+                if (k2 < key[u]) sec[u] = min(sec[u], key[u] >> 16), key[u] = k2;
+                else sec[u] = min(sec[u], d);
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int qi = q0 + u;
+        if (qi >= N) continue;
+        uint32_t k = key[u], s = sec[u];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t ok = (uint32_t)__shfl_xor((int)k, o, 64), os = (uint32_t)__shfl_xor((int)s, o, 64);
+            s = min(min(s, os), max(k, ok) >> 16);              // the loser's best is a runner-up (65535 when it has none)
+            k = min(k, ok);
+        }
+        if (lane == 0) {
+            int32_t* o = nn + (((size_t)dir * B + b) * N + qi) * 3;
+            const bool none = k == 0xFFFFFFFFu;
+            o[0] = none ? -1 : (int32_t)(k & 0xFFFF), o[1] = none ? FT_NO_DIST : (int32_t)(k >> 16), o[2] = (int32_t)s;
+        }
+    }
+}
+
+// matches int32 [B, N, 2]: (slot of image 1, slot of image 2) in slot order of image 1, (-1, -1) behind the last; count int32 [B]
+__global__ void __launch_bounds__(1024) ft_compact_kernel(const int32_t* __restrict__ nn, int B, int N, int32_t* __restrict__ matches, int32_t* __restrict__ count) {
+    __shared__ int ws[16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = blockIdx.x;
+    const int per = (N + 1023) / 1024, i0 = min(t * per, N), i1 = min(i0 + per, N);
+    const int32_t* f = nn + (size_t)b * N * 3;
+    const int32_t* r = nn + ((size_t)B + b) * N * 3;
+    uint32_t flags = 0;
+    int c = 0;
+    for (int i = i0; i < i1; ++i) {
+        const int j = f[3 * i], d1 = f[3 * i + 1], d2 = f[3 * i + 2];
+        if (j >= 0 && j < N && d1 < FT_MAX_DIST && FT_RATIO_DEN * d1 < FT_RATIO_NUM * d2 && r[3 * j] == i) flags |= 1u << (i - i0), ++c;
+    }
+    int inc = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    if (lane == 63) ws[wave] = inc;
+    __syncthreads();
+    int at = inc - c, m = 0;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        if (v < wave) at += ws[v];
+        m += ws[v];
+    }
+    int32_t* o = matches + (size_t)b * N * 2;
+    for (int i = i0; i < i1; ++i)
+        if (flags >> (i - i0) & 1) o[2 * at] = i, o[2 * at + 1] = f[3 * i], ++at;
+    for (int p = m + t; p < N; p += 1024) o[2 * p] = -1, o[2 * p + 1] = -1;
+    if (t == 0) count[b] = m;
+}
+
+__device__ __forceinline__ int ft_count(const int32_t* __restrict__ count, int b, int N) { return min(max(count[b], 0), N); }
+
+// mc fp64 [B, N, 4]: (x1, y1, x2, y2) of list entry p, normalised as (x - W/2) / (W/2), (y - H/2) / (H/2)
+__global__ void __launch_bounds__(FT_THREADS) ft_norm_kernel(const int32_t* __restrict__ kp1, const int32_t* __restrict__ kp2, const int32_t* __restrict__ matches,
+                                                              const int32_t* __restrict__ count, int H, int W, int N, double* __restrict__ mc) {
+    const int p = blockIdx.x * FT_THREADS + threadIdx.x, b = blockIdx.y;
+    if (p >= ft_count(count, b, N)) return;
+    const int i = min(max(matches[((size_t)b * N + p) * 2], 0), N - 1), j = min(max(matches[((size_t)b * N + p) * 2 + 1], 0), N - 1);
+    const double sx = 0.5 * W, sy = 0.5 * H;
+    double* o = mc + ((size_t)b * N + p) * 4;
+    o[0] = ((double)kp1[((size_t)b * N + i) * 2] - sx) / sx;
+    o[1] = ((double)kp1[((size_t)b * N + i) * 2 + 1] - sy) / sy;
+    o[2] = ((double)kp2[((size_t)b * N + j) * 2] - sx) / sx;
+    o[3] = ((double)kp2[((size_t)b * N + j) * 2 + 1] - sy) / sy;
+}
+
+// element `c` (0..8; 8 = right-hand side) of the two rows a match (x, y) -> (u, v) contributes to the system of h (h33 = 1)
+__device__ __forceinline__ double ft_row0(int c, double x, double y, double u) {
+    switch (c) {
+        case 0: return x;
+        case 1: return y;
+        case 2: return 1.0;
+        case 6: return -u * x;
+        case 7: return -u * y;
+        case 8: return u;
+        default: return 0.0;
+    }
+}
+__device__ __forceinline__ double ft_row1(int c, double x, double y, double v) {
+    switch (c) {
+        case 3: return x;
+        case 4: return y;
+        case 5: return 1.0;
+        case 6: return -v * x;
+        case 7: return -v * y;
+        case 8: return v;
+        default: return 0.0;
+    }
+}
+
+// Gaussian elimination with partial pivoting (first row on ties) of the 8 x 9 system at a[(r * 9 + c) * S]; a pivot below FT_PIVOT_MIN
+// (or a NaN) voids it
+template <int S>
+__device__ __forceinline__ bool ft_solve8(double* __restrict__ a, double (&x)[8]) {
+    for (int c = 0; c < 8; ++c) {
+        int piv = c;
+        double best = fabs(a[(c * 9 + c) * S]);
+        for (int r = c + 1; r < 8; ++r) {
+            const double v = fabs(a[(r * 9 + c) * S]);
+            if (v > best) best = v, piv = r;
+        }
+        if (!(best >= FT_PIVOT_MIN)) return false;
+        if (piv != c)
+            for (int k = 0; k < 9; ++k) {
+                const double tmp = a[(c * 9 + k) * S];
+                a[(c * 9 + k) * S] = a[(piv * 9 + k) * S];
+                a[(piv * 9 + k) * S] = tmp;
+            }
+        const double pv = a[(c * 9 + c) * S];
+        for (int r = c + 1; r < 8; ++r) {
+            const double f = a[(r * 9 + c) * S] / pv;
+            for (int k = c + 1; k < 9; ++k) a[(r * 9 + k) * S] = a[(r * 9 + k) * S] - f * a[(c * 9 + k) * S];
+        }
+    }
+#pragma unroll
+    for (int r = 7; r >= 0; --r) {
+        double s = a[(r * 9 + 8) * S];
+#pragma unroll
+        for (int k = r + 1; k < 8; ++k) s = s - a[(r * 9 + k) * S] * x[k];
+        x[r] = s / a[(r * 9 + r) * S];
+    }
+    return true;
+}
+
+// hypothesis k of an item with m >= 8 matches: four draws, void on a repeat; the 4-point system into a[(.) * S]; solved into h
+template <int S>
+__device__ __forceinline__ bool ft_hypothesis(const double* __restrict__ mc, int m, uint32_t seed, int k, double* __restrict__ a, double (&h)[8]) {
+    const uint32_t key = ft_fmix32(seed ^ ft_fmix32((uint32_t)k));
+    int idx[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) idx[t] = (int)(ft_fmix32(key ^ (uint32_t)(t + 1)) % (uint32_t)m);
+    if (idx[0] == idx[1] || idx[0] == idx[2] || idx[0] == idx[3] || idx[1] == idx[2] || idx[1] == idx[3] || idx[2] == idx[3]) return false;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const double x = mc[4 * idx[t]], y = mc[4 * idx[t] + 1], u = mc[4 * idx[t] + 2], v = mc[4 * idx[t] + 3];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) a[((2 * t) * 9 + c) * S] = ft_row0(c, x, y, u), a[((2 * t + 1) * 9 + c) * S] = ft_row1(c, x, y, v);
+    }
+    return ft_solve8<S>(a, h);
+}
+
+// a positive denominator and a squared one-sided reprojection error, in pixels, below thr^2
+__device__ __forceinline__ bool ft_inlier(const double (&h)[8], double x, double y, double u, double v, double sx, double sy, double thr2) {
+    const double den = (h[6] * x + h[7] * y) + 1.0;
+    if (!(den > 0.0)) return false;
+    const double px = ((h[0] * x + h[1] * y) + h[2]) / den, py = ((h[3] * x + h[4] * y) + h[5]) / den;
+    const double ex = (px - u) * sx, ey = (py - v) * sy;
+    return ex * ex + ey * ey < thr2;
+}
+
+// scores int32 [B, max_hyp]: inliers of hypothesis k, -1 when it is void (all of them with fewer than 8 matches)
+__global__ void __launch_bounds__(64) ft_hyp_kernel(const double* __restrict__ mc, const int32_t* __restrict__ count, int H, int W, int N, int max_hyp, uint32_t seed,
+                                                     double thr2, int32_t* __restrict__ scores) {
+    __shared__ double sa[72 * 64];                           // the 8 x 9 systems, one column per thread; then 1024 matches at a time
+    const int t = threadIdx.x, b = blockIdx.y, k = blockIdx.x * 64 + t, m = ft_count(count, b, N);
+    const double* mb = mc + (size_t)b * N * 4;
+    double h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool ok = false;
+    if (k < max_hyp && m >= FT_MIN_MATCHES) ok = ft_hypothesis<64>(mb, m, seed, k, sa + t, h);
+    const double sx = 0.5 * W, sy = 0.5 * H;
+    int score = 0;
+    for (int c0 = 0; c0 < m; c0 += FT_CHUNK) {
+        const int n = min(FT_CHUNK, m - c0);
+        __syncthreads();
+        for (int e = t; e < 4 * n; e += 64) sa[e] = mb[4 * (size_t)c0 + e];
+        __syncthreads();
+        if (ok)
+            for (int e = 0; e < n; ++e) score += ft_inlier(h, sa[4 * e], sa[4 * e + 1], sa[4 * e + 2], sa[4 * e + 3], sx, sy, thr2);
+    }
+    if (k < max_hyp) scores[(size_t)b * max_hyp + k] = ok ? score : -1;
+}
+
+__device__ __forceinline__ int ft_block_sum(int v, int* part) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return part[0] + part[1] + part[2] + part[3];
+}
+__device__ __forceinline__ int ft_block_max(int v, int* part) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return max(max(part[0], part[1]), max(part[2], part[3]));
+}
+
+__global__ void __launch_bounds__(FT_THREADS) ft_refit_kernel(const int32_t* __restrict__ kp1, const int32_t* __restrict__ kp2, const double* __restrict__ mc,
+                                                               const int32_t* __restrict__ count, const int32_t* __restrict__ scores, int H, int W, int N, int max_hyp,
+                                                               uint32_t seed, double thr2, int min_inliers, float* __restrict__ motion, float* __restrict__ Hout,
+                                                               int32_t* __restrict__ info, uint8_t* __restrict__ mask) {
+    __shared__ uint8_t sm[4 * FT_CHUNK];                     // inlier flag of every list entry (N <= 4096)
+    __shared__ double sa[72], sh[8], sp[4][44], smc[4 * FT_CHUNK];
+    __shared__ int part[4], s_have;
+    const int t = threadIdx.x, b = blockIdx.x, m = ft_count(count, b, N);
+    const double* mb = mc + (size_t)b * N * 4;
+    const double sx = 0.5 * W, sy = 0.5 * H;
+    int n1 = 0, n2 = 0, best = -1;
+    for (int i = t; i < N; i += FT_THREADS) n1 += kp1[((size_t)b * N + i) * 2] >= 0, n2 += kp2[((size_t)b * N + i) * 2] >= 0;
+    n1 = ft_block_sum(n1, part), n2 = ft_block_sum(n2, part);
+    // the winner: the highest score, ties to the lowest k
+    for (int k = t; k < max_hyp; k += FT_THREADS) {
+        const int s = scores[(size_t)b * max_hyp + k];
+        if (s >= 0) best = max(best, s * 65536 + (65535 - k));
+    }
+    best = ft_block_max(best, part);
+    const int winner = m >= FT_MIN_MATCHES && best >= 0 ? 65535 - (best & 65535) : -1;
+    if (t == 0) {
+        double h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const bool ok = winner >= 0 && ft_hypothesis<1>(mb, m, seed, winner, sa, h);
+        s_have = ok;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) sh[c] = h[c];
+    }
+    __syncthreads();
+    const bool have = s_have;
+    int inliers = 0;
+    for (int round = 0; round <= 2; ++round) {
+        if (round && have) {                                 // a refit over the current inliers
+            // 36 entries of the upper triangle of A^T A, then the 8 of A^T b.  An entry is (s0 + s1) + (s2 + s3), s_q the sum over the inliers at
+            // list positions p = q mod 4 in list order: thread 44 q + e sums s_q of entry e, the matches 1024 at a time in LDS
+            const int e = t % 44, q = t / 44;
+            int r = 0, c = e;
+            if (e >= 36) r = e - 36, c = 8;
+            else
+                while (c >= 8 - r) c -= 8 - r, ++r;
+            if (e < 36) c += r;
+            double acc = 0.0;
+            for (int c0 = 0; c0 < m; c0 += FT_CHUNK) {
+                const int n = min(FT_CHUNK, m - c0);
+                __syncthreads();
+                for (int i = t; i < 4 * n; i += FT_THREADS) smc[i] = mb[4 * (size_t)c0 + i];
+                __syncthreads();
+                if (q < 4)
+                    for (int p = q; p < n; p += 4) {
+                        if (!sm[c0 + p]) continue;
+                        const double x = smc[4 * p], y = smc[4 * p + 1], u = smc[4 * p + 2], v = smc[4 * p + 3];
+                        acc = acc + ft_row0(r, x, y, u) * ft_row0(c, x, y, u);
+                        acc = acc + ft_row1(r, x, y, v) * ft_row1(c, x, y, v);
+                    }
+            }
+            if (q < 4) sp[q][e] = acc;
+            __syncthreads();
+            if (t < 44) {
+                const double total = (sp[0][e] + sp[1][e]) + (sp[2][e] + sp[3][e]);
+                sa[r * 9 + c] = total;
+                if (c < 8) sa[c * 9 + r] = total;
+            }
+            __syncthreads();
+            if (t == 0) {
+                double h[8];
+                if (ft_solve8<1>(sa, h))                     // singular: the previous H stays
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) sh[c] = h[c];
+            }
+            __syncthreads();
+        }
+        double h[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) h[c] = sh[c];
+        int n = 0;
+        for (int p = t; p < m; p += FT_THREADS) {
+            const bool in = have && ft_inlier(h, mb[4 * p], mb[4 * p + 1], mb[4 * p + 2], mb[4 * p + 3], sx, sy, thr2);
+            sm[p] = in, n += in;
+        }
+        inliers = ft_block_sum(n, part);                     // (its barriers also order sm and sa between the rounds)
+    }
+    for (int p = t; p < N; p += FT_THREADS) mask[(size_t)b * N + p] = p < m ? sm[p] : 0;
+    if (t == 0) {
+        double h[9];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) h[c] = sh[c];
+        h[8] = 1.0;
+        // pixel units: D Hn Nm with Nm = [[1/sx, 0, -1], [0, 1/sy, -1], [0, 0, 1]], D = [[sx, 0, sx], [0, sy, sy], [0, 0, 1]]
+        double M[9], P[9];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) M[3 * r] = h[3 * r] / sx, M[3 * r + 1] = h[3 * r + 1] / sy, M[3 * r + 2] = (h[3 * r + 2] - h[3 * r]) - h[3 * r + 1];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) P[c] = sx * M[c] + sx * M[6 + c], P[3 + c] = sy * M[3 + c] + sy * M[6 + c], P[6 + c] = M[6 + c];
+        float Hf[9], mo[8];
+        bool fin = true;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) Hf[c] = c == 8 ? 1.f : (float)(P[c] / P[8]), fin = fin && isfinite(Hf[c]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                        // the corners (0,0), (W,0), (0,H), (W,H): -1 / +1 in normalised units
+            const double xn = q & 1 ? 1.0 : -1.0, yn = q & 2 ? 1.0 : -1.0, cx = q & 1 ? (double)W : 0.0, cy = q & 2 ? (double)H : 0.0;
+            const double den = (h[6] * xn + h[7] * yn) + 1.0;
+            const double ux = ((h[0] * xn + h[1] * yn) + h[2]) / den, uy = ((h[3] * xn + h[4] * yn) + h[5]) / den;
+            mo[2 * q] = (float)((ux * sx + sx) - cx), mo[2 * q + 1] = (float)((uy * sy + sy) - cy);
+            fin = fin && isfinite(mo[2 * q]) && isfinite(mo[2 * q + 1]);
+        }
+        const bool valid = have && fin && inliers >= min_inliers;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) Hout[(size_t)b * 9 + c] = valid ? Hf[c] : (c % 4 == 0 ? 1.f : 0.f);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) motion[(size_t)b * 8 + c] = valid ? mo[c] : 0.f;
+        int32_t* o = info + (size_t)b * 8;
+        o[0] = valid, o[1] = n1, o[2] = n2, o[3] = m, o[4] = have ? winner : -1, o[5] = inliers, o[6] = 0, o[7] = 0;
+    }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------
+struct ft_region {
+    const void* p;
+    int64_t bytes;
+    bool out;
+};
+
+// no null pointer; an output overlaps nothing
+static bool ft_regions_ok(const ft_region* r, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!r[i].p) return false;
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n; ++j) {
+            if (!r[i].out && !r[j].out) continue;
+            const uintptr_t a = (uintptr_t)r[i].p, b = (uintptr_t)r[j].p;
+            if (a < b + (uintptr_t)r[j].bytes && b < a + (uintptr_t)r[i].bytes) return false;
+        }
+    return true;
+}
+
+static bool ft_shape_ok(int B, int H, int W) {
+    return B >= 1 && B <= FT_MAX_BATCH && H >= FT_MIN_SIDE && H <= FT_MAX_SIDE && W >= FT_MIN_SIDE && W <= FT_MAX_SIDE;
+}
+static int ft_cells(int side) { return (side + FT_CELL - 1) / FT_CELL; }
+static int ft_slots(int H, int W) { return FT_PER_CELL * ft_cells(H) * ft_cells(W); }
+
+// workspace of st_feature_homography, every region rounded up to 16 bytes: box uint16 [2,B,H,W]; kp int32 [2,B,N,2]; desc uint32 [2,B,N,8];
+// nn int32 [2,B,N,3]; matches int32 [B,N,2]; count int32 [B]; mc fp64 [B,N,4]; scores int32 [B,max_hyp]; mask uint8 [B,N]
+struct ft_layout {
+    int N;
+    int64_t box, kp, desc, nn, matches, count, mc, scores, mask, total;
+};
+static bool ft_plan(int B, int H, int W, int max_hyp, ft_layout& L) {
+    if (!ft_shape_ok(B, H, W) || max_hyp < 1 || max_hyp > FT_MAX_HYP) return false;
+    int64_t at = 0;
+    auto take = [&](int64_t bytes) { const int64_t o = at; at += (bytes + 15) & ~(int64_t)15; return o; };
+    const int64_t N = L.N = ft_slots(H, W), b = B;
+    L.box = take(2 * 2 * b * H * W), L.kp = take(4 * 2 * b * N * 2), L.desc = take(4 * 2 * b * N * 8), L.nn = take(4 * 2 * b * N * 3);
+    L.matches = take(4 * b * N * 2), L.count = take(4 * b), L.mc = take(8 * b * N * 4), L.scores = take(4 * b * max_hyp), L.mask = take(b * N);
+    L.total = at;
+    return true;
+}
+
+static int ft_launch_detect(const float* img1, const float* img2, int B, int nimg, int H, int W, int32_t* kp, uint16_t* box, hipStream_t s) {
+    ft_detect_kernel<<<dim3(ft_cells(W), ft_cells(H), nimg * B), FT_THREADS, 0, s>>>(img1, img2, B, H, W, kp, box);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}
+static int ft_launch_describe(const uint16_t* box, const int32_t* kp, int n2, int H, int W, uint32_t* desc, hipStream_t s) {
+    const int N = ft_slots(H, W);
+    ft_describe_kernel<<<dim3((N * FT_WORDS + FT_THREADS - 1) / FT_THREADS, n2), FT_THREADS, 0, s>>>(box, kp, H, W, N, desc);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}
+static int ft_launch_match(const int32_t* kp1, const uint32_t* desc1, const int32_t* kp2, const uint32_t* desc2, int B, int N, int32_t* nn, int32_t* matches,
+                           int32_t* count, hipStream_t s) {
+    ft_match_kernel<<<dim3((N + 31) / 32, 2, B), FT_THREADS, 0, s>>>(kp1, desc1, kp2, desc2, B, N, nn);
+    ST_CHECK_LAUNCH();
+    ft_compact_kernel<<<B, 1024, 0, s>>>(nn, B, N, matches, count);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}
+static int ft_launch_ransac(const int32_t* kp1, const int32_t* kp2, const int32_t* matches, const int32_t* count, int B, int H, int W, int max_hyp, double thr,
+                            int min_inliers, uint32_t seed, double* mc, int32_t* scores, float* motion, float* Hout, int32_t* info, uint8_t* mask, hipStream_t s) {
+    const int N = ft_slots(H, W);
+    const double thr2 = thr * thr;
+    ft_norm_kernel<<<dim3((N + FT_THREADS - 1) / FT_THREADS, B), FT_THREADS, 0, s>>>(kp1, kp2, matches, count, H, W, N, mc);
+    ST_CHECK_LAUNCH();
+    ft_hyp_kernel<<<dim3((max_hyp + 63) / 64, B), 64, 0, s>>>(mc, count, H, W, N, max_hyp, seed, thr2, scores);
+    ST_CHECK_LAUNCH();
+    ft_refit_kernel<<<B, FT_THREADS, 0, s>>>(kp1, kp2, mc, count, scores, H, W, N, max_hyp, seed, thr2, min_inliers, motion, Hout, info, mask);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}
+
+static bool ft_params_ok(int max_hyp, double thr, int min_inliers) {
+    return max_hyp >= 1 && max_hyp <= FT_MAX_HYP && thr > 0.0 && thr <= 1.7e308 && min_inliers >= 0;       // (a NaN thr fails both comparisons)
+}
+
+extern "C" int st_feature_slots(int32_t H, int32_t W) { return ft_shape_ok(1, H, W) ? ft_slots(H, W) : 0; }
+
+extern "C" int st_feature_brief_pattern(int8_t* out_host) {
+    if (!out_host) return ST_EINVAL;
+    for (int i = 0; i < 1024; ++i) out_host[i] = ft_pattern_host.v[i];
+    return ST_OK;
+}
+
+extern "C" int st_feature_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t max_hyp) {
+    ft_layout L;
+    return ft_plan(B, H, W, max_hyp, L) ? (int)L.total : 0;
+}
+
+extern "C" int st_feature_workspace_layout(int32_t B, int32_t H, int32_t W, int32_t max_hyp, int64_t* offsets_host) {
+    ft_layout L;
+    if (!offsets_host || !ft_plan(B, H, W, max_hyp, L)) return ST_EINVAL;
+    const int64_t o[10] = {L.box, L.kp, L.desc, L.nn, L.matches, L.count, L.mc, L.scores, L.mask, L.total};
+    for (int i = 0; i < 10; ++i) offsets_host[i] = o[i];
+    return ST_OK;
+}
+
+extern "C" int st_feature_detect(const float* img, int32_t B, int32_t H, int32_t W, int32_t* kp_out, uint16_t* box_out, void* stream) {
+    if (!ft_shape_ok(B, H, W)) return ST_EINVAL;
+    const int64_t px = (int64_t)B * H * W, N = ft_slots(H, W);
+    const ft_region r[3] = {{img, 12 * px, false}, {kp_out, 8 * B * N, true}, {box_out, 2 * px, true}};
+    if (!ft_regions_ok(r, 3)) return ST_EINVAL;
+    return ft_launch_detect(img, img, B, 1, H, W, kp_out, box_out, (hipStream_t)stream);
+}
+
+extern "C" int st_feature_describe(const uint16_t* box, const int32_t* kp, int32_t B, int32_t H, int32_t W, uint32_t* desc_out, void* stream) {
+    if (!ft_shape_ok(B, H, W)) return ST_EINVAL;
+    const int64_t px = (int64_t)B * H * W, N = ft_slots(H, W);
+    const ft_region r[3] = {{box, 2 * px, false}, {kp, 8 * B * N, false}, {desc_out, 32 * B * N, true}};
+    if (!ft_regions_ok(r, 3)) return ST_EINVAL;
+    return ft_launch_describe(box, kp, B, H, W, desc_out, (hipStream_t)stream);
+}
+
+extern "C" int st_feature_match(const int32_t* kp1, const uint32_t* desc1, const int32_t* kp2, const uint32_t* desc2, int32_t B, int32_t H, int32_t W, int32_t* nn_out,
+                                int32_t* matches_out, int32_t* count_out, void* stream) {
+    if (!ft_shape_ok(B, H, W)) return ST_EINVAL;
+    const int64_t N = ft_slots(H, W), bn = (int64_t)B * N;
+    const ft_region r[7] = {{kp1, 8 * bn, false}, {desc1, 32 * bn, false}, {kp2, 8 * bn, false}, {desc2, 32 * bn, false},
+                            {nn_out, 24 * bn, true}, {matches_out, 8 * bn, true}, {count_out, 4 * B, true}};
+    if (!ft_regions_ok(r, 7)) return ST_EINVAL;
+    return ft_launch_match(kp1, desc1, kp2, desc2, B, (int)N, nn_out, matches_out, count_out, (hipStream_t)stream);
+}
+
+// workspace: mc fp64 [B,N,4] then scores int32 [B,max_hyp] = 32 B N + 4 B max_hyp bytes
+extern "C" int st_feature_ransac(const int32_t* kp1, const int32_t* kp2, const int32_t* matches, const int32_t* count, int32_t B, int32_t H, int32_t W, int32_t max_hyp,
+                                 double thr, int32_t min_inliers, int32_t seed, float* motion_out, float* H_out, int32_t* info_out, uint8_t* mask_out, void* workspace,
+                                 int64_t workspace_bytes, void* stream) {
+    if (!ft_shape_ok(B, H, W) || !ft_params_ok(max_hyp, thr, min_inliers)) return ST_EINVAL;
+    const int64_t N = ft_slots(H, W), bn = (int64_t)B * N, need = 32 * bn + 4 * (int64_t)B * max_hyp;
+    if (workspace_bytes < need || ((uintptr_t)workspace & 15)) return ST_EINVAL;
+    const ft_region r[9] = {{kp1, 8 * bn, false}, {kp2, 8 * bn, false}, {matches, 8 * bn, false}, {count, 4 * B, false}, {motion_out, 32 * B, true},
+                            {H_out, 36 * B, true}, {info_out, 32 * B, true}, {mask_out, bn, true}, {workspace, need, true}};
+    if (!ft_regions_ok(r, 9)) return ST_EINVAL;
+    double* mc = (double*)workspace;
+    return ft_launch_ransac(kp1, kp2, matches, count, B, H, W, max_hyp, thr, min_inliers, (uint32_t)seed, mc, (int32_t*)((char*)workspace + 32 * bn), motion_out, H_out,
+                            info_out, mask_out, (hipStream_t)stream);
+}
+
+extern "C" int st_feature_homography(const float* img1, const float* img2, int32_t B, int32_t H, int32_t W, int32_t max_hyp, double thr, int32_t min_inliers,
+                                     int32_t seed, float* motion_out, float* H_out, int32_t* info_out, void* workspace, int64_t workspace_bytes, void* stream) {
+    ft_layout L;
+    if (!ft_plan(B, H, W, max_hyp, L) || !ft_params_ok(max_hyp, thr, min_inliers)) return ST_EINVAL;
+    if (workspace_bytes < L.total || ((uintptr_t)workspace & 15)) return ST_EINVAL;
+    const int64_t px = (int64_t)B * H * W;
+    const ft_region r[6] = {{img1, 12 * px, false}, {img2, 12 * px, false}, {motion_out, 32 * B, true}, {H_out, 36 * B, true}, {info_out, 32 * B, true},
+                            {workspace, L.total, true}};
+    if (!ft_regions_ok(r, 6)) return ST_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const int64_t bn = (int64_t)B * L.N;
+    int32_t* kp = (int32_t*)(ws + L.kp);
+    uint32_t* desc = (uint32_t*)(ws + L.desc);
+    int32_t* matches = (int32_t*)(ws + L.matches);
+    int32_t* count = (int32_t*)(ws + L.count);
+    int rc = ft_launch_detect(img1, img2, B, 2, H, W, kp, (uint16_t*)(ws + L.box), s);
+    if (rc) return rc;
+    rc = ft_launch_describe((const uint16_t*)(ws + L.box), kp, 2 * B, H, W, desc, s);
+    if (rc) return rc;
+    rc = ft_launch_match(kp, desc, kp + 2 * bn, desc + 8 * bn, B, L.N, (int32_t*)(ws + L.nn), matches, count, s);
+    if (rc) return rc;
+    return ft_launch_ransac(kp, kp + 2 * bn, matches, count, B, H, W, max_hyp, thr, min_inliers, (uint32_t)seed, (double*)(ws + L.mc), (int32_t*)(ws + L.scores),
+                            motion_out, H_out, info_out, (uint8_t*)(ws + L.mask), s);
+}

@@ -195,10 +195,11 @@ class EvalPipeline:
     def _slot(self, k, shape, u8):
         """The slot (stream + graph) number k for this input shape; captured on first use.  The cache is bounded: a dataset of many image
         sizes (or ragged batch tails) evicts the least recently used SHAPE -- its graphs, private pools and pinned buffers go with it.
-        The model's test_eval branch is part of the key: a cfg flag flipped after a capture (only_homo, use_combine_h_flow) captures anew
+        The model's test_eval branch and its (homo_source, flow_source) are part of the key: a cfg flag flipped after a capture (only_homo, use_combine_h_flow) captures anew
         instead of replaying the other branch's graph."""
         branch = self.model.eval_branch() if hasattr(self.model, "eval_branch") else None
-        key = (shape, u8, branch)
+        sources = self.model.sources() if hasattr(self.model, "sources") else None
+        key = (shape, u8, branch, sources)
         group = self._slots.pop(key, None)
         if group is None:
             group = {}

@@ -1713,3 +1713,166 @@ def inpaint_patchmatch(img, mask, levels=None, iters=4, seed=1, workspace=None, 
     check(lib.st_patchmatch_fill(_pc(img), _pc(mask), H, W, lv, int(iters), seed - (1 << 32) if seed >= 1 << 31 else seed, _p(out), _p(info), _p(nnf), _p(sad),
                                  _p(workspace), workspace.numel() * workspace.element_size(), _stream()), "st_patchmatch_fill")
     return (out, info, nnf, sad) if return_fields else (out, info)
+
+
+# ---- feature_align: corners, binary descriptors, matching, RANSAC homography (csrc/features.hip; README.md, feature_align) -------------------
+FEATURE_MIN_SIDE, FEATURE_MAX_SIDE, FEATURE_MAX_BATCH, FEATURE_MAX_HYP = 64, 1024, 64, 65536
+_FEATURE_REGIONS = ("box", "kp", "desc", "nn", "matches", "count", "mc", "scores", "mask", "total")
+
+
+def _feature_image(img, name="img"):
+    if img.dim() != 4 or img.shape[1] != 3 or img.dtype != torch.float32:
+        raise ValueError(f"{name}: float32 [B,3,H,W] expected, got {img.dtype} {tuple(img.shape)}")
+    B, _, H, W = img.shape
+    _feature_shape(B, H, W)
+    return B, H, W
+
+
+def _feature_shape(B, H, W):
+    if not 1 <= B <= FEATURE_MAX_BATCH:
+        raise ValueError(f"batch must be in 1..{FEATURE_MAX_BATCH}, got {B}")
+    if not (FEATURE_MIN_SIDE <= H <= FEATURE_MAX_SIDE and FEATURE_MIN_SIDE <= W <= FEATURE_MAX_SIDE):
+        raise ValueError(f"sides must be in {FEATURE_MIN_SIDE}..{FEATURE_MAX_SIDE}, got {H} x {W}")
+
+
+def _feature_operand(t, name, dtype, shape):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {dtype} {tuple(shape)} expected, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _feature_seed(seed):
+    seed = int(seed) & 0xFFFFFFFF
+    return seed - (1 << 32) if seed >= 1 << 31 else seed
+
+
+def _feature_params(max_hyp, thr, min_inliers):
+    if not 1 <= int(max_hyp) <= FEATURE_MAX_HYP:
+        raise ValueError(f"max_hyp must be in 1..{FEATURE_MAX_HYP}, got {max_hyp}")
+    if not 0.0 < float(thr) < float("inf"):
+        raise ValueError(f"thr must be finite and positive, got {thr}")
+    if int(min_inliers) < 0:
+        raise ValueError(f"min_inliers must be >= 0, got {min_inliers}")
+    return int(max_hyp), float(thr), int(min_inliers)
+
+
+def feature_slots(H, W):
+    """N = 4 ceil(H/32) ceil(W/32), the keypoint slots of an H x W image; 0 for a side outside 64..1024"""
+    return int(lib.st_feature_slots(int(H), int(W)))
+
+
+def feature_brief_pattern():
+    """the BRIEF-256 pattern, an int8 [256,4] CPU tensor: bit k of a descriptor is S(p + (ax, ay)) < S(p + (bx, by)) for row k = (ax, ay, bx, by)"""
+    buf = (C.c_int8 * 1024)()
+    check(lib.st_feature_brief_pattern(C.cast(buf, C.c_void_p)), "st_feature_brief_pattern")
+    return torch.tensor(list(buf), dtype=torch.int8).reshape(256, 4)
+
+
+def feature_workspace_bytes(B, H, W, max_hyp=2048):
+    """bytes of workspace `feature_homography` needs; 0 for a shape or max_hyp outside the contract"""
+    return int(lib.st_feature_workspace_bytes(int(B), int(H), int(W), int(max_hyp)))
+
+
+def feature_workspace_layout(B, H, W, max_hyp=2048):
+    """{region: byte offset} of that workspace (include/stitch_gfx950.h, st_feature_workspace_layout) and its "total" """
+    off = (C.c_int64 * 10)()
+    check(lib.st_feature_workspace_layout(int(B), int(H), int(W), int(max_hyp), C.cast(off, C.c_void_p)), "st_feature_workspace_layout")
+    return dict(zip(_FEATURE_REGIONS, (int(v) for v in off)))
+
+
+def feature_detect(img):
+    """Stage 1 (README.md, feature_align): img fp32 [B,3,H,W] -> (kp int32 [B,N,2] = (x, y) per slot, (-1, -1) unused; box int16 [B,H,W] (values 0..6375), the
+    5x5 box sum of the luma that `feature_describe` reads)."""
+    B, H, W = _feature_image(img)
+    N = feature_slots(H, W)
+    kp = torch.empty((B, N, 2), dtype=torch.int32, device=img.device)
+    box = torch.empty((B, H, W), dtype=torch.int16, device=img.device)
+    check(lib.st_feature_detect(_pc(img), B, H, W, _p(kp), _p(box), _stream()), "st_feature_detect")
+    return kp, box
+
+
+def feature_describe(box, kp):
+    """Stage 2: box int16 [B,H,W], kp int32 [B,N,2] -> desc uint32 [B,N,8] (as int32 bit patterns: torch has no uint32 arithmetic), zero
+    for an unused slot."""
+    B, H, W = box.shape
+    _feature_shape(B, H, W)
+    N = feature_slots(H, W)
+    _feature_operand(box, "box", torch.int16, (B, H, W))
+    _feature_operand(kp, "kp", torch.int32, (B, N, 2))
+    desc = torch.empty((B, N, 8), dtype=torch.int32, device=box.device)
+    check(lib.st_feature_describe(_pc(box), _pc(kp), B, H, W, _p(desc), _stream()), "st_feature_describe")
+    return desc
+
+
+def feature_match(kp1, desc1, kp2, desc2, H, W):
+    """Stage 3: -> (nn int32 [2,B,N,3] = per direction and slot (best slot or -1, d1, d2); matches int32 [B,N,2] = (slot 1, slot 2) in slot
+    order of image 1, (-1, -1) behind the last; count int32 [B])."""
+    B = kp1.shape[0]
+    _feature_shape(B, H, W)
+    N = feature_slots(H, W)
+    for k, d, n in ((kp1, desc1, "1"), (kp2, desc2, "2")):
+        _feature_operand(k, "kp" + n, torch.int32, (B, N, 2))
+        _feature_operand(d, "desc" + n, torch.int32, (B, N, 8))
+    dev = kp1.device
+    nn = torch.empty((2, B, N, 3), dtype=torch.int32, device=dev)
+    matches = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib.st_feature_match(_pc(kp1), _pc(desc1), _pc(kp2), _pc(desc2), B, H, W, _p(nn), _p(matches), _p(count), _stream()), "st_feature_match")
+    return nn, matches, count
+
+
+def feature_ransac(kp1, kp2, matches, count, H, W, *, max_hyp=2048, thr=3.0, min_inliers=12, seed=1):
+    """Stage 4: -> (motion fp32 [B,4,2], H fp32 [B,3,3], info int32 [B,8], mask uint8 [B,N]: the inlier flag of every list entry)."""
+    B = kp1.shape[0]
+    _feature_shape(B, H, W)
+    max_hyp, thr, min_inliers = _feature_params(max_hyp, thr, min_inliers)
+    N = feature_slots(H, W)
+    _feature_operand(kp1, "kp1", torch.int32, (B, N, 2))
+    _feature_operand(kp2, "kp2", torch.int32, (B, N, 2))
+    _feature_operand(matches, "matches", torch.int32, (B, N, 2))
+    _feature_operand(count, "count", torch.int32, (B,))
+    dev = kp1.device
+    motion = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
+    Hm = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+    info = torch.empty((B, 8), dtype=torch.int32, device=dev)
+    mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    ws = torch.empty(32 * B * N + 4 * B * max_hyp, dtype=torch.uint8, device=dev)
+    check(lib.st_feature_ransac(_pc(kp1), _pc(kp2), _pc(matches), _pc(count), B, H, W, max_hyp, thr, min_inliers, _feature_seed(seed), _p(motion), _p(Hm), _p(info),
+                                _p(mask), _p(ws), ws.numel(), _stream()), "st_feature_ransac")
+    return motion, Hm, info, mask
+
+
+def feature_homography(img1, img2, *, max_hyp=2048, thr=3.0, min_inliers=12, seed=1, workspace=None, return_fields=False):
+    """A homography from pixels, without weights (README.md, feature_align; this project's own contract, pinned against no library): img1,
+    img2 fp32 [B,3,H,W] in 0..255 -> (motion fp32 [B,4,2], H fp32 [B,3,3], info int32 [B,8]), all on the device.  H maps image-1 pixels onto
+    image-2 pixels (h33 = 1) -- the matrix `dlt4` gives for the corners (0,0), (W,0), (0,H), (W,H) moved by `motion`, the direction of the
+    homography network's offsets.  info = (valid, keypoints 1, keypoints 2, matches, winning hypothesis or -1, inliers, 0, 0); without a
+    valid model motion is zero and H the identity.  ``max_hyp`` RANSAC hypotheses, ``thr`` the inlier distance in pixels, ``min_inliers``
+    what a valid model needs, ``seed`` keys every draw.  ``workspace``: a uint8 device tensor of at least `feature_workspace_bytes` bytes,
+    16-byte aligned (default: allocated here).  ``return_fields``: also a dict of copies of the workspace's regions after the call: kp1, kp2
+    int32 [B,N,2]; desc1, desc2 int32 [B,N,8]; nn int32 [2,B,N,3]; matches int32 [B,N,2]; count int32 [B]; mask uint8 [B,N].  All
+    launches go to the current stream and nothing is read back."""
+    B, H, W = _feature_image(img1, "img1")
+    if img2.shape != img1.shape or img2.dtype != torch.float32 or img2.device != img1.device:
+        raise ValueError(f"img2: float32 {tuple(img1.shape)} on {img1.device} expected, got {img2.dtype} {tuple(img2.shape)} on {img2.device}")
+    max_hyp, thr, min_inliers = _feature_params(max_hyp, thr, min_inliers)
+    dev = img1.device
+    if workspace is None:
+        workspace = torch.empty(feature_workspace_bytes(B, H, W, max_hyp), dtype=torch.uint8, device=dev)
+    motion = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
+    Hm = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+    info = torch.empty((B, 8), dtype=torch.int32, device=dev)
+    check(lib.st_feature_homography(_pc(img1), _pc(img2), B, H, W, max_hyp, thr, min_inliers, _feature_seed(seed), _p(motion), _p(Hm), _p(info), _p(workspace),
+                                    workspace.numel() * workspace.element_size(), _stream()), "st_feature_homography")
+    if not return_fields:
+        return motion, Hm, info
+    N, L, raw = feature_slots(H, W), feature_workspace_layout(B, H, W, max_hyp), workspace.view(torch.uint8).reshape(-1)
+
+    def region(name, nbytes, dtype, shape):
+        return raw[L[name]:L[name] + nbytes].view(dtype).reshape(shape).clone()
+    kp = region("kp", 16 * B * N, torch.int32, (2, B, N, 2))
+    desc = region("desc", 64 * B * N, torch.int32, (2, B, N, 8))
+    fields = dict(kp1=kp[0], kp2=kp[1], desc1=desc[0], desc2=desc[1], nn=region("nn", 24 * B * N, torch.int32, (2, B, N, 3)),
+                  matches=region("matches", 8 * B * N, torch.int32, (B, N, 2)), count=region("count", 4 * B, torch.int32, (B,)),
+                  mask=region("mask", B * N, torch.uint8, (B, N)))
+    return motion, Hm, info, fields

@@ -74,7 +74,7 @@ class SequenceStitcher:
                 return self._run(image1, image2)             # raises: there is no CPU path
             with ops.workspace_scope(self._workspace(dev)):
                 return self._run(image1, image2)
-        key = (tuple(image1.shape), dev.index, m.eval_branch(), self.iters)      # a cfg flip re-captures
+        key = (tuple(image1.shape), dev.index, m.eval_branch(), m.sources(), self.iters)      # a cfg flip re-captures
         ent = self._graphs.get(key)
         if ent is not None and ent[4] != m.weights_generation():                 # weights re-packed since the capture
             ent = None
