@@ -26,8 +26,8 @@ def validate(cfg, val_dataset, batch_size=1, gpu_decode=False):
     if not (hasattr(cfg, "homo_backbone") and cfg.homo_backbone is not None):
         raise NotImplementedError
     model = stitch_amd.build_model(cfg)
-    if model.sources() == ("features", "zero") and not os.path.exists(cfg.restore_ckpt):
-        print("[No ckpt at {}: homo_source='features' and flow_source='zero' read no network weights]".format(cfg.restore_ckpt))
+    if "network" not in model.sources() and not os.path.exists(cfg.restore_ckpt):
+        print("[No ckpt at {}: homo_source='{}' and flow_source='{}' read no network weights]".format(cfg.restore_ckpt, *model.sources()))
     else:
         print("[Loading ckpt from {}]".format(cfg.restore_ckpt))
         model.load_state_dict(torch.load(cfg.restore_ckpt, map_location="cpu", weights_only=True), strict=True)

@@ -955,6 +955,34 @@ int st_feature_ransac(const int32_t* kp1, const int32_t* kp2, const int32_t* mat
 int st_feature_homography(const float* img1, const float* img2, int32_t B, int32_t H, int32_t W, int32_t max_hyp, double thr, int32_t min_inliers,
                           int32_t seed, float* motion_out, float* H_out, int32_t* info_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- dense_flow: a weight-free residual flow (csrc/dense_flow.hip; contract in README.md, dense_flow; CPU restatement
+ *      tests/_dense_flow_ref.py; this project's own contract, pinned against no library).  Coarse-to-fine, zero-mean Lucas-Kanade on integer
+ *      pyramids: V = 16 luma (int16) and a validity mask (uint8) per level, the flow state int32 (Ux, Uy) in 1/256 px of its level.  Images
+ *      float32 [B,3,H,W], pixel = trunc(clamp(x, 0, 255)); B 1..64, sides 16..1024.  A mask is float32 with 1 or 3 channels per item
+ *      (mask*_channels; channel 0 is read, set iff > 0.5), or a null pointer for all set.  levels 1..8 (capped: level l+1 exists iff
+ *      l+1 < levels and min(H_l, W_l) >= 32; it is ceil(H_l/2) x ceil(W_l/2)), iters 1..16, radius 1..7, damping 0..2^24.  No call
+ *      synchronises, allocates or uses atomics; the launch count and every grid depend on B, H, W, levels and iters alone; no buffer needs
+ *      initialisation.  Every entry returns ST_EINVAL before any launch for a null pointer (other than a mask), a rejected shape or
+ *      parameter, a small or misaligned workspace, and an output that overlaps any other operand of the call.                             */
+/* *bytes_host = bytes of workspace st_dense_flow needs.                                                                                  */
+int st_dense_flow_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t levels, int64_t* bytes_host);
+/* the regions of that workspace into HOST memory int64 [28]: [0] the number of levels L; [1+l], [9+l], [17+l] the byte offsets of level
+ * l's V int16 [2,B,Hl,Wl], m uint8 [2,B,Hl,Wl] (image 1's planes first) and U int32 [B,2,Hl,Wl] (-1 for l >= L); [25] the flow before the
+ * median int32 [B,2,H,W]; [26] the support of an iteration uint8 [B,H,W]; [27] total.  After a call they hold that call's data.            */
+int st_dense_flow_workspace_layout(int32_t B, int32_t H, int32_t W, int32_t levels, int64_t* offsets_host);
+/* both pyramids into the V and m regions of `workspace` (at least the total above, 16-byte aligned).  L launches.                         */
+int st_dense_flow_pyramid(const float* img1, const float* img2, const float* mask1, int32_t mask1_channels, const float* mask2, int32_t mask2_channels,
+                          int32_t B, int32_t H, int32_t W, int32_t levels, void* workspace, int64_t workspace_bytes, void* stream);
+/* one iteration at one level of H x W (sides 16..1024): v1, v2 int16 [B,H,W], m1, m2 uint8 [B,H,W], u int32 [B,2,H,W] -> u_out int32
+ * [B,2,H,W] (the update, then the 3x3 median), support_out uint8 [B,H,W].  workspace: at least 8 B H W bytes, 16-byte aligned.  2 launches. */
+int st_dense_flow_iterate(const int16_t* v1, const int16_t* v2, const uint8_t* m1, const uint8_t* m2, const int32_t* u, int32_t B, int32_t H, int32_t W,
+                          int32_t radius, int32_t damping, int32_t* u_out, uint8_t* support_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* flow_out float32 [B,2,H,W] = (dx, dy) with img1(p) ~ img2(p + flow(p)), exactly U / 256 of level 0; support_out uint8 [B,H,W]: the
+ * supported flag of the last iteration at level 0.  2 L + 2 L iters launches.                                                            */
+int st_dense_flow(const float* img1, const float* img2, const float* mask1, int32_t mask1_channels, const float* mask2, int32_t mask2_channels, int32_t B,
+                  int32_t H, int32_t W, int32_t levels, int32_t iters, int32_t radius, int32_t damping, float* flow_out, uint8_t* support_out, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

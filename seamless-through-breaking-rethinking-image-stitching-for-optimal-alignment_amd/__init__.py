@@ -7,6 +7,7 @@ Importing this package requires the built library: there is no CPU or eager-PyTo
 """
 from . import _lib  # noqa: F401  (fails loudly if the HIP extension is missing)
 from . import ops  # noqa: F401
+from .dense_flow import DenseFlow  # noqa: E402,F401
 from .feature_align import FeatureAligner  # noqa: E402,F401
 from .adapter import FlowHomoAdpater, preprocess_occlusion_mask  # noqa: E402,F401
 from .config import CfgNode, load_inference_config, load_model_config  # noqa: E402,F401

@@ -18,10 +18,11 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .dense_flow import DenseFlow
 from .feature_align import FeatureAligner
 
 HOMO_SOURCES = ("network", "features")           # cfg.homo_source: the UDIS2 regression network, or corners + BRIEF + RANSAC (feature_align.py)
-FLOW_SOURCES = ("network", "zero")               # cfg.flow_source: FlowFormer++, or no residual flow at all
+FLOW_SOURCES = ("network", "zero", "dense_lk")   # cfg.flow_source: FlowFormer++, no residual flow at all, or pyramidal Lucas-Kanade (dense_flow.py)
 
 
 def preprocess_occlusion_mask(occlusion_mask, kernel_size=(19, 19)):
@@ -46,6 +47,7 @@ class FlowHomoAdpater(nn.Module):
         self.flow_backbone = flow_backbone
         self._host = {}
         self._aligner = None             # feature_align.FeatureAligner, built on first use with cfg.homo_source == "features"
+        self._dense_flow = None          # dense_flow.DenseFlow, built on first use with cfg.flow_source == "dense_lk"
         self._eval_pipeline = None       # stitch_amd.evaluate.EvalPipeline: hipGraphs of the evaluation loop, captured on first use
 
     # checkpoints saved from DataParallel carry a "module." prefix (out.py:80-85)
@@ -118,6 +120,12 @@ class FlowHomoAdpater(nn.Module):
             self._aligner = FeatureAligner(**dict(_flag(self.cfg, "feature_align", {}) or {}))
         return self._aligner
 
+    def dense_flow(self):
+        """the flow of flow_source="dense_lk"; cfg.dense_flow (optional) holds DenseFlow's keyword arguments"""
+        if self._dense_flow is None:
+            self._dense_flow = DenseFlow(**dict(_flag(self.cfg, "dense_flow", {}) or {}))
+        return self._dense_flow
+
     # ------------------------------------------------------------------ reference surface
     def predict_homo(self, input1_tensor, input2_tensor):
         """[0,255] -> corner offsets [B,4,2] (flowHomoAdpater.py:53-61); x/127.5 - 1 is fused into the prep.  With homo_source="features"
@@ -137,10 +145,18 @@ class FlowHomoAdpater(nn.Module):
         both = self.flow_backbone.flow_rows_pair(input1_tensor, input2_tensor, iters=iters, flow_init=flow_init)[0]
         return both[:B], both[B:]
 
-    def _flows(self, input1_tensor, input2_tensor, pair, warm):
+    def _flows(self, input1_tensor, input2_tensor, pair, warm, warp_mask=None):
         """The flow pass of a branch: (flow 1->2, flow 2->1 or None).  ``warm`` (a ``sequence.SequenceStitcher``'s state, or None): the
         refinement starts from its buffer and the splat of this call's final low-res flow (``ops.forward_interpolate`` on coords1's
-        rows) replaces it, both on the current stream: no host synchronisation, the same launch sequence for every frame."""
+        rows) replaces it, both on the current stream: no host synchronisation, the same launch sequence for every frame.  With
+        flow_source="dense_lk" no FlowFormer kernel is launched: forward = dense_flow(1, 2, mask2=warp_mask) and back = dense_flow(2, 1,
+        mask1=warp_mask), as one batch of 2B; ``warp_mask`` is the ones-plane of the homography warp that produced image 2 (there is no
+        warm start to carry: ``warm`` is not read)."""
+        if self.sources()[1] == "dense_lk":
+            lk = self.dense_flow()
+            if pair:
+                return lk.flow_pair(input1_tensor, input2_tensor, warp_mask)
+            return lk.flow(input1_tensor, input2_tensor, mask2=warp_mask), None
         if warm is None:
             return self.predict_flow_pair(input1_tensor, input2_tensor) if pair else (self.predict_flow(input1_tensor, input2_tensor)[0], None)
         B, _, h, w = input1_tensor.shape
@@ -230,12 +246,12 @@ class FlowHomoAdpater(nn.Module):
                         flow_predictions=None, H=H)
         warp2 = output_H[:, 0:3].contiguous()
         if branch == "combine":
-            flow = self._flows(input1_tensor, warp2, False, warm)[0]                                   # :148
+            flow = self._flows(input1_tensor, warp2, False, warm, output_H[:, 3:4])[0]                 # :148
             final, overlap, Hi = ops.homo_flow_warp(input2_tensor, H, flow)                            # :150-164
             return dict(output_H=output_H, output_H_inv=output_H_inv, final_warp_output=final, overlap=overlap,
                         flow_predictions=[flow], H=Hi)                                                 # H reassigned at :150
         fb = _flag(self.cfg, "use_fb_consistency_mask")              # missing key = False, as hasattr(...) and ... (:176)
-        flow_ij, flow_ji = self._flows(input1_tensor, warp2, fb, warm)                                 # :167 (and :178 in the same batch)
+        flow_ij, flow_ji = self._flows(input1_tensor, warp2, fb, warm, output_H[:, 3:4])               # :167 (and :178 in the same batch)
         final = ops.flow_warp(output_H, flow_ij)                                                       # :170
         out = dict()
         if fb:
@@ -259,7 +275,8 @@ class FlowHomoAdpater(nn.Module):
         No host synchronisation and a fixed launch sequence for a given input shape, so it can be replayed from a hipGraph
         (``GraphedTestOut``); everything it returns is a device tensor.  Without the consistency mask only the forward flow
         is computed (one flow-network pass) and ``back`` is None.  With flow_source="zero" no FlowFormer kernel is launched: the residual
-        is all zero and ``back`` is None, so the canvas part takes the blend without the consistency mask."""
+        is all zero and ``back`` is None, so the canvas part takes the blend without the consistency mask; with flow_source="dense_lk" the
+        Lucas-Kanade flow (dense_flow.py) is resized exactly as FlowFormer's is."""
         fb = self.test_out_branch() == "fb"
         zero_flow = self.sources()[1] == "zero"
         dev = input1_tensor.device
@@ -281,7 +298,7 @@ class FlowHomoAdpater(nn.Module):
         if zero_flow:
             residual = torch.zeros((B, 2, img_h, img_w), device=dev)
         else:
-            flow512, back512 = self._flows(a512, warp2_512, fb, warm)                                  # :236 (and :326 in the same batch)
+            flow512, back512 = self._flows(a512, warp2_512, fb, warm, out_H[:, 3:4])                   # :236 (and :326 in the same batch)
             residual = ops.resize_bilinear(flow512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))  # :241
         if fb and not zero_flow:
             back = ops.resize_bilinear(back512, img_h, img_w, True, div=(512 / float(img_w), 512 / float(img_h)))

@@ -1876,3 +1876,155 @@ def feature_homography(img1, img2, *, max_hyp=2048, thr=3.0, min_inliers=12, see
                   matches=region("matches", 8 * B * N, torch.int32, (B, N, 2)), count=region("count", 4 * B, torch.int32, (B,)),
                   mask=region("mask", B * N, torch.uint8, (B, N)))
     return motion, Hm, info, fields
+
+
+# ---- dense_flow: coarse-to-fine, zero-mean Lucas-Kanade residual flow on integer pyramids (csrc/dense_flow.hip; README.md, dense_flow) ------
+DENSE_FLOW_MIN_SIDE, DENSE_FLOW_MAX_SIDE, DENSE_FLOW_MAX_BATCH, DENSE_FLOW_MAX_LEVELS = 16, 1024, 64, 8
+DENSE_FLOW_MAX_ITERS, DENSE_FLOW_MAX_RADIUS, DENSE_FLOW_MAX_DAMPING = 16, 7, 1 << 24
+DENSE_FLOW_DEFAULTS = dict(levels=5, iters=4, radius=4, damping=65536)
+
+
+def _dense_flow_shape(B, H, W):
+    if not 1 <= B <= DENSE_FLOW_MAX_BATCH:
+        raise ValueError(f"batch must be in 1..{DENSE_FLOW_MAX_BATCH}, got {B}")
+    if not (DENSE_FLOW_MIN_SIDE <= H <= DENSE_FLOW_MAX_SIDE and DENSE_FLOW_MIN_SIDE <= W <= DENSE_FLOW_MAX_SIDE):
+        raise ValueError(f"sides must be in {DENSE_FLOW_MIN_SIDE}..{DENSE_FLOW_MAX_SIDE}, got {H} x {W}")
+
+
+def _dense_flow_params(levels, iters, radius, damping):
+    for name, v, lo, hi in (("levels", levels, 1, DENSE_FLOW_MAX_LEVELS), ("iters", iters, 1, DENSE_FLOW_MAX_ITERS), ("radius", radius, 1, DENSE_FLOW_MAX_RADIUS),
+                            ("damping", damping, 0, DENSE_FLOW_MAX_DAMPING)):
+        if int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v}")
+    return int(levels), int(iters), int(radius), int(damping)
+
+
+def _dense_flow_images(img1, img2):
+    if img1.dim() != 4 or img1.shape[1] != 3 or img1.dtype != torch.float32:
+        raise ValueError(f"img1: float32 [B,3,H,W] expected, got {img1.dtype} {tuple(img1.shape)}")
+    if img2.shape != img1.shape or img2.dtype != torch.float32 or img2.device != img1.device:
+        raise ValueError(f"img2: float32 {tuple(img1.shape)} on {img1.device} expected, got {img2.dtype} {tuple(img2.shape)} on {img2.device}")
+    B, _, H, W = img1.shape
+    _dense_flow_shape(B, H, W)
+    return B, H, W
+
+
+def _dense_flow_mask(mask, name, ref):
+    """-> (dense tensor or None, channels per item)"""
+    if mask is None:
+        return None, 1
+    B, _, H, W = ref.shape
+    if mask.dim() != 4 or mask.dtype != torch.float32 or mask.device != ref.device or mask.shape[0] != B or mask.shape[1] not in (1, 3) or tuple(mask.shape[2:]) != (H, W):
+        raise ValueError(f"{name}: float32 [{B},1 or 3,{H},{W}] on {ref.device} expected, got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+    return mask.contiguous(), int(mask.shape[1])
+
+
+def dense_flow_level_sizes(H, W, levels=5):
+    """[(H_l, W_l)] of the pyramid: level l+1 exists iff l+1 < levels and min(H_l, W_l) >= 32, and is ceil(H_l/2) x ceil(W_l/2)"""
+    sizes = [(int(H), int(W))]
+    while len(sizes) < levels and min(sizes[-1]) >= 32:
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    return sizes
+
+
+def dense_flow_workspace_bytes(B, H, W, levels=5):
+    """bytes of workspace `dense_flow` needs; 0 for a shape or `levels` outside the contract"""
+    n = C.c_int64(0)
+    return int(n.value) if lib.st_dense_flow_workspace_bytes(int(B), int(H), int(W), int(levels), C.cast(C.byref(n), C.c_void_p)) == 0 else 0
+
+
+def dense_flow_workspace_layout(B, H, W, levels=5):
+    """the regions of that workspace (include/stitch_gfx950.h, st_dense_flow_workspace_layout): dict(levels=L, v=[...], m=[...], u=[...] byte
+    offsets per level, tmp, sup, total)"""
+    off = (C.c_int64 * 28)()
+    check(lib.st_dense_flow_workspace_layout(int(B), int(H), int(W), int(levels), C.cast(off, C.c_void_p)), "st_dense_flow_workspace_layout")
+    o = [int(v) for v in off]
+    L = o[0]
+    return dict(levels=L, v=o[1:1 + L], m=o[9:9 + L], u=o[17:17 + L], tmp=o[25], sup=o[26], total=o[27])
+
+
+def _dense_flow_workspace(workspace, B, H, W, levels, dev):
+    need = dense_flow_workspace_bytes(B, H, W, levels)
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if workspace.device != dev:
+        raise ValueError(f"workspace on {dev} expected, got {workspace.device}")
+    return workspace
+
+
+def _dense_flow_pyramid_views(workspace, B, H, W, levels):
+    """copies of the pyramid regions of a workspace: (v1, v2 lists of int16 [B,Hl,Wl], m1, m2 lists of uint8 [B,Hl,Wl], layout, sizes)"""
+    P, raw = dense_flow_workspace_layout(B, H, W, levels), workspace.view(torch.uint8).reshape(-1)
+    sizes = dense_flow_level_sizes(H, W, levels)
+    v1, v2, m1, m2 = [], [], [], []
+    for l, (h, w) in enumerate(sizes):
+        v = raw[P["v"][l]:P["v"][l] + 4 * B * h * w].view(torch.int16).reshape(2, B, h, w).clone()
+        m = raw[P["m"][l]:P["m"][l] + 2 * B * h * w].reshape(2, B, h, w).clone()
+        v1.append(v[0]), v2.append(v[1]), m1.append(m[0]), m2.append(m[1])
+    return v1, v2, m1, m2, P, sizes
+
+
+def dense_flow_pyramid(img1, img2, mask1=None, mask2=None, *, levels=5, workspace=None):
+    """Stage 1 (README.md, dense_flow): both pyramids.  -> dict(v1, v2: lists per level of int16 [B,Hl,Wl], V = 16 luma at level 0;
+    m1, m2: lists of uint8 [B,Hl,Wl])."""
+    B, H, W = _dense_flow_images(img1, img2)
+    levels = _dense_flow_params(levels, 1, 1, 0)[0]
+    img1, img2 = img1.contiguous(), img2.contiguous()
+    mask1, c1 = _dense_flow_mask(mask1, "mask1", img1)
+    mask2, c2 = _dense_flow_mask(mask2, "mask2", img1)
+    workspace = _dense_flow_workspace(workspace, B, H, W, levels, img1.device)
+    check(lib.st_dense_flow_pyramid(_pc(img1), _pc(img2), _pc(mask1), c1, _pc(mask2), c2, B, H, W, levels, _p(workspace), workspace.numel() * workspace.element_size(),
+                                    _stream()), "st_dense_flow_pyramid")
+    v1, v2, m1, m2, _, _ = _dense_flow_pyramid_views(workspace, B, H, W, levels)
+    return dict(v1=v1, v2=v2, m1=m1, m2=m2)
+
+
+def dense_flow_iterate(v1, v2, m1, m2, u, *, radius=4, damping=65536):
+    """Stage 2: one iteration at one level.  v1, v2 int16 [B,H,W], m1, m2 uint8 [B,H,W], u int32 [B,2,H,W] (1/256 px) ->
+    (u_out int32 [B,2,H,W]: the clamped Lucas-Kanade update, then the 3x3 median; support uint8 [B,H,W])."""
+    if v1.dim() != 3 or v1.dtype != torch.int16:
+        raise ValueError(f"v1: int16 [B,H,W] expected, got {v1.dtype} {tuple(v1.shape)}")
+    B, H, W = v1.shape
+    _dense_flow_shape(B, H, W)
+    _, _, radius, damping = _dense_flow_params(1, 1, radius, damping)
+    for t, name, dtype, shape in ((v2, "v2", torch.int16, (B, H, W)), (m1, "m1", torch.uint8, (B, H, W)), (m2, "m2", torch.uint8, (B, H, W)),
+                                  (u, "u", torch.int32, (B, 2, H, W))):
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != v1.device:
+            raise ValueError(f"{name}: {dtype} {shape} on {v1.device} expected, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    dev = v1.device
+    u_out = torch.empty((B, 2, H, W), dtype=torch.int32, device=dev)
+    support = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    ws = torch.empty(8 * B * H * W, dtype=torch.uint8, device=dev)
+    check(lib.st_dense_flow_iterate(_pc(v1), _pc(v2), _pc(m1), _pc(m2), _pc(u), B, H, W, radius, damping, _p(u_out), _p(support), _p(ws), ws.numel(), _stream()),
+          "st_dense_flow_iterate")
+    return u_out, support
+
+
+def dense_flow(img1, img2, mask1=None, mask2=None, *, levels=5, iters=4, radius=4, damping=65536, workspace=None, return_fields=False):
+    """A dense residual flow from pixels, without weights (README.md, dense_flow; this project's own contract, pinned against no library):
+    img1, img2 fp32 [B,3,H,W] in 0..255 -> (flow fp32 [B,2,H,W], support uint8 [B,1,H,W]).  flow[:,0] = dx, flow[:,1] = dy in pixels,
+    1 -> 2: img1(p) ~ img2(p + flow(p)), the flow `flow_warp(img2, flow)` consumes to bring image 2 onto image 1.  support: whether the
+    last iteration at full resolution had enough valid window pixels and a positive determinant (elsewhere the flow is what the coarser
+    levels and the median left).  mask1, mask2: fp32 [B,1,H,W] or [B,3,H,W] (channel 0), valid iff > 0.5, None = all valid.  ``levels``
+    1..8 (capped by the size), ``iters`` 1..16 per level, ``radius`` 1..7 of the window, ``damping`` 0..2^24 on the diagonal.
+    ``workspace``: a uint8 device tensor of at least `dense_flow_workspace_bytes` bytes, 16-byte aligned (default: allocated here).
+    ``return_fields``: also a dict of copies of the workspace's regions after the call: v1, v2, m1, m2 (the pyramids, lists per level) and
+    u (list per level of int32 [B,2,Hl,Wl], the final flow of each level in 1/256 px).  All launches go to the current stream and nothing
+    is read back."""
+    B, H, W = _dense_flow_images(img1, img2)
+    levels, iters, radius, damping = _dense_flow_params(levels, iters, radius, damping)
+    img1, img2 = img1.contiguous(), img2.contiguous()
+    mask1, c1 = _dense_flow_mask(mask1, "mask1", img1)
+    mask2, c2 = _dense_flow_mask(mask2, "mask2", img1)
+    dev = img1.device
+    workspace = _dense_flow_workspace(workspace, B, H, W, levels, dev)
+    flow = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+    support = torch.empty((B, 1, H, W), dtype=torch.uint8, device=dev)
+    check(lib.st_dense_flow(_pc(img1), _pc(img2), _pc(mask1), c1, _pc(mask2), c2, B, H, W, levels, iters, radius, damping, _p(flow), _p(support), _p(workspace),
+                            workspace.numel() * workspace.element_size(), _stream()), "st_dense_flow")
+    if not return_fields:
+        return flow, support
+    v1, v2, m1, m2, P, sizes = _dense_flow_pyramid_views(workspace, B, H, W, levels)
+    raw = workspace.view(torch.uint8).reshape(-1)
+    u = [raw[P["u"][l]:P["u"][l] + 8 * B * h * w].view(torch.int32).reshape(B, 2, h, w).clone() for l, (h, w) in enumerate(sizes)]
+    return flow, support, dict(v1=v1, v2=v2, m1=m1, m2=m2, u=u)
