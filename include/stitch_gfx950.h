@@ -955,6 +955,48 @@ int st_feature_ransac(const int32_t* kp1, const int32_t* kp2, const int32_t* mat
 int st_feature_homography(const float* img1, const float* img2, int32_t B, int32_t H, int32_t W, int32_t max_hyp, double thr, int32_t min_inliers,
                           int32_t seed, float* motion_out, float* H_out, int32_t* info_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- feature_align_ms: the oriented, multi-scale front end beside feature_align (csrc/features_ms.hip; contract in README.md,
+ *      feature_align_ms; CPU restatement tests/_features_ms_ref.py; this project's own contract, pinned against no library).  Operands as
+ *      feature_align's; levels 1..8 (capped: level l+1 exists iff l+1 < levels and min(4 H_l div 5, 4 W_l div 5) >= 64, and is that size),
+ *      oriented 0 / 1.  The slots of all levels are concatenated, level 0 first: N = sum of 4 ceil(H_l/32) ceil(W_l/32); keypoints int32
+ *      (x, y) in their level's pixels, one orientation bin 0..31 (uint8) per slot.  A pyramid or box-sum buffer of n planes holds level l's
+ *      [n, H_l, W_l] planes behind those of the levels before it.  Same conventions as st_feature_*: no call synchronises, allocates or uses
+ *      atomics; the launch count and every grid depend on B, H, W, levels and max_hyp alone; no buffer needs initialisation; ST_EINVAL
+ *      before any launch for a null pointer, a rejected shape or parameter, a small or misaligned workspace, and an output that overlaps
+ *      any other operand of the call.  --------------------------------------------------------------------------------------------------- */
+/* the number of levels L (0 for a rejected H, W or levels); sizes_host (may be null) int32 [8,2] = (H_l, W_l), 0 for l >= L.              */
+int st_feature_ms_level_sizes(int32_t H, int32_t W, int32_t levels, int32_t* sizes_host);
+/* N over all levels; 0 for a rejected H, W or levels.                                                                                    */
+int st_feature_ms_slots(int32_t H, int32_t W, int32_t levels);
+/* bytes of workspace st_feature_ms_homography needs (below 2^31 for every accepted shape); 0 for a rejected argument.                    */
+int st_feature_ms_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t levels, int32_t max_hyp);
+/* the regions of that workspace, byte offsets into HOST memory int64 [13]: pyramids uint8 (2B planes, image 1's first), box sums uint16
+ * (2B planes), keypoints int32 [2,B,N,2], bins uint8 [2,B,N], descriptors uint32 [2,B,N,8], nn int32 [2,B,N,3], matches int32 [B,N,2],
+ * count int32 [B], level-0 coordinates fp64 [2,B,N,2], normalised match coordinates fp64 [B,N,4], scores int32 [B,max_hyp], inlier mask
+ * uint8 [B,N], total.  After a call they hold that call's intermediate data.                                                             */
+int st_feature_ms_workspace_layout(int32_t B, int32_t H, int32_t W, int32_t levels, int32_t max_hyp, int64_t* offsets_host);
+/* pyr_out uint8, B planes per level: level 0 the luma, level l+1 the centre-aligned x 5/4 bilinear resample of level l.  L launches.      */
+int st_feature_ms_pyramid(const float* img, int32_t B, int32_t H, int32_t W, int32_t levels, uint8_t* pyr_out, void* stream);
+/* kp_out int32 [B,N,2], bins_out uint8 [B,N] (all 0 with oriented = 0), box_out uint16 (B planes per level): the 5x5 box sum of each level.
+ * 1 launch over the cells of all levels.                                                                                                  */
+int st_feature_ms_detect(const uint8_t* pyr, int32_t B, int32_t H, int32_t W, int32_t levels, int32_t oriented, int32_t* kp_out, uint8_t* bins_out,
+                         uint16_t* box_out, void* stream);
+/* desc_out uint32 [B,N,8]: the BRIEF pattern steered by the slot's bin on the box sums of the slot's level; zero for an unused slot.  1 launch. */
+int st_feature_ms_describe(const uint16_t* box, const int32_t* kp, const uint8_t* bins, int32_t B, int32_t H, int32_t W, int32_t levels, uint32_t* desc_out,
+                           void* stream);
+/* st_feature_match over the N slots of all levels.  2 launches.                                                                          */
+int st_feature_ms_match(const int32_t* kp1, const uint32_t* desc1, const int32_t* kp2, const uint32_t* desc2, int32_t B, int32_t H, int32_t W, int32_t levels,
+                        int32_t* nn_out, int32_t* matches_out, int32_t* count_out, void* stream);
+/* st_feature_ransac on level-0 coordinates: xy_out fp64 [2,B,N,2], the level-0 position ((2 x + 1) 5^l) / (2 4^l) - 1/2 of every slot of
+ * both images, (-1, -1) for an unused one.  workspace: at least 32 B N + 4 B max_hyp bytes, 16-byte aligned.  3 launches.                  */
+int st_feature_ms_ransac(const int32_t* kp1, const int32_t* kp2, const int32_t* matches, const int32_t* count, int32_t B, int32_t H, int32_t W, int32_t levels,
+                         int32_t max_hyp, double thr, int32_t min_inliers, int32_t seed, float* motion_out, float* H_out, int32_t* info_out, uint8_t* mask_out,
+                         double* xy_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* all stages on both images inside `workspace` (st_feature_ms_workspace_bytes, 16-byte aligned): L + 7 launches.                         */
+int st_feature_ms_homography(const float* img1, const float* img2, int32_t B, int32_t H, int32_t W, int32_t levels, int32_t oriented, int32_t max_hyp, double thr,
+                             int32_t min_inliers, int32_t seed, float* motion_out, float* H_out, int32_t* info_out, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+
 /* ---- dense_flow: a weight-free residual flow (csrc/dense_flow.hip; contract in README.md, dense_flow; CPU restatement
  *      tests/_dense_flow_ref.py; this project's own contract, pinned against no library).  Coarse-to-fine, zero-mean Lucas-Kanade on integer
  *      pyramids: V = 16 luma (int16) and a validity mask (uint8) per level, the flow state int32 (Ux, Uy) in 1/256 px of its level.  Images

@@ -12,13 +12,13 @@ OUT = os.path.join(HERE, "libstitch_gfx950.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # geom.hip pins every fp32 rounding (bit-exact sample indices), inpaint.hip the Telea arrival times, tps_other.hip the fp64 remap
 # maps, transref.hip the inpainter's pre / post steps, flow_splat.hip the warm start's fp64 nearest-source distances, multiband.hip every fp32 rounding of its pyramids,
-# exposure.hip the fp64 gain solves and the fp32 smoothing / interpolation / apply chain, features.hip the fp64 RANSAC, dense_flow.hip the fp64 solve of every pixel: no fma contraction there (seam.hip, seam_gc.hip, crop.hip and patchmatch.hip are all integers)
+# exposure.hip the fp64 gain solves and the fp32 smoothing / interpolation / apply chain, features.hip and features_ms.hip the fp64 RANSAC, dense_flow.hip the fp64 solve of every pixel: no fma contraction there (seam.hip, seam_gc.hip, crop.hip and patchmatch.hip are all integers)
 SOURCES = {"gemm.hip": [], "gemm_split3.hip": [], "gemm_rows.hip": [], "nn.hip": [], "flowops.hip": [], "geom.hip": ["-ffp-contract=off"],
            "metrics.hip": ["-ffp-contract=off"], "operators.hip": [], "composition.hip": ["-ffp-contract=off"], "tps_pipeline.hip": ["-ffp-contract=off"], "patchembed.hip": [],
            "inpaint.hip": ["-ffp-contract=off"], "tps_other.hip": ["-ffp-contract=off"],
            "transref.hip": ["-ffp-contract=off"], "flow_splat.hip": ["-ffp-contract=off"], "jpeg.hip": [], "jpeg_dec.hip": [],
            "multiband.hip": ["-ffp-contract=off"], "exposure.hip": ["-ffp-contract=off"], "seam.hip": [], "seam_gc.hip": [], "crop.hip": [], "patchmatch.hip": [],
-           "features.hip": ["-ffp-contract=off"], "dense_flow.hip": ["-ffp-contract=off"]}
+           "features.hip": ["-ffp-contract=off"], "dense_flow.hip": ["-ffp-contract=off"], "features_ms.hip": ["-ffp-contract=off"]}
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # No packed-fp32 VALU instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) anywhere in the library.  Measured in round 6
 # (tools/neighbour_stress.py, profiles/r6_pk_f32_beside_bf16_mfma.txt): while another wave of the SIMD issues v_mfma_f32_32x32x16_bf16
@@ -48,7 +48,7 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=False):
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_split3.h"), os.path.join(CSRC, "mlp_split3.h"), os.path.join(CSRC, "tps_solve.h"), os.path.join(CSRC, "jpeg_dec_core.h"), os.path.join(CSRC, "jpeg_tables.h"), os.path.join(CSRC, "jpeg_huff_core.h"), os.path.join(CSRC, "jpeg_scan.h"), os.path.join(CSRC, "jpeg_rst_core.h"), os.path.join(HERE, "..", "include", "stitch_gfx950.h")]
+    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_split3.h"), os.path.join(CSRC, "mlp_split3.h"), os.path.join(CSRC, "tps_solve.h"), os.path.join(CSRC, "jpeg_dec_core.h"), os.path.join(CSRC, "jpeg_tables.h"), os.path.join(CSRC, "jpeg_huff_core.h"), os.path.join(CSRC, "jpeg_scan.h"), os.path.join(CSRC, "jpeg_rst_core.h"), os.path.join(CSRC, "features_common.h"), os.path.join(HERE, "..", "include", "stitch_gfx950.h")]
     objs, jobs = [], []
     os.makedirs(os.path.join(CSRC, "_obj"), exist_ok=True)
     for src in SOURCES:

@@ -14,57 +14,10 @@
 //   ft_norm_kernel      normalised fp64 coordinates of the matches
 //   ft_hyp_kernel       one thread per hypothesis: draw, 8x8 solve in LDS, score against the match list (1024 matches at a time in LDS)
 //   ft_refit_kernel     one workgroup per item: winner, inlier mask, two least-squares refits (four interleaved partial sums per entry), H / motion / info
-#include "common.h"
+#include "features_common.h"           // the constants, the hash, the solve, the inlier test and the H / motion / info tail, shared with features_ms.hip
 
-#define FT_MIN_SIDE 64
-#define FT_MAX_SIDE 1024
-#define FT_MAX_BATCH 64
-#define FT_MAX_HYP 65536
-#define FT_CELL 32
-#define FT_PER_CELL 4
-#define FT_BORDER 16
-#define FT_WORDS 8
-#define FT_MAX_DIST 80                  // a match needs d1 < 80 of 256 bits ...
-#define FT_RATIO_NUM 8                  // ... and 10 d1 < 8 d2
-#define FT_RATIO_DEN 10
-#define FT_NO_DIST 257
-#define FT_MIN_MATCHES 8
-#define FT_PIVOT_MIN 1e-10
-#define FT_PATTERN_KEY 0x9E3779B9u
-#define FT_CHUNK 1024                   // candidates / matches staged in LDS at a time
-#define FT_THREADS 256
-
-__host__ __device__ constexpr uint32_t ft_fmix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x85EBCA6Bu;
-    x ^= x >> 13;
-    x *= 0xC2B2AE35u;
-    x ^= x >> 16;
-    return x;
-}
-
-// pair k compares the box sums at p + (v[4k], v[4k+1]) and p + (v[4k+2], v[4k+3]) (x, y); every offset in -12..12
-struct ft_pattern_t {
-    int8_t v[1024];
-};
-constexpr ft_pattern_t ft_make_pattern() {
-    ft_pattern_t p{};
-    for (int i = 0; i < 1024; ++i) p.v[i] = (int8_t)((int)(ft_fmix32(FT_PATTERN_KEY ^ (uint32_t)i) % 25u) - 12);
-    return p;
-}
 static constexpr ft_pattern_t ft_pattern_host = ft_make_pattern();
 __constant__ ft_pattern_t ft_pattern = ft_make_pattern();
-
-// the saver's pixel: trunc(clamp(x, 0, 255)); NaN and -Inf read 0, +Inf 255
-__device__ __forceinline__ int ft_pixel(float v) { return (int)fminf(fmaxf(v, 0.f), 255.f); }
-
-__device__ __forceinline__ long long ft_shfl_xor64(long long v, int o) {
-    const int lo = __shfl_xor((int)(v & 0xFFFFFFFFll), o, 64), hi = __shfl_xor((int)(v >> 32), o, 64);
-    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-// (R descending, index ascending)
-__device__ __forceinline__ bool ft_better(long long ra, int ia, long long rb, int ib) { return ra > rb || (ra == rb && ia < ib); }
 
 __global__ void __launch_bounds__(FT_THREADS) ft_detect_kernel(const float* __restrict__ img1, const float* __restrict__ img2, int B, int H, int W,
                                                                 int32_t* __restrict__ kp, uint16_t* __restrict__ box) {
@@ -282,8 +235,6 @@ __global__ void __launch_bounds__(1024) ft_compact_kernel(const int32_t* __restr
     if (t == 0) count[b] = m;
 }
 
-__device__ __forceinline__ int ft_count(const int32_t* __restrict__ count, int b, int N) { return min(max(count[b], 0), N); }
-
 // mc fp64 [B, N, 4]: (x1, y1, x2, y2) of list entry p, normalised as (x - W/2) / (W/2), (y - H/2) / (H/2)
 __global__ void __launch_bounds__(FT_THREADS) ft_norm_kernel(const int32_t* __restrict__ kp1, const int32_t* __restrict__ kp2, const int32_t* __restrict__ matches,
                                                               const int32_t* __restrict__ count, int H, int W, int N, double* __restrict__ mc) {
@@ -296,90 +247,6 @@ __global__ void __launch_bounds__(FT_THREADS) ft_norm_kernel(const int32_t* __re
     o[1] = ((double)kp1[((size_t)b * N + i) * 2 + 1] - sy) / sy;
     o[2] = ((double)kp2[((size_t)b * N + j) * 2] - sx) / sx;
     o[3] = ((double)kp2[((size_t)b * N + j) * 2 + 1] - sy) / sy;
-}
-
-// element `c` (0..8; 8 = right-hand side) of the two rows a match (x, y) -> (u, v) contributes to the system of h (h33 = 1)
-__device__ __forceinline__ double ft_row0(int c, double x, double y, double u) {
-    switch (c) {
-        case 0: return x;
-        case 1: return y;
-        case 2: return 1.0;
-        case 6: return -u * x;
-        case 7: return -u * y;
-        case 8: return u;
-        default: return 0.0;
-    }
-}
-__device__ __forceinline__ double ft_row1(int c, double x, double y, double v) {
-    switch (c) {
-        case 3: return x;
-        case 4: return y;
-        case 5: return 1.0;
-        case 6: return -v * x;
-        case 7: return -v * y;
-        case 8: return v;
-        default: return 0.0;
-    }
-}
-
-// Gaussian elimination with partial pivoting (first row on ties) of the 8 x 9 system at a[(r * 9 + c) * S]; a pivot below FT_PIVOT_MIN
-// (or a NaN) voids it
-template <int S>
-__device__ __forceinline__ bool ft_solve8(double* __restrict__ a, double (&x)[8]) {
-    for (int c = 0; c < 8; ++c) {
-        int piv = c;
-        double best = fabs(a[(c * 9 + c) * S]);
-        for (int r = c + 1; r < 8; ++r) {
-            const double v = fabs(a[(r * 9 + c) * S]);
-            if (v > best) best = v, piv = r;
-        }
-        if (!(best >= FT_PIVOT_MIN)) return false;
-        if (piv != c)
-            for (int k = 0; k < 9; ++k) {
-                const double tmp = a[(c * 9 + k) * S];
-                a[(c * 9 + k) * S] = a[(piv * 9 + k) * S];
-                a[(piv * 9 + k) * S] = tmp;
-            }
-        const double pv = a[(c * 9 + c) * S];
-        for (int r = c + 1; r < 8; ++r) {
-            const double f = a[(r * 9 + c) * S] / pv;
-            for (int k = c + 1; k < 9; ++k) a[(r * 9 + k) * S] = a[(r * 9 + k) * S] - f * a[(c * 9 + k) * S];
-        }
-    }
-#pragma unroll
-    for (int r = 7; r >= 0; --r) {
-        double s = a[(r * 9 + 8) * S];
-#pragma unroll
-        for (int k = r + 1; k < 8; ++k) s = s - a[(r * 9 + k) * S] * x[k];
-        x[r] = s / a[(r * 9 + r) * S];
-    }
-    return true;
-}
-
-// hypothesis k of an item with m >= 8 matches: four draws, void on a repeat; the 4-point system into a[(.) * S]; solved into h
-template <int S>
-__device__ __forceinline__ bool ft_hypothesis(const double* __restrict__ mc, int m, uint32_t seed, int k, double* __restrict__ a, double (&h)[8]) {
-    const uint32_t key = ft_fmix32(seed ^ ft_fmix32((uint32_t)k));
-    int idx[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) idx[t] = (int)(ft_fmix32(key ^ (uint32_t)(t + 1)) % (uint32_t)m);
-    if (idx[0] == idx[1] || idx[0] == idx[2] || idx[0] == idx[3] || idx[1] == idx[2] || idx[1] == idx[3] || idx[2] == idx[3]) return false;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const double x = mc[4 * idx[t]], y = mc[4 * idx[t] + 1], u = mc[4 * idx[t] + 2], v = mc[4 * idx[t] + 3];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) a[((2 * t) * 9 + c) * S] = ft_row0(c, x, y, u), a[((2 * t + 1) * 9 + c) * S] = ft_row1(c, x, y, v);
-    }
-    return ft_solve8<S>(a, h);
-}
-
-// a positive denominator and a squared one-sided reprojection error, in pixels, below thr^2
-__device__ __forceinline__ bool ft_inlier(const double (&h)[8], double x, double y, double u, double v, double sx, double sy, double thr2) {
-    const double den = (h[6] * x + h[7] * y) + 1.0;
-    if (!(den > 0.0)) return false;
-    const double px = ((h[0] * x + h[1] * y) + h[2]) / den, py = ((h[3] * x + h[4] * y) + h[5]) / den;
-    const double ex = (px - u) * sx, ey = (py - v) * sy;
-    return ex * ex + ey * ey < thr2;
 }
 
 // scores int32 [B, max_hyp]: inliers of hypothesis k, -1 when it is void (all of them with fewer than 8 matches)
@@ -402,23 +269,6 @@ __global__ void __launch_bounds__(64) ft_hyp_kernel(const double* __restrict__ m
             for (int e = 0; e < n; ++e) score += ft_inlier(h, sa[4 * e], sa[4 * e + 1], sa[4 * e + 2], sa[4 * e + 3], sx, sy, thr2);
     }
     if (k < max_hyp) scores[(size_t)b * max_hyp + k] = ok ? score : -1;
-}
-
-__device__ __forceinline__ int ft_block_sum(int v, int* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return part[0] + part[1] + part[2] + part[3];
-}
-__device__ __forceinline__ int ft_block_max(int v, int* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return max(max(part[0], part[1]), max(part[2], part[3]));
 }
 
 __global__ void __launch_bounds__(FT_THREADS) ft_refit_kernel(const int32_t* __restrict__ kp1, const int32_t* __restrict__ kp2, const double* __restrict__ mc,
@@ -502,7 +352,7 @@ __global__ void __launch_bounds__(FT_THREADS) ft_refit_kernel(const int32_t* __r
         inliers = ft_block_sum(n, part);                     // (its barriers also order sm and sa between the rounds)
     }
     for (int p = t; p < N; p += FT_THREADS) mask[(size_t)b * N + p] = p < m ? sm[p] : 0;
-    if (t == 0) {
+    if (t == 0) {                                            // (features_common.h has this tail as ft_write_model; called from here the compiler schedules this kernel differently, and its code object is pinned)
         double h[9];
 #pragma unroll
         for (int c = 0; c < 8; ++c) h[c] = sh[c];
@@ -536,31 +386,6 @@ __global__ void __launch_bounds__(FT_THREADS) ft_refit_kernel(const int32_t* __r
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-struct ft_region {
-    const void* p;
-    int64_t bytes;
-    bool out;
-};
-
-// no null pointer; an output overlaps nothing
-static bool ft_regions_ok(const ft_region* r, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!r[i].p) return false;
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j) {
-            if (!r[i].out && !r[j].out) continue;
-            const uintptr_t a = (uintptr_t)r[i].p, b = (uintptr_t)r[j].p;
-            if (a < b + (uintptr_t)r[j].bytes && b < a + (uintptr_t)r[i].bytes) return false;
-        }
-    return true;
-}
-
-static bool ft_shape_ok(int B, int H, int W) {
-    return B >= 1 && B <= FT_MAX_BATCH && H >= FT_MIN_SIDE && H <= FT_MAX_SIDE && W >= FT_MIN_SIDE && W <= FT_MAX_SIDE;
-}
-static int ft_cells(int side) { return (side + FT_CELL - 1) / FT_CELL; }
-static int ft_slots(int H, int W) { return FT_PER_CELL * ft_cells(H) * ft_cells(W); }
-
 // workspace of st_feature_homography, every region rounded up to 16 bytes: box uint16 [2,B,H,W]; kp int32 [2,B,N,2]; desc uint32 [2,B,N,8];
 // nn int32 [2,B,N,3]; matches int32 [B,N,2]; count int32 [B]; mc fp64 [B,N,4]; scores int32 [B,max_hyp]; mask uint8 [B,N]
 struct ft_layout {
@@ -589,11 +414,16 @@ static int ft_launch_describe(const uint16_t* box, const int32_t* kp, int n2, in
     ST_CHECK_LAUNCH();
     return ST_OK;
 }
-static int ft_launch_match(const int32_t* kp1, const uint32_t* desc1, const int32_t* kp2, const uint32_t* desc2, int B, int N, int32_t* nn, int32_t* matches,
-                           int32_t* count, hipStream_t s) {
+int ft_launch_match(const int32_t* kp1, const uint32_t* desc1, const int32_t* kp2, const uint32_t* desc2, int B, int N, int32_t* nn, int32_t* matches, int32_t* count,
+                    hipStream_t s) {
     ft_match_kernel<<<dim3((N + 31) / 32, 2, B), FT_THREADS, 0, s>>>(kp1, desc1, kp2, desc2, B, N, nn);
     ST_CHECK_LAUNCH();
     ft_compact_kernel<<<B, 1024, 0, s>>>(nn, B, N, matches, count);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}
+int ft_launch_hyp(const double* mc, const int32_t* count, int B, int H, int W, int N, int max_hyp, uint32_t seed, double thr2, int32_t* scores, hipStream_t s) {
+    ft_hyp_kernel<<<dim3((max_hyp + 63) / 64, B), 64, 0, s>>>(mc, count, H, W, N, max_hyp, seed, thr2, scores);
     ST_CHECK_LAUNCH();
     return ST_OK;
 }
@@ -603,15 +433,11 @@ static int ft_launch_ransac(const int32_t* kp1, const int32_t* kp2, const int32_
     const double thr2 = thr * thr;
     ft_norm_kernel<<<dim3((N + FT_THREADS - 1) / FT_THREADS, B), FT_THREADS, 0, s>>>(kp1, kp2, matches, count, H, W, N, mc);
     ST_CHECK_LAUNCH();
-    ft_hyp_kernel<<<dim3((max_hyp + 63) / 64, B), 64, 0, s>>>(mc, count, H, W, N, max_hyp, seed, thr2, scores);
-    ST_CHECK_LAUNCH();
+    const int rc = ft_launch_hyp(mc, count, B, H, W, N, max_hyp, seed, thr2, scores, s);
+    if (rc) return rc;
     ft_refit_kernel<<<B, FT_THREADS, 0, s>>>(kp1, kp2, mc, count, scores, H, W, N, max_hyp, seed, thr2, min_inliers, motion, Hout, info, mask);
     ST_CHECK_LAUNCH();
     return ST_OK;
-}
-
-static bool ft_params_ok(int max_hyp, double thr, int min_inliers) {
-    return max_hyp >= 1 && max_hyp <= FT_MAX_HYP && thr > 0.0 && thr <= 1.7e308 && min_inliers >= 0;       // (a NaN thr fails both comparisons)
 }
 
 extern "C" int st_feature_slots(int32_t H, int32_t W) { return ft_shape_ok(1, H, W) ? ft_slots(H, W) : 0; }

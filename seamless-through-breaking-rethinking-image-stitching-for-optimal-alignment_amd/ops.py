@@ -1878,6 +1878,174 @@ def feature_homography(img1, img2, *, max_hyp=2048, thr=3.0, min_inliers=12, see
     return motion, Hm, info, fields
 
 
+# ---- feature_align_ms: oriented, multi-scale keypoints in front of the same matching and RANSAC (csrc/features_ms.hip; README.md, feature_align_ms) ----
+FEATURE_MS_MAX_LEVELS = 8
+_FEATURE_MS_REGIONS = ("pyr", "box", "kp", "bins", "desc", "nn", "matches", "count", "xy", "mc", "scores", "mask", "total")
+
+
+def _feature_ms_levels(levels):
+    if int(levels) != levels or not 1 <= int(levels) <= FEATURE_MS_MAX_LEVELS:
+        raise ValueError(f"levels must be an integer in 1..{FEATURE_MS_MAX_LEVELS}, got {levels}")
+    return int(levels)
+
+
+def feature_ms_level_sizes(H, W, levels=6):
+    """[(H_l, W_l)] of the pyramid: level l+1 exists iff l+1 < levels and min(4 H_l div 5, 4 W_l div 5) >= 64; [] for a rejected argument"""
+    buf = (C.c_int32 * 16)()
+    n = int(lib.st_feature_ms_level_sizes(int(H), int(W), int(levels), C.cast(buf, C.c_void_p)))
+    return [(int(buf[2 * l]), int(buf[2 * l + 1])) for l in range(n)]
+
+
+def feature_ms_slots(H, W, levels=6):
+    """N = the keypoint slots of all levels, level 0 first; 0 for a rejected argument"""
+    return int(lib.st_feature_ms_slots(int(H), int(W), int(levels)))
+
+
+def feature_ms_workspace_bytes(B, H, W, levels=6, max_hyp=2048):
+    """bytes of workspace `feature_homography_ms` needs; 0 for an argument outside the contract"""
+    return int(lib.st_feature_ms_workspace_bytes(int(B), int(H), int(W), int(levels), int(max_hyp)))
+
+
+def feature_ms_workspace_layout(B, H, W, levels=6, max_hyp=2048):
+    """{region: byte offset} of that workspace (include/stitch_gfx950.h, st_feature_ms_workspace_layout) and its "total" """
+    off = (C.c_int64 * 13)()
+    check(lib.st_feature_ms_workspace_layout(int(B), int(H), int(W), int(levels), int(max_hyp), C.cast(off, C.c_void_p)), "st_feature_ms_workspace_layout")
+    return dict(zip(_FEATURE_MS_REGIONS, (int(v) for v in off)))
+
+
+def _feature_ms_split(flat, n, sizes):
+    """a flat level-major buffer of n planes per level -> [view [n,H_l,W_l]]"""
+    out, at = [], 0
+    for h, w in sizes:
+        out.append(flat[at:at + n * h * w].view(n, h, w))
+        at += n * h * w
+    return out
+
+
+def _feature_ms_join(planes, name, dtype, n, sizes):
+    if len(planes) != len(sizes):
+        raise ValueError(f"{name}: {len(sizes)} levels expected, got {len(planes)}")
+    for p, (h, w) in zip(planes, sizes):
+        _feature_operand(p, name, dtype, (n, h, w))
+    return torch.cat([p.reshape(-1) for p in planes])
+
+
+def feature_ms_pyramid(img, levels=6):
+    """Stage 1 (README.md, feature_align_ms): img fp32 [B,3,H,W] -> [uint8 [B,H_l,W_l]]: the luma, then each level the centre-aligned x 5/4 resample of the one before"""
+    B, H, W = _feature_image(img)
+    sizes = feature_ms_level_sizes(H, W, _feature_ms_levels(levels))
+    flat = torch.empty(B * sum(h * w for h, w in sizes), dtype=torch.uint8, device=img.device)
+    check(lib.st_feature_ms_pyramid(_pc(img), B, H, W, int(levels), _p(flat), _stream()), "st_feature_ms_pyramid")
+    return _feature_ms_split(flat, B, sizes)
+
+
+def feature_ms_detect(pyr, levels=6, oriented=True):
+    """Stage 2: the pyramid of `feature_ms_pyramid` -> (kp int32 [B,N,2] in each slot's level pixels, (-1, -1) unused; bins uint8 [B,N], the orientation
+    bin 0..31 of every slot; box: [int16 [B,H_l,W_l]], the 5x5 box sums `feature_ms_describe` reads)"""
+    B, H, W = pyr[0].shape
+    _feature_shape(B, H, W)
+    sizes = feature_ms_level_sizes(H, W, _feature_ms_levels(levels))
+    flat = _feature_ms_join(pyr, "pyr", torch.uint8, B, sizes)
+    N, dev = feature_ms_slots(H, W, levels), flat.device
+    kp = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
+    bins = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    box = torch.empty(flat.numel(), dtype=torch.int16, device=dev)
+    check(lib.st_feature_ms_detect(_pc(flat), B, H, W, int(levels), int(bool(oriented)), _p(kp), _p(bins), _p(box), _stream()), "st_feature_ms_detect")
+    return kp, bins, _feature_ms_split(box, B, sizes)
+
+
+def feature_ms_describe(box, kp, bins, levels=6):
+    """Stage 3: -> desc uint32 [B,N,8] (as int32 bit patterns): the BRIEF pattern steered by each slot's bin, on its level's box sums"""
+    B, H, W = box[0].shape
+    _feature_shape(B, H, W)
+    sizes = feature_ms_level_sizes(H, W, _feature_ms_levels(levels))
+    flat = _feature_ms_join(box, "box", torch.int16, B, sizes)
+    N = feature_ms_slots(H, W, levels)
+    _feature_operand(kp, "kp", torch.int32, (B, N, 2))
+    _feature_operand(bins, "bins", torch.uint8, (B, N))
+    desc = torch.empty((B, N, 8), dtype=torch.int32, device=flat.device)
+    check(lib.st_feature_ms_describe(_pc(flat), _pc(kp), _pc(bins), B, H, W, int(levels), _p(desc), _stream()), "st_feature_ms_describe")
+    return desc
+
+
+def feature_ms_match(kp1, desc1, kp2, desc2, H, W, levels=6):
+    """Stage 4: `feature_match` over the slots of all levels -> (nn int32 [2,B,N,3], matches int32 [B,N,2], count int32 [B])"""
+    B = kp1.shape[0]
+    _feature_shape(B, H, W)
+    N = feature_ms_slots(H, W, _feature_ms_levels(levels))
+    for k, d, n in ((kp1, desc1, "1"), (kp2, desc2, "2")):
+        _feature_operand(k, "kp" + n, torch.int32, (B, N, 2))
+        _feature_operand(d, "desc" + n, torch.int32, (B, N, 8))
+    dev = kp1.device
+    nn = torch.empty((2, B, N, 3), dtype=torch.int32, device=dev)
+    matches = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib.st_feature_ms_match(_pc(kp1), _pc(desc1), _pc(kp2), _pc(desc2), B, H, W, int(levels), _p(nn), _p(matches), _p(count), _stream()), "st_feature_ms_match")
+    return nn, matches, count
+
+
+def feature_ms_ransac(kp1, kp2, matches, count, H, W, levels=6, *, max_hyp=2048, thr=3.0, min_inliers=12, seed=1):
+    """Stage 5: `feature_ransac` on level-0 coordinates -> (motion fp32 [B,4,2], H fp32 [B,3,3], info int32 [B,8], mask uint8 [B,N], xy fp64 [2,B,N,2]:
+    the level-0 position of every slot of both images, (-1, -1) unused)."""
+    B = kp1.shape[0]
+    _feature_shape(B, H, W)
+    max_hyp, thr, min_inliers = _feature_params(max_hyp, thr, min_inliers)
+    N = feature_ms_slots(H, W, _feature_ms_levels(levels))
+    _feature_operand(kp1, "kp1", torch.int32, (B, N, 2))
+    _feature_operand(kp2, "kp2", torch.int32, (B, N, 2))
+    _feature_operand(matches, "matches", torch.int32, (B, N, 2))
+    _feature_operand(count, "count", torch.int32, (B,))
+    dev = kp1.device
+    motion = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
+    Hm = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+    info = torch.empty((B, 8), dtype=torch.int32, device=dev)
+    mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    xy = torch.empty((2, B, N, 2), dtype=torch.float64, device=dev)
+    ws = torch.empty(32 * B * N + 4 * B * max_hyp, dtype=torch.uint8, device=dev)
+    check(lib.st_feature_ms_ransac(_pc(kp1), _pc(kp2), _pc(matches), _pc(count), B, H, W, int(levels), max_hyp, thr, min_inliers, _feature_seed(seed), _p(motion), _p(Hm),
+                                   _p(info), _p(mask), _p(xy), _p(ws), ws.numel(), _stream()), "st_feature_ms_ransac")
+    return motion, Hm, info, mask, xy
+
+
+def feature_homography_ms(img1, img2, *, levels=6, oriented=True, max_hyp=2048, thr=3.0, min_inliers=12, seed=1, workspace=None, return_fields=False):
+    """`feature_homography` for rotated and zoomed pairs (README.md, feature_align_ms; this project's own contract, pinned against no library):
+    corners on ``levels`` levels of a 5/4 pyramid (capped by the size), a 32-bin orientation per corner (``oriented``) that steers the
+    descriptor, then the same matching over all slots and the same RANSAC on level-0 coordinates.  Operands, results, ``max_hyp``, ``thr``,
+    ``min_inliers``, ``seed`` and ``info`` as `feature_homography`; ``workspace`` at least `feature_ms_workspace_bytes` bytes, 16-byte
+    aligned.  ``return_fields``: also a dict of copies of the workspace's regions after the call: what `feature_homography` returns (kp in
+    each slot's level pixels) and pyr1, pyr2 [uint8 [B,H_l,W_l]], bins1, bins2 uint8 [B,N], xy fp64 [2,B,N,2] (level-0 coordinates).  All
+    launches go to the current stream and nothing is read back."""
+    B, H, W = _feature_image(img1, "img1")
+    if img2.shape != img1.shape or img2.dtype != torch.float32 or img2.device != img1.device:
+        raise ValueError(f"img2: float32 {tuple(img1.shape)} on {img1.device} expected, got {img2.dtype} {tuple(img2.shape)} on {img2.device}")
+    levels = _feature_ms_levels(levels)
+    max_hyp, thr, min_inliers = _feature_params(max_hyp, thr, min_inliers)
+    dev = img1.device
+    if workspace is None:
+        workspace = torch.empty(feature_ms_workspace_bytes(B, H, W, levels, max_hyp), dtype=torch.uint8, device=dev)
+    motion = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
+    Hm = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+    info = torch.empty((B, 8), dtype=torch.int32, device=dev)
+    check(lib.st_feature_ms_homography(_pc(img1), _pc(img2), B, H, W, levels, int(bool(oriented)), max_hyp, thr, min_inliers, _feature_seed(seed), _p(motion), _p(Hm),
+                                       _p(info), _p(workspace), workspace.numel() * workspace.element_size(), _stream()), "st_feature_ms_homography")
+    if not return_fields:
+        return motion, Hm, info
+    N, L, raw = feature_ms_slots(H, W, levels), feature_ms_workspace_layout(B, H, W, levels, max_hyp), workspace.view(torch.uint8).reshape(-1)
+    sizes = feature_ms_level_sizes(H, W, levels)
+
+    def region(name, nbytes, dtype, shape):
+        return raw[L[name]:L[name] + nbytes].view(dtype).reshape(shape).clone()
+    kp = region("kp", 16 * B * N, torch.int32, (2, B, N, 2))
+    desc = region("desc", 64 * B * N, torch.int32, (2, B, N, 8))
+    bins = region("bins", 2 * B * N, torch.uint8, (2, B, N))
+    pyr = _feature_ms_split(region("pyr", 2 * B * sum(h * w for h, w in sizes), torch.uint8, (-1,)), 2 * B, sizes)
+    fields = dict(kp1=kp[0], kp2=kp[1], desc1=desc[0], desc2=desc[1], bins1=bins[0], bins2=bins[1], pyr1=[p[:B] for p in pyr], pyr2=[p[B:] for p in pyr],
+                  nn=region("nn", 24 * B * N, torch.int32, (2, B, N, 3)), matches=region("matches", 8 * B * N, torch.int32, (B, N, 2)),
+                  count=region("count", 4 * B, torch.int32, (B,)), mask=region("mask", B * N, torch.uint8, (B, N)),
+                  xy=region("xy", 32 * B * N, torch.float64, (2, B, N, 2)))
+    return motion, Hm, info, fields
+
+
 # ---- dense_flow: coarse-to-fine, zero-mean Lucas-Kanade residual flow on integer pyramids (csrc/dense_flow.hip; README.md, dense_flow) ------
 DENSE_FLOW_MIN_SIDE, DENSE_FLOW_MAX_SIDE, DENSE_FLOW_MAX_BATCH, DENSE_FLOW_MAX_LEVELS = 16, 1024, 64, 8
 DENSE_FLOW_MAX_ITERS, DENSE_FLOW_MAX_RADIUS, DENSE_FLOW_MAX_DAMPING = 16, 7, 1 << 24
