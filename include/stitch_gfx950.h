@@ -873,7 +873,12 @@ int st_seam_gc_begin(const float* img1, const float* img2, const float* mask1, c
  * gather-relabel sweeps, then 8 launches of the global relabel (64 label sweeps inside a tile each) and the status record: 73 launches.
  * While a relabel has not reached its fixpoint (status word 1) the sweeps of a round do nothing and the round only continues the relabel;
  * st_seam_gc_relabel is that round without the idle launches: 16 launches of the relabel and the status record, 17 launches.  After done
- * neither changes anything.  Both count as a round in the status record.                                                            */
+ * neither changes anything.  Both count as a round in the status record.
+ * PRECONDITION (not checked: the state lives in device memory): the workspace holds what st_seam_gc_begin and the rounds since wrote for
+ * this H and W, untouched by anyone else.  A positive residual names a neighbour, and the setup gives none across the canvas edge; a
+ * workspace that st_seam_gc_begin never initialised may hold one there, and the push and gather kernels of st_seam_gc_round would follow it
+ * up to W words outside a label plane.  st_seam_gc_relabel and st_seam_gc_finish form no address from the workspace's contents, but what
+ * they compute on such a workspace is undefined.                                                                                     */
 int st_seam_gc_round(int32_t H, int32_t W, void* workspace, int64_t workspace_bytes, void* stream);
 int st_seam_gc_relabel(int32_t H, int32_t W, void* workspace, int64_t workspace_bytes, void* stream);
 /* side_out uint8 [H,W], info_out int32 [4] = (valid, 3, cut >> 31, cut & (2^31 - 1)); when the status record does not say done: valid =
@@ -1015,8 +1020,10 @@ int st_dense_flow_workspace_layout(int32_t B, int32_t H, int32_t W, int32_t leve
 /* both pyramids into the V and m regions of `workspace` (at least the total above, 16-byte aligned).  L launches.                         */
 int st_dense_flow_pyramid(const float* img1, const float* img2, const float* mask1, int32_t mask1_channels, const float* mask2, int32_t mask2_channels,
                           int32_t B, int32_t H, int32_t W, int32_t levels, void* workspace, int64_t workspace_bytes, void* stream);
-/* one iteration at one level of H x W (sides 16..1024): v1, v2 int16 [B,H,W], m1, m2 uint8 [B,H,W], u int32 [B,2,H,W] -> u_out int32
- * [B,2,H,W] (the update, then the 3x3 median), support_out uint8 [B,H,W].  workspace: at least 8 B H W bytes, 16-byte aligned.  2 launches. */
+/* one iteration at one level of H x W (sides 16..1024): v1, v2 int16 [B,H,W], m1, m2 uint8 [B,H,W] (set iff nonzero), u int32 [B,2,H,W]
+ * -> u_out int32 [B,2,H,W] (the update, then the 3x3 median), support_out uint8 [B,H,W].  workspace: at least 8 B H W bytes, 16-byte
+ * aligned.  2 launches.  u is data: a sample position outside 0..W-2 x 0..H-2 reads nothing and the pixel carries no weight; the result is
+ * defined for |u| <= 2^31 - 1 - 256 * 1023 - 256 (256 x + u and u + du stay inside int32).                                              */
 int st_dense_flow_iterate(const int16_t* v1, const int16_t* v2, const uint8_t* m1, const uint8_t* m2, const int32_t* u, int32_t B, int32_t H, int32_t W,
                           int32_t radius, int32_t damping, int32_t* u_out, uint8_t* support_out, void* workspace, int64_t workspace_bytes, void* stream);
 /* flow_out float32 [B,2,H,W] = (dx, dy) with img1(p) ~ img2(p + flow(p)), exactly U / 256 of level 0; support_out uint8 [B,H,W]: the

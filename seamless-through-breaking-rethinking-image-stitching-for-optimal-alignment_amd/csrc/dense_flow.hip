@@ -97,10 +97,10 @@ __global__ void __launch_bounds__(DF_THREADS) df_iterate_kernel(const int16_t* _
             const size_t ql = (size_t)y * W + xl, qr = (size_t)y * W + xr, qu = (size_t)yu * W + x, qd = (size_t)yd * W + x;
             const int sx = 256 * x + ux[q], sy = 256 * y + uy[q];
             const int xs = sx >> 8, fx = sx & 255, ys = sy >> 8, fy = sy & 255;
-            w = m1[q] & m1[ql] & m1[qr] & m1[qu] & m1[qd];
+            w = (m1[q] != 0) & (m1[ql] != 0) & (m1[qr] != 0) & (m1[qu] != 0) & (m1[qd] != 0);   // (a mask byte is set iff nonzero: w is 0 or 1, it is summed below)
             if (w && xs >= 0 && xs <= W - 2 && ys >= 0 && ys <= H - 2) {
                 const size_t p = (size_t)ys * W + xs;
-                if (m2[p] & m2[p + 1] & m2[p + W] & m2[p + W + 1]) {
+                if ((m2[p] != 0) & (m2[p + 1] != 0) & (m2[p + W] != 0) & (m2[p + W + 1] != 0)) {
                     const int J = ((256 - fx) * (256 - fy) * v2[p] + fx * (256 - fy) * v2[p + 1] + (256 - fx) * fy * v2[p + W] + fx * fy * v2[p + W + 1] + (1 << 15)) >> 16;
                     gx = v1[qr] - v1[ql], gy = v1[qd] - v1[qu], it = J - v1[q];
                 } else

@@ -129,7 +129,8 @@ def median3(U):
 
 
 def update(V1, V2, m1, m2, U, r, damping, defects=NONE):
-    """the Jacobi update before the median: -> (U + dU int64 [2,H,W], supported uint8 [H,W])"""
+    """the Jacobi update before the median: -> (U + dU int64 [2,H,W], supported uint8 [H,W]); a mask byte is set iff nonzero"""
+    m1, m2 = (np.asarray(m1) != 0).astype(np.int64), (np.asarray(m2) != 0).astype(np.int64)
     gx, gy, w1 = gradients(V1, m1)
     J, w2 = sample(V2, m2, U[0], U[1], defects)
     w = w1 & w2
