@@ -130,7 +130,8 @@ int st_set_gemm_observer(void* callback, void* user);
  *   plan4[0] kernel family (0 skinny_gemm, 1 narrow_conv, 2 conv_gemm_kernel [register-staged], 3 conv_gemm_dma_kernel,
  *            4 rowstream_gemm_kernel, 5 rowchain128_kernel [st_linear_chain128, reported to the observer as M x 128L x 128],
  *            6 rowmlp128_kernel [st_mlp128, reported as M x 2 hidden x 128], 7 patch_c0c2_kernel [st_patch_conv12], 8 conv_gemm_split3_kernel
- *            [st_gemm_desc.split3: tile_cfg 31..37], 9 rowmlp128_split3_kernel [st_mlp128_split3], 10 rowlin128_split3_kernel [st_rowlin128_split3], 11 pe_tail_split3_kernel [st_pe_tail_split3])
+ *            [st_gemm_desc.split3: tile_cfg 31..37], 9 rowmlp128_split3_kernel [st_mlp128_split3], 10 rowlin128_split3_kernel [st_rowlin128_split3], 11 pe_tail_split3_kernel [st_pe_tail_split3],
+ *            12 latent_self_attn_split3_kernel [st_latent_self_attn_split3])
  *   plan4[1] tile_cfg actually used, plan4[2] split_k actually used, plan4[3] 1 = persistent M walk, 2 / 3 = first / second
  *            member of an st_conv_gemm_pair launch (one dispatch, reported with the second member).
  * Used by tools/gemm_shapes_csv.py to label every launch of a step (profiles/r2_gemm_shapes.csv). */
@@ -226,6 +227,18 @@ int st_rowlin128_split3_image_bytes(int32_t N, int64_t* bytes);
 int st_rowlin128_split3_pack(const float* w, const float* b, int32_t N, void* image, int64_t image_bytes, void* stream);
 int st_rowlin128_split3(const float* a, int32_t lda, float* out, int32_t ldo, int32_t M, int32_t N, int32_t ln, float ln_eps, const void* image,
                         int64_t image_bytes, const float* aux, int32_t ld_aux, int32_t row_div, void* stream);
+/* The latent self-attention of the cost encoder (encoder.py:156-162) in one launch (csrc/mlp_split3.h, latent_self_attn_split3_kernel):
+ *   q | k | v = LayerNorm(a)[M, 128] . w^T + b  (w [384, 128] = the q, k, v rows, b [384] or NULL),  out[M, 128] = softmax(scale q k^T) v per group of
+ * 8 consecutive rows (the 8 latents of a cost map) and per head (8 heads of 16 features).  The [M, 384] q | k | v tensor is never written.  The
+ * products are st_rowlin128_split3's and the row arithmetic is st_attention_small's (one device function, csrc/attn_small.h): the result equals
+ * st_rowlin128_split3 -> st_attention_small(B = M / 8, heads = 8, Nq = Nk = 8, D = 16) bit for bit.  M % 8 == 0; a, out, image 16-byte aligned;
+ * lda, ldo >= 128 and multiples of 4; out must not alias a; image_bytes exactly what st_latent_self_attn_split3_image_bytes reports
+ * (12 chunk images of 24 KiB in the order q_c, k_c, v_c, c = 0..3, then the 384 bias floats in the same order).  plan4[0] = 12; reported to
+ * the observer as M x 384 x 128 with split3 = 1.                                                                                        */
+int st_latent_self_attn_split3_image_bytes(int64_t* bytes);
+int st_latent_self_attn_split3_pack(const float* w, const float* b, void* image, int64_t image_bytes, void* stream);
+int st_latent_self_attn_split3(const float* a, int32_t lda, float* out, int32_t ldo, int32_t M, int32_t ln, float ln_eps, float scale,
+                               const void* image, int64_t image_bytes, void* stream);
 
 /* All-pairs correlation volume, MemoryEncoder.corr (encoder.py:359-369):
  *   f1, f2 [B, N, C] channels-last features -> vol [B, N1, N2] = f1 . f2^T (no scaling). */

@@ -48,7 +48,7 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=False):
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_split3.h"), os.path.join(CSRC, "mlp_split3.h"), os.path.join(CSRC, "tps_solve.h"), os.path.join(CSRC, "jpeg_dec_core.h"), os.path.join(CSRC, "jpeg_tables.h"), os.path.join(CSRC, "jpeg_huff_core.h"), os.path.join(CSRC, "jpeg_scan.h"), os.path.join(CSRC, "jpeg_rst_core.h"), os.path.join(CSRC, "features_common.h"), os.path.join(HERE, "..", "include", "stitch_gfx950.h")]
+    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_split3.h"), os.path.join(CSRC, "mlp_split3.h"), os.path.join(CSRC, "attn_small.h"),os.path.join(CSRC, "tps_solve.h"), os.path.join(CSRC, "jpeg_dec_core.h"), os.path.join(CSRC, "jpeg_tables.h"), os.path.join(CSRC, "jpeg_huff_core.h"), os.path.join(CSRC, "jpeg_scan.h"), os.path.join(CSRC, "jpeg_rst_core.h"), os.path.join(CSRC, "features_common.h"), os.path.join(HERE, "..", "include", "stitch_gfx950.h")]
     objs, jobs = [], []
     os.makedirs(os.path.join(CSRC, "_obj"), exist_ok=True)
     for src in SOURCES:

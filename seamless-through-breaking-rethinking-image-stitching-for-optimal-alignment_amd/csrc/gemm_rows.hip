@@ -2,8 +2,9 @@
 // operand layout while several layers are applied, so the intermediate activations never leave the CU.
 //   rowchain128_kernel   st_linear_chain128: up to three Linear(128 -> 128) layers (fp32 MFMA)
 //   rowmlp128_kernel     st_mlp128: [projection + residual ->] LayerNorm -> fc1 + GELU -> fc2 + residual(s) (fp32 MFMA)
-//   mlp_split3.h         the same block tail, LayerNorm -> Linear(128 -> N), and PatchEmbed's tail on the exact-split bf16 contraction
-//                        (rowmlp128_split3_kernel, rowlin128_split3_kernel, pe_tail_split3_kernel and their weight-image pack kernels)
+//   mlp_split3.h         the same block tail, LayerNorm -> Linear(128 -> N), the latent self-attention (LayerNorm -> q | k | v -> 8 x 8 attention) and
+//                        PatchEmbed's tail on the exact-split bf16 contraction (rowmlp128_split3_kernel, rowlin128_split3_kernel,
+//                        latent_self_attn_split3_kernel, pe_tail_split3_kernel and their weight-image pack kernels)
 // The loaders and vector types they share with the tiled kernels of gemm.hip / gemm_split3.hip are in gemm_common.h.
 #include "gemm_common.h"
 
@@ -583,6 +584,39 @@ extern "C" int st_rowlin128_split3(const float* a, int32_t lda, float* out, int3
     const bool obs = row_launch_begin(od, 10, 40, stream, a, lda, out, ldo, image, M, N, 1);
     hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, (hipStream_t)stream, a, (int)lda, out, (int)ldo, (int)M, (int)N, (int)ln, ln_eps,
                        (const unsigned char*)image, (unsigned)need, aux, (int)ld_aux, (int)(row_div > 0 ? row_div : 1));
+    if (obs) st_observe(&od, stream, 1);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}
+
+// The latent self-attention in one launch (csrc/mlp_split3.h, latent_self_attn_split3_kernel): out[M, 128] = attention(LayerNorm(a) . wqkv^T + bqkv) over
+// groups of 8 consecutive rows (the 8 latents of a cost map), 8 heads of 16; w [384, 128] = q | k | v rows, packed once into 12 chunk images + the bias
+extern "C" int st_latent_self_attn_split3_image_bytes(int64_t* bytes) {
+    if (!bytes) return ST_EINVAL;
+    *bytes = LA3_IMAGE_B;
+    return ST_OK;
+}
+extern "C" int st_latent_self_attn_split3_pack(const float* w, const float* b, void* image, int64_t image_bytes, void* stream) {
+    if (!w || !image || ((uintptr_t)image & 15) || image_bytes != LA3_IMAGE_B) return ST_EINVAL;
+    hipLaunchKernelGGL(latent_self_attn_split3_pack_kernel, dim3(3, LA3_STEPS), dim3(256), 0, (hipStream_t)stream, w, b, (unsigned char*)image);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}
+extern "C" int st_latent_self_attn_split3(const float* a, int32_t lda, float* out, int32_t ldo, int32_t M, int32_t ln, float ln_eps, float scale,
+                                          const void* image, int64_t image_bytes, void* stream) {
+    if (!a || !out || !image || M <= 0 || (M & 7) || lda < 128 || ldo < 128 || (lda & 3) || (ldo & 3) || a == out) return ST_EINVAL;
+    if ((((uintptr_t)a | (uintptr_t)out | (uintptr_t)image) & 15) || (int64_t)M * (lda > ldo ? lda : ldo) >= ((int64_t)1 << 40)) return ST_EINVAL;
+    if (image_bytes != LA3_IMAGE_B) return ST_EINVAL;
+    const int nblk = (M + 31) / 32;
+    int G = (nblk + 3) / 4;
+    if (G > 512) G = 512;                                       // 80 KB of LDS: two workgroups per CU
+    const size_t lds = (size_t)LA3_LDS_B;
+    (void)hipFuncSetAttribute((const void*)latent_self_attn_split3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    // reported to the observer as the projection it holds: M x 384 x 128
+    st_gemm_desc od;
+    const bool obs = row_launch_begin(od, 12, 42, stream, a, lda, out, ldo, image, M, 384, 1);
+    hipLaunchKernelGGL(latent_self_attn_split3_kernel, dim3(G), dim3(256), lds, (hipStream_t)stream, a, (int)lda, out, (int)ldo, (int)M, (int)ln, ln_eps,
+                       scale, (const unsigned char*)image);
     if (obs) st_observe(&od, stream, 1);
     ST_CHECK_LAUNCH();
     return ST_OK;

@@ -30,6 +30,7 @@
 // which the accumulator layout hands the values over; the packed weights follow it.
 #pragma once
 #include "gemm_common.h"
+#include "attn_small.h"
 
 #define MS3_W1_B 24576            // 3 planes x 32 rows x 256 B
 #define MS3_W2_B 24576            // 3 planes x 128 rows x 64 B
@@ -554,6 +555,208 @@ __global__ __launch_bounds__(256, 2) void rowlin128_split3_kernel(const float* _
                 }
             }
             g = g + 1 == 3 ? 0 : g + 1;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The latent self-attention of the cost encoder (encoder.py:156-162) as ONE launch: LayerNorm -> q | k | v projection (128 -> 384) -> the 8-latent,
+// 8-head, D = 16 attention of every cost map, rows [M * 8, 128] in, attention output [M * 8, 128] out.  Unfused, rowlin128_split3_kernel writes
+// q | k | v (384 floats per row) and attention_small_kernel<16> reads them back: 3 x the bytes of the rows, for an attention that never leaves a
+// wave's block -- the 8 latents of a cost map are 8 consecutive rows, a 32-row block is 4 whole cost maps.
+//   * the products are rowlin128_split3_kernel's (same planes, same k order, 48 MFMAs per 32-feature chunk), the chunks walked as
+//     (q_c, k_c, v_c), c = 0..3 -- a chunk is two heads -- and the weight rows of a chunk permuted by the pack kernel so that the accumulator
+//     slot 8 jj + 4 lh + t holds feature 16 lh + 4 jj + t: lane (li, lh) then owns the 16 features of head 2 c + lh of row li, e = 0..15 in
+//     its accumulator registers 0..15, which is attention_small_kernel's thread.  A chunk's products do not depend on the walk or on the slot:
+//     the q | k | v values are the unfused ones, bit for bit.
+//   * q stays in registers; k and v go to the wave's own LDS slab (2 x 4 KiB, 16-byte units XOR-swizzled by (head half, map) so that the eight
+//     (head, map) groups of a wave read eight different bank groups; the 8 lanes of a group read one address); no barrier: a wave reads only
+//     what it wrote itself.  The row's arithmetic is st_attn_small_row (csrc/attn_small.h), the function attention_small_kernel runs.
+//   * LDS: a TWO-stage ring of 24-KiB chunk images + 4 slabs = 80 KiB, two workgroups per CU as rowlin128_split3_kernel; the bias (which rides
+//     with the permutation) sits behind the 12 chunk images and comes by four 16-byte global loads per chunk, requested before the MFMAs.
+//   * stores: 64 bytes per lane and v chunk (the head's 16 outputs), 128 contiguous bytes per row.
+#define LA3_STAGE_B MS3_W1_B
+#define LA3_STEPS 12
+#define LA3_BIAS_OFF (LA3_STEPS * LA3_STAGE_B)
+#define LA3_IMAGE_B (LA3_BIAS_OFF + 384 * 4)
+#define LA3_SLAB_B 8192           // per wave: k 4 KiB | v 4 KiB
+#define LA3_LDS_B (2 * LA3_STAGE_B + 4 * LA3_SLAB_B)
+
+// grid (3, 12) x 256 threads: step s = 3 c + (0 q, 1 k, 2 v); blocks 0-1 the 512 slots of the chunk, 2 its 32 bias floats (head half lh: floats 16 lh + e)
+__global__ __launch_bounds__(256) void latent_self_attn_split3_pack_kernel(const float* __restrict__ w, const float* __restrict__ b, unsigned char* __restrict__ image) {
+    const int s = blockIdx.y, t = threadIdx.x;
+    const int f0 = (s % 3) * 128 + (s / 3) * 32;                // first feature of the chunk in q | k | v
+    if (blockIdx.x < 2) {
+        const int idx = blockIdx.x * 256 + t, r = idx >> 4, sl = idx & 15, ks = sl >> 1, lh = sl & 1;
+        const int feat = 16 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3);      // slot r = 8 jj + 4 lh' + t'  <-  feature 16 lh' + 4 jj + t'
+        const float* W = w + (size_t)(f0 + feat) * 128;
+        bf16x8 h, m, l;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            __bf16 a0, a1, a2;
+            st_split3(W[16 * ks + 8 * (e >> 2) + 4 * lh + (e & 3)], a0, a1, a2);
+            h[e] = a0; m[e] = a1; l[e] = a2;
+        }
+        unsigned char* o = image + (size_t)s * LA3_STAGE_B + r * 256 + ((sl ^ (r & 15)) << 4);
+        *reinterpret_cast<bf16x8*>(o) = h;
+        *reinterpret_cast<bf16x8*>(o + 8192) = m;
+        *reinterpret_cast<bf16x8*>(o + 16384) = l;
+    } else if (t < 32) {
+        reinterpret_cast<float*>(image + LA3_BIAS_OFF)[32 * s + t] = b ? b[f0 + t] : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void latent_self_attn_split3_kernel(const float* __restrict__ a, const int lda, float* __restrict__ out, const int ldo, const int M,
+                                                                         const int ln, const float ln_eps, const float scale, const unsigned char* __restrict__ image) {
+    extern __shared__ __attribute__((aligned(1024))) unsigned char sm3[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 31, lh = lane >> 5;
+    const int nblk = (M + 31) >> 5;
+    const int G = (int)gridDim.x;
+    const int blk0 = (int)blockIdx.x * 4;
+    const int rounds = blk0 < nblk ? (nblk - blk0 + G * 4 - 1) / (G * 4) : 0;
+    const int total = rounds * LA3_STEPS;
+    if (total == 0) return;
+    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)sm3;
+    const i32x4 rsd = make_rsrc(image, (unsigned)LA3_BIAS_OFF);
+    const unsigned vlin = (unsigned)lane << 4;
+    int s_dma = 0, g_dma = 0, q_dma = 0;
+    // (m0 is on the clobber lists: the compiler must not carry an M0 value of its own across the blocks; it notes that the register is reserved)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+    auto dma_step = [&]() {                                      // wave w: bytes [6 144 w, 6 144 (w + 1)) of the chunk as a run of four + a run of two
+        const unsigned dst = lds0 + (unsigned)(g_dma * LA3_STAGE_B), src = (unsigned)(s_dma * LA3_STAGE_B), o = (unsigned)wave * 6144u;
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\t"
+                     "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
+                     "buffer_load_dwordx4 %1, %2, %3 offen offset:1024 lds\n\t"
+                     "buffer_load_dwordx4 %1, %2, %3 offen offset:2048 lds\n\t"
+                     "buffer_load_dwordx4 %1, %2, %3 offen offset:3072 lds"
+                     : : "s"(dst + o), "v"(vlin), "s"(rsd), "s"(src + o) : "memory", "m0");
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\t"
+                     "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
+                     "buffer_load_dwordx4 %1, %2, %3 offen offset:1024 lds"
+                     : : "s"(dst + o + 4096u), "v"(vlin), "s"(rsd), "s"(src + o + 4096u) : "memory", "m0");
+        ++q_dma;
+        s_dma = s_dma + 1 == LA3_STEPS ? 0 : s_dma + 1;
+        g_dma ^= 1;
+    };
+#pragma clang diagnostic pop
+    dma_step();
+    int fo1[8];
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) fo1[ks] = li * 256 + (((2 * ks + lh) ^ (li & 15)) << 4);
+    // the wave's slab: group sg = (head half, cost map of the block), 512 bytes = 8 rows x 4 units of 16 bytes, unit (4 row + u) ^ (2 sg)
+    unsigned char* const slab = sm3 + 2 * LA3_STAGE_B + wave * LA3_SLAB_B;
+    const int sg = 4 * lh + (li >> 3), sgx = 2 * sg;
+    const int own = sg * 512, lr4 = 4 * (li & 7);
+    const float* const bias = reinterpret_cast<const float*>(image + LA3_BIAS_OFF) + 16 * lh;
+    int g = 0, step = 0;
+    for (int rd = 0; rd < rounds; ++rd) {
+        const int blk = blk0 + wave + rd * G * 4;
+        const bool active = blk < nblk;                         // wave-uniform; an idle wave still copies weights and meets the barriers
+        const int row = blk * 32 + li;
+        const bool rok = active && row < M;                     // (M % 8 == 0: a cost map is stored whole or not at all)
+        const size_t rowc = (size_t)(rok ? row : M - 1);
+        u32x4 xp[3][8];
+        if (active) {
+            float4 x[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) x[j] = *reinterpret_cast<const float4*>(a + rowc * lda + 8 * j + 4 * lh);
+            if (ln) {                                           // as rowlin128_split3_kernel
+                float s = 0.f;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) s += (x[j].x + x[j].y) + (x[j].z + x[j].w);
+                s += __shfl_xor(s, 32, 64);
+                const float mean = s * (1.0f / 128.0f);
+                float v = 0.f;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    x[j].x -= mean; x[j].y -= mean; x[j].z -= mean; x[j].w -= mean;
+                    v += (x[j].x * x[j].x + x[j].y * x[j].y) + (x[j].z * x[j].z + x[j].w * x[j].w);
+                }
+                v += __shfl_xor(v, 32, 64);
+                const float rstd = 1.0f / sqrtf(v * (1.0f / 128.0f) + ln_eps);
+#pragma unroll
+                for (int j = 0; j < 16; ++j) { x[j].x *= rstd; x[j].y *= rstd; x[j].z *= rstd; x[j].w *= rstd; }
+            }
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                unsigned h0, m0, l0, h1, m1, l1;
+                ms3_split_pair(x[j].x, x[j].y, h0, m0, l0);
+                ms3_split_pair(x[j].z, x[j].w, h1, m1, l1);
+                xp[0][j >> 1][2 * (j & 1)] = h0; xp[0][j >> 1][2 * (j & 1) + 1] = h1;
+                xp[1][j >> 1][2 * (j & 1)] = m0; xp[1][j >> 1][2 * (j & 1) + 1] = m1;
+                xp[2][j >> 1][2 * (j & 1)] = l0; xp[2][j >> 1][2 * (j & 1) + 1] = l1;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // one step of the walk: the chunk of ring stage g against the block, + bias -> val[e], e = 0..15 of head 2 c + lh.  `stores`: the four
+        // stores of the previous (v) step, younger than this wave's DMA pieces of the step, may still be in flight (an active wave always
+        // stores: its first row exists)
+        auto chunk = [&](const bool stores, float (&val)[16]) {
+            if (stores && active) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (q_dma < total) dma_step();
+            if (active) {
+                const unsigned char* ws_ = sm3 + g * LA3_STAGE_B;
+                float4 bv[4];
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) bv[jj] = *reinterpret_cast<const float4*>(bias + 32 * step + 4 * jj);
+                f32x16 acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+                u32x4 f[3], fn[3];
+#pragma unroll
+                for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const u32x4*>(ws_ + p * 8192 + fo1[0]);
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) {
+                    const int kn = ks + 1 < 8 ? ks + 1 : ks;
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) fn[p] = *reinterpret_cast<const u32x4*>(ws_ + p * 8192 + fo1[kn]);
+                    MS3_SIX(acc, f, xp[0][ks], xp[1][ks], xp[2][ks])
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) f[p] = fn[p];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    val[4 * jj] = acc[4 * jj] + bv[jj].x; val[4 * jj + 1] = acc[4 * jj + 1] + bv[jj].y;
+                    val[4 * jj + 2] = acc[4 * jj + 2] + bv[jj].z; val[4 * jj + 3] = acc[4 * jj + 3] + bv[jj].w;
+                }
+            }
+            g ^= 1;
+            step = step + 1 == LA3_STEPS ? 0 : step + 1;
+        };
+        auto to_slab = [&](const int off, const float (&val)[16]) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                *reinterpret_cast<float4*>(slab + off + own + (((lr4 + u) ^ sgx) << 4)) = make_float4(val[4 * u], val[4 * u + 1], val[4 * u + 2], val[4 * u + 3]);
+        };
+#pragma unroll 1
+        for (int c = 0; c < 4; ++c) {
+            float qv[16], kv[16], ov[16];
+            chunk(c > 0, qv);
+            chunk(false, kv);
+            if (active) to_slab(0, kv);
+            chunk(false, kv);
+            if (active) {
+                to_slab(4096, kv);
+                // the wave's own writes, read back by other lanes of the wave: LDS serves a wave's accesses in order
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                st_attn_small_row<16>(qv, scale, 8,
+                                      [&](int j, int e) { return *reinterpret_cast<const float4*>(slab + own + (((4 * j + (e >> 2)) ^ sgx) << 4)); },
+                                      [&](int j, int e) { return *reinterpret_cast<const float4*>(slab + 4096 + own + (((4 * j + (e >> 2)) ^ sgx) << 4)); }, ov);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (rok) {
+                    float* op = out + rowc * ldo + 32 * c + 16 * lh;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) *reinterpret_cast<float4*>(op + 4 * u) = make_float4(ov[4 * u], ov[4 * u + 1], ov[4 * u + 2], ov[4 * u + 3]);
+                }
+            }
         }
     }
 }

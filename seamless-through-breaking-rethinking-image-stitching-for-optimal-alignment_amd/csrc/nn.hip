@@ -2,6 +2,7 @@
 // HBM-bound elementwise and reduction work: 16-B accesses where the layout allows, wave-shuffle
 // reductions (64 lanes), K/V tiles staged in LDS for the attention variants.
 #include "common.h"
+#include "attn_small.h"
 #include "../../include/stitch_gfx950.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -294,56 +295,21 @@ __global__ __launch_bounds__(256) void attention_small_kernel(const float* __res
     const int iq = idx % Nq;
     const int h = (idx / Nq) % heads;
     const int b = idx / ((long)Nq * heads);
-    float qr[D], acc[D];
+    float qv[D], ov[D];
     const float* qp = q + b * q_bs + iq * q_ts + h * D;
 #pragma unroll
     for (int e = 0; e < D; e += 4) {
         const float4 t = *reinterpret_cast<const float4*>(qp + e);
-        // scale goes into q, as in the kvlds kernels: both passes below then run the SAME fma chain and the row maximum is one of the
-        // scores the second pass exponentiates.  With `s * scale` taken after the chain the compiler contracted the second pass to
-        // fma(s, scale, -mx) against a maximum of rounded products, so the top key's weight was exp(rounding residual) instead of 1
-        // whenever scale is not a power of two (D = 8, 32): Nk = 1 did not return the V row.  Same bits as before for D = 16.
-        qr[e] = t.x * scale; qr[e + 1] = t.y * scale; qr[e + 2] = t.z * scale; qr[e + 3] = t.w * scale;
+        qv[e] = t.x; qv[e + 1] = t.y; qv[e + 2] = t.z; qv[e + 3] = t.w;
     }
     const float* kb = k + b * k_bs + h * D;
     const float* vb = v + b * v_bs + h * D;
-    float mx = -INFINITY;
-    for (int j = 0; j < Nk; ++j) {
-        const float* kp = kb + j * k_ts;
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < D; e += 4) {
-            const float4 t = *reinterpret_cast<const float4*>(kp + e);
-            s = fmaf(qr[e], t.x, s); s = fmaf(qr[e + 1], t.y, s); s = fmaf(qr[e + 2], t.z, s); s = fmaf(qr[e + 3], t.w, s);
-        }
-        mx = fmaxf(mx, s);
-    }
-#pragma unroll
-    for (int e = 0; e < D; ++e) acc[e] = 0.f;
-    float sum = 0.f;
-    for (int j = 0; j < Nk; ++j) {
-        const float* kp = kb + j * k_ts;
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < D; e += 4) {
-            const float4 t = *reinterpret_cast<const float4*>(kp + e);
-            s = fmaf(qr[e], t.x, s); s = fmaf(qr[e + 1], t.y, s); s = fmaf(qr[e + 2], t.z, s); s = fmaf(qr[e + 3], t.w, s);
-        }
-        const float p = __expf(s - mx);
-        sum += p;
-        const float* vp = vb + j * v_ts;
-#pragma unroll
-        for (int e = 0; e < D; e += 4) {
-            const float4 t = *reinterpret_cast<const float4*>(vp + e);
-            acc[e] = fmaf(p, t.x, acc[e]); acc[e + 1] = fmaf(p, t.y, acc[e + 1]);
-            acc[e + 2] = fmaf(p, t.z, acc[e + 2]); acc[e + 3] = fmaf(p, t.w, acc[e + 3]);
-        }
-    }
-    const float inv = 1.0f / sum;
+    // the arithmetic of the row: csrc/attn_small.h (shared with the fused latent self-attention of csrc/mlp_split3.h)
+    st_attn_small_row<D>(qv, scale, Nk, [&](int j, int e) { return *reinterpret_cast<const float4*>(kb + j * k_ts + e); },
+                         [&](int j, int e) { return *reinterpret_cast<const float4*>(vb + j * v_ts + e); }, ov);
     float* op = out + b * o_bs + iq * o_ts + h * D;
 #pragma unroll
-    for (int e = 0; e < D; e += 4)
-        *reinterpret_cast<float4*>(op + e) = make_float4(acc[e] * inv, acc[e + 1] * inv, acc[e + 2] * inv, acc[e + 3] * inv);
+    for (int e = 0; e < D; e += 4) *reinterpret_cast<float4*>(op + e) = make_float4(ov[e], ov[e + 1], ov[e + 2], ov[e + 3]);
 }
 
 extern "C" int st_attention_small(const float* q, int64_t q_bs, int64_t q_ts, const float* k, int64_t k_bs, int64_t k_ts,

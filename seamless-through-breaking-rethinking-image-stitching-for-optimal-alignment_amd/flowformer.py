@@ -197,6 +197,8 @@ class FlowFormer(ParamTree):
                 d["qkv"] = cat_lin([name + ".q", name + ".k", name + ".v"])
                 d["qkv_ln"] = ops.fold_layernorm(*d["n1"], *d["qkv"])
                 d["qkv_s3"] = lin_image(d["qkv_ln"])
+                # LayerNorm -> q | k | v -> the 8 x 8 attention of every cost map in one launch: q | k | v never reach memory
+                d["attn_s3"] = ops.latent_self_attn_split3_pack(*d["qkv_ln"]) if d["qkv_s3"] is not None else None
             d["kv"] = cat_lin([name + ".k", name + ".v"])
             d["f0_ln"] = ops.fold_layernorm(*d["n2"], *d["f0"])
             # the latent layers' tails are the same operator as the Block tails with hidden = 128 (proj + residual -> LN -> ffn.0 + GELU -> ffn.3 + residual)
@@ -455,14 +457,17 @@ class FlowFormer(ParamTree):
         """a self-attention layer over the 8 latents of each of the M cost maps (encoder.py:156-172); x rows [M*8, 128]."""
         dev = x.device
         nl = self._pk["latents"].shape[0]
-        qkv = _new(M * nl, 384, dev)
-        if L.get("qkv_s3") is not None:
-            ops.rowlin128_split3(x, qkv, L["qkv_s3"], ln_eps=1e-5)
-        else:
-            ops.conv_gemm(x, L["qkv_ln"][0], qkv, bias=L["qkv_ln"][1], ln_eps=1e-5)
         att = _new(M * nl, 128, dev)
-        ops.attention_small(qkv[:, :128], (nl * 384, 384), qkv[:, 128:256], (nl * 384, 384), qkv[:, 256:], (nl * 384, 384),
-                            att, (nl * 128, 128), M, 8, nl, nl, 16, 16 ** -0.5)
+        if L.get("attn_s3") is not None and nl == 8:
+            ops.latent_self_attn_split3(x, att, L["attn_s3"], ln_eps=1e-5, scale=16 ** -0.5)
+        else:
+            qkv = _new(M * nl, 384, dev)
+            if L.get("qkv_s3") is not None:
+                ops.rowlin128_split3(x, qkv, L["qkv_s3"], ln_eps=1e-5)
+            else:
+                ops.conv_gemm(x, L["qkv_ln"][0], qkv, bias=L["qkv_ln"][1], ln_eps=1e-5)
+            ops.attention_small(qkv[:, :128], (nl * 384, 384), qkv[:, 128:256], (nl * 384, 384), qkv[:, 256:], (nl * 384, 384),
+                                att, (nl * 128, 128), M, 8, nl, nl, 16, 16 ** -0.5)
         # proj + residual -> LayerNorm -> ffn.0 + GELU -> ffn.3 + residual in ONE launch: x1 and the hidden activation
         # never leave the CU (encoder.py:163-172)
         o = _new(M * nl, 128, dev)

@@ -310,6 +310,25 @@ def rowlin128_split3(a, out, image, ln_eps=None, aux=None, row_div=1):
     return out
 
 
+def latent_self_attn_split3_pack(w, b):
+    """q | k | v weights [384, 128] (+ bias [384] or None) of a latent self-attention layer -> the image st_latent_self_attn_split3 streams (uint8 tensor)"""
+    assert w.shape == (384, 128) and w.is_contiguous() and (b is None or b.shape == (384,))
+    nb = C.c_int64(0)
+    check(lib.st_latent_self_attn_split3_image_bytes(C.byref(nb)), "st_latent_self_attn_split3_image_bytes")
+    img = torch.empty(nb.value, dtype=torch.uint8, device=w.device)
+    check(lib.st_latent_self_attn_split3_pack(_p(w), _p(b), C.c_void_p(img.data_ptr()), nb.value, _stream()), "st_latent_self_attn_split3_pack")
+    return img
+
+
+def latent_self_attn_split3(a, out, image, ln_eps=None, scale=16 ** -0.5):
+    """out[M * 8, 128] = the 8-latent, 8-head, D = 16 self-attention of every 8 consecutive rows of q | k | v = LayerNorm(a) @ w^T + b, one launch
+    (ln_eps None: no LayerNorm); the weights of `image` (latent_self_attn_split3_pack).  Same bits as rowlin128_split3 -> attention_small."""
+    assert a.shape[1] == 128 and out.shape == (a.shape[0], 128)
+    check(lib.st_latent_self_attn_split3(_p(a), _ld(a), _p(out), _ld(out), a.shape[0], 1 if ln_eps is not None else 0, float(ln_eps or 0.0), float(scale),
+                                         C.c_void_p(image.data_ptr()), image.numel(), _stream()), "st_latent_self_attn_split3")
+    return out
+
+
 def mlp128_split3_pack(w1, b1, w2, proj=None):
     """weights of one st_mlp128 -> the image st_mlp128_split3 streams (uint8 tensor; pack once per weight load).  proj = (wp, bp or None)."""
     hidden = w1.shape[0]
