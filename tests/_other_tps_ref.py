@@ -74,6 +74,88 @@ def f32_sum(a):
     return f(f32_sum(a[:n2]) + f32_sum(a[n2:]))
 
 
+def _f32_leaf(a):
+    """the block of f32_sum applied to a whole array, whatever its length"""
+    f = np.float32
+    n = len(a)
+    if n < 8:
+        r = f(0)
+        for v in a:
+            r = f(r + v)
+        return r
+    r = [a[j] for j in range(8)]
+    i = 8
+    while i < n - n % 8:
+        for j in range(8):
+            r[j] = f(r[j] + a[i + j])
+        i += 8
+    res = f(f(f(r[0] + r[1]) + f(r[2] + r[3])) + f(f(r[4] + r[5]) + f(r[6] + r[7])))
+    for v in a[i:]:
+        res = f(res + v)
+    return res
+
+
+# Three wrong summations, each one way a kernel's copy of f32_sum can go wrong while staying a sum (tests/test_other_tps_cpu.py shows
+# that the inputs of `case` tell every one of them from f32_sum; tests/test_other_tps_matrix_gpu.py leans on that).
+def sum_in_order(a):
+    """WRONG: one running float32 sum in index order.  Defined differently from f32_sum from 8 elements on."""
+    r = np.float32(0)
+    for v in np.asarray(a, np.float32):
+        r = np.float32(r + v)
+    return r
+
+
+def sum_leaf_no_split(a):
+    """WRONG: the eight-lane block over the whole array, never halved.  Defined differently from f32_sum above 128 elements."""
+    return _f32_leaf(np.asarray(a, np.float32))
+
+
+def sum_halves_unrounded(a):
+    """WRONG: the halving recursion with n2 = n // 2, not rounded down to a multiple of 8.  Defined differently from f32_sum
+    wherever unrounded_halves_differ(len(a))."""
+    a = np.asarray(a, np.float32)
+    n = len(a)
+    if n <= 128:
+        return _f32_leaf(a)
+    return np.float32(sum_halves_unrounded(a[:n // 2]) + sum_halves_unrounded(a[n // 2:]))
+
+
+def unrounded_halves_differ(m):
+    """whether sum_halves_unrounded splits m elements differently from f32_sum at any level (129, 256 and 512 do not)"""
+    if m <= 128:
+        return False
+    h = m // 2
+    return h % 8 != 0 or unrounded_halves_differ(h) or unrounded_halves_differ(m - h)
+
+
+# The control-point counts of the teacher-forced maps tests.  n - 1 elements are summed for w_0: 0, fewer than 8, exactly 8, 8 plus
+# a tail (1..17); the 128-element block limit and the first split, 129 = 64 + 65 (129, 130); 136 and 137 elements, whose halves are
+# (64 + 72) and are not (64 + 73) multiples of 8; both sides of the staging chunk of 256 centres (255..264) and a partial third chunk
+# (513); 2055, the right half of 4095, which itself splits off a 1031; the accepted maximum 4096.
+N_TABLE = (1, 2, 3, 8, 9, 10, 17, 128, 129, 130, 137, 138, 255, 256, 257, 264, 300, 512, 513, 1031, 2055, 4095, 4096)
+CASE_SEED = {}                      # n -> seed, where 7000 + n does not meet the conditions of tests/test_other_tps_cpu.py (none so far)
+PROBE_R = 3.0
+
+
+def case(n):
+    """-> (kw [n,2], aw [3,2], centres [n,2]) float32, seeded by n: weights small enough that the map stays a map, large enough
+    that the spline term, not the affine one, decides its last bits"""
+    rng = np.random.default_rng(CASE_SEED.get(n, 7000 + n))
+    kw = (0.05 * rng.standard_normal((n, 2))).astype(np.float32)
+    aw = (0.01 * rng.standard_normal((3, 2))).astype(np.float32)
+    centres = rng.uniform(-0.1, 1.1, (n, 2)).astype(np.float32)
+    return kw, aw, centres
+
+
+def probe_case(n):
+    """the w_0 probe on a 1 x 1 canvas (x = y = 0): centres 1..n-1 at the origin, where U(0) = 0 exactly, centre 0 at (PROBE_R, 0)
+    and no affine part, so that the maps are float32(U(PROBE_R) * w_0[axis]) and nothing else"""
+    kw = case(n)[0]
+    centres = np.zeros((n, 2), np.float32)
+    centres[0, 0] = PROBE_R
+    return kw, np.zeros((3, 2), np.float32), centres
+
+
 def reduce_w0(kw):
     """w_0 = -sum_{i>=1} w_i as the reference computes it: np.sum of the float32 weights (other_tps.py TPS.z)"""
     kw = np.asarray(kw, np.float32).copy()
@@ -120,8 +202,9 @@ def quantise_map(m):
     return X >> 5, X & 31, ok
 
 
-def remap_cubic(planes_u8, mapx, mapy, table):
-    """cv2.remap(INTER_CUBIC, BORDER_CONSTANT 0) on integer planes [P,Hs,Ws] -> int32 [P,H,W] in 0..255"""
+def remap_cubic(planes_u8, mapx, mapy, table, saturate=True):
+    """cv2.remap(INTER_CUBIC, BORDER_CONSTANT 0) on integer planes [P,Hs,Ws] -> int32 [P,H,W] in 0..255
+    (saturate=False: the rounded sum before the clamp, to see whether a case reaches it)"""
     src = np.asarray(planes_u8, np.int64)
     P, Hs, Ws = src.shape
     sx, fx, okx = quantise_map(mapx)
@@ -136,7 +219,8 @@ def remap_cubic(planes_u8, mapx, mapy, table):
             inside = ok & (yy >= 0) & (yy < Hs) & (xx >= 0) & (xx < Ws)
             v = src[:, np.where(inside, yy, 0), np.where(inside, xx, 0)] * inside
             acc += v * tab[..., k1 * 4 + k2]
-    return np.clip((acc + 16384) >> 15, 0, 255).astype(np.int32)
+    res = (acc + 16384) >> 15
+    return (np.clip(res, 0, 255) if saturate else res).astype(np.int32)
 
 
 def warp_other(H_warp, H_warp_mask, points_src, points_dst, out_h, out_w, table):

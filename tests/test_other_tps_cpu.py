@@ -59,6 +59,90 @@ def test_w0_is_numpys_float32_sum():
             assert R.f32_sum(a[:, k]) == np.sum(a[:, k], keepdims=True)[0], (n, k)
 
 
+@pytest.mark.parametrize("n", R.N_TABLE)
+def test_matrix_case_w0_is_numpys_float32_sum(n):
+    """the inputs of tests/test_other_tps_matrix_gpu.py: the restated sum of w_1..w_{n-1} is numpy's, on the strided column itself"""
+    kw = R.case(n)[0]
+    assert kw.shape == (n, 2) and kw.dtype == np.float32
+    for a in range(2):
+        col = kw[1:, a]
+        assert col.strides == (8,)
+        assert R.f32_sum(col).tobytes() == np.sum(col, keepdims=True)[0].tobytes(), (n, a)
+        assert R.reduce_w0(kw)[0, a].tobytes() == (-np.sum(col, keepdims=True)[0]).tobytes(), (n, a)
+
+
+WRONG_SUMS = {"in_order": (R.sum_in_order, lambda m: m >= 8),
+              "leaf_no_split": (R.sum_leaf_no_split, lambda m: m > 128),
+              "halves_unrounded": (R.sum_halves_unrounded, R.unrounded_halves_differ)}
+
+
+@pytest.mark.parametrize("wrong", sorted(WRONG_SUMS))
+@pytest.mark.parametrize("n", [n for n in R.N_TABLE if n >= 130])
+def test_matrix_case_tells_a_wrong_sum_from_numpys(n, wrong):
+    """a kernel that sums w_1..w_{n-1} in one of the three wrong ways gets another w_0 on at least one axis, at every n of the table
+    past the 128-element block, wherever the wrong way is a different sequence of additions at that length (the unrounded halves
+    are the same additions at 129, 256 and 512 elements: n = 130, 257, 513)"""
+    fn, defined_differently = WRONG_SUMS[wrong]
+    kw = R.case(n)[0]
+    if not defined_differently(n - 1):
+        assert wrong == "halves_unrounded" and n in (130, 257, 513)
+        assert all(fn(kw[1:, a]) == R.f32_sum(kw[1:, a]) for a in range(2))
+        return
+    assert any(fn(kw[1:, a]) != R.f32_sum(kw[1:, a]) for a in range(2)), (n, wrong)
+    # ... and the 1 x 1 probe, float32(U(3) * w_0), shows it: the product does not round the two w_0 onto one float32
+    u3 = R.u(np.float64(R.PROBE_R))
+    probe = lambda s: np.float32(u3 * np.float64(-s))                                                       # noqa: E731
+    assert any(probe(fn(kw[1:, a])) != probe(R.f32_sum(kw[1:, a])) for a in range(2)), (n, wrong)
+
+
+def test_in_order_sum_differs_from_numpys_from_eight_elements_on():
+    """below the 128-element block only the in-order sum is a different sequence; the matrix cases see it from n = 9 on"""
+    for n in R.N_TABLE:
+        kw = R.case(n)[0]
+        same = all(R.sum_in_order(kw[1:, a]) == R.f32_sum(kw[1:, a]) for a in range(2))
+        assert same == (n - 1 < 8), n
+
+
+@pytest.mark.parametrize("n", [257, 264, 300, 513])
+def test_matrix_case_sees_a_dropped_last_chunk(n):
+    """centres are staged 256 at a time: what the centres of a partial last chunk add to the 37 x 130 maps is far above the 1 ulp
+    that the GPU test allows, at most pixels, so a kernel that drops them fails there"""
+    H, W = 37, 130
+    kw, aw, centres = R.case(n)
+    mx, my = R.maps(kw, aw, centres, H, W)
+    xs, ys = R.grid_axes(H, W)
+    x, y = xs.astype(np.float64)[None, :], ys.astype(np.float64)[:, None]
+    c, w = centres.astype(np.float64), kw.astype(np.float64)
+    last = np.zeros((2, H, W))
+    for k in range(n - n % 256, n):
+        uk = R.u(np.sqrt((x - c[k, 0]) ** 2 + (y - c[k, 1]) ** 2))
+        last[0] += uk * w[k, 0] * W
+        last[1] += uk * w[k, 1] * H
+    for part, m in zip(last, (mx, my)):
+        assert np.mean(np.abs(part) > 4 * np.spacing(np.abs(m))) > 0.9, n
+
+
+@pytest.mark.parametrize("n", R.N_TABLE)
+def test_w0_probe_does_not_sit_on_a_float32_rounding_boundary(n):
+    """the probe's maps are float32(U(3) * w_0) and are compared bit for bit, while the GPU's log may differ from the host's in the
+    last place: 9 * (log(3 + 1e-6) +- 1 ulp) rounds to U(3) moved by up to 2 fp64 ulps, and no such move may change the float32"""
+    kw, aw, centres = R.probe_case(n)
+    w0 = R.reduce_w0(kw)[0].astype(np.float64)
+    u3 = R.u(np.float64(R.PROBE_R))
+    mx, my = R.maps(kw, aw, centres, 1, 1)
+    want = (0.0 + u3 * w0).astype(np.float32)                      # the spline sum starts from +0.0
+    assert mx.shape == (1, 1) and mx[0, 0].tobytes() == want[0].tobytes() and my[0, 0].tobytes() == want[1].tobytes()
+    if n == 1:
+        assert np.signbit(R.reduce_w0(kw)[0]).all() and not np.signbit(want).any() and (want == 0).all()      # w_0 = -0.0, maps +0.0
+    else:
+        assert (want != 0).all()
+    for k in (-2, -1, 1, 2):
+        moved = u3
+        for _ in range(abs(k)):
+            moved = np.nextafter(moved, np.inf if k > 0 else -np.inf)
+        assert (0.0 + moved * w0).astype(np.float32).tobytes() == want.tobytes(), (n, k)
+
+
 @pytest.mark.parametrize("name", ["well", "chain"])
 def test_fp64_fit_against_the_reference_sgesv(gold, name):
     """the documented deviation: the fit is solved in fp64 (the reference: float32 sgesv).  Reported on both sets, bounded on the
@@ -173,6 +257,11 @@ def test_capi_rejects_bad_arguments_on_the_host():
     assert lib.st_tps_other_maps(dp, dp, dp, 0, 8, 8, dp, dp, None) == 1001
     assert lib.st_tps_other_maps(dp, dp, dp, 10, 0, 8, dp, dp, None) == 1001
     assert lib.st_tps_other_maps(dp, dp, dp, 10, 8, 8, dp, None, None) == 1001
+    assert lib.st_tps_other_maps(dp, dp, dp, 10, 8, 8, None, dp, None) == 1001
+    assert lib.st_tps_other_maps(dp, dp, dp, 4097, 8, 8, dp, dp, None) == 1001
+    assert lib.st_tps_other_maps(dp, dp, dp, 10, 8, 0, dp, dp, None) == 1001
+    assert lib.st_tps_other_maps(dp, dp, dp, 10, 8, -1, dp, dp, None) == 1001
+    assert lib.st_tps_other_maps(dp, dp, dp, 10, 65536, 32768, dp, dp, None) == 1001              # h w = 2^31
     assert lib.st_remap_cubic_u8(dp, 6, 8, 8, dp, dp, 8, 8, dp, None, None) == 1001
     assert lib.st_remap_cubic_u8(dp, 0, 8, 8, dp, dp, 8, 8, dp, dp, None) == 1001
     assert lib.st_remap_cubic_u8(dp, 6, 32761, 8, dp, dp, 8, 8, dp, dp, None) == 1001
