@@ -6,15 +6,17 @@
 // alone, so a call captures into a hipGraph as a linear chain.  What depends on the data -- the number of keypoints, of matches, whether a
 // hypothesis is void -- is read on the device by the kernels it concerns.
 //
-//   ft_detect_kernel    one workgroup per 32x32 cell: luma tile (halo 5) -> Sobel (halo 4) -> Harris response (halo 1) in LDS, the 3x3
-//                       non-maximum suppression, the cell's best 4 corners, and the 5x5 box sum of the luma for the descriptor
+//   ft_detect_kernel    one workgroup per 32x32 cell: the luma tile (halo 5) from RGB into LDS, then ft_corners: Sobel (halo 4) -> Harris response
+//                       (halo 1), the 3x3 non-maximum suppression, the cell's best 4 corners, and the 5x5 box sum of the luma for the descriptor
 //   ft_describe_kernel  one thread per descriptor word: 32 comparisons of box sums
 //   ft_match_kernel     both directions: 1024 candidate descriptors at a time in LDS, one wave per query, (distance, slot) reduced over the wave
 //   ft_compact_kernel   ratio test, mutual check, the match list in slot order (one workgroup per item: scan)
 //   ft_norm_kernel      normalised fp64 coordinates of the matches
 //   ft_hyp_kernel       one thread per hypothesis: draw, 8x8 solve in LDS, score against the match list (1024 matches at a time in LDS)
-//   ft_refit_kernel     one workgroup per item: winner, inlier mask, two least-squares refits (four interleaved partial sums per entry), H / motion / info
-#include "features_common.h"           // the constants, the hash, the solve, the inlier test and the H / motion / info tail, shared with features_ms.hip
+//   ft_refit_kernel     one workgroup per item: ft_refit with the inlier flags of 4096 list entries in LDS
+// The bodies ft_corners and ft_refit are in features_common.h, with everything else that features_ms.hip shares: its detect and refit kernels are
+// shells around the same two bodies.
+#include "features_common.h"
 
 static constexpr ft_pattern_t ft_pattern_host = ft_make_pattern();
 __constant__ ft_pattern_t ft_pattern = ft_make_pattern();
@@ -22,11 +24,7 @@ __constant__ ft_pattern_t ft_pattern = ft_make_pattern();
 __global__ void __launch_bounds__(FT_THREADS) ft_detect_kernel(const float* __restrict__ img1, const float* __restrict__ img2, int B, int H, int W,
                                                                 int32_t* __restrict__ kp, uint16_t* __restrict__ box) {
     __shared__ uint8_t sy[42][44];
-    __shared__ int16_t sgx[40][40], sgy[40][40];
-    __shared__ long long sr[34][34];
-    __shared__ long long wr[4];
-    __shared__ int wi[4];
-    const int t = threadIdx.x, z = blockIdx.z, CW = gridDim.x, N = FT_PER_CELL * gridDim.x * gridDim.y;
+    const int t = threadIdx.x, z = blockIdx.z, N = FT_PER_CELL * gridDim.x * gridDim.y, cell = blockIdx.y * gridDim.x + blockIdx.x;
     const int x0 = blockIdx.x * FT_CELL, y0 = blockIdx.y * FT_CELL;
     const size_t hw = (size_t)H * W;
     const float* img = (z < B ? img1 + (size_t)z * 3 * hw : img2 + (size_t)(z - B) * 3 * hw);
@@ -38,87 +36,8 @@ __global__ void __launch_bounds__(FT_THREADS) ft_detect_kernel(const float* __re
         sy[ty][tx] = (uint8_t)((19595 * r + 38470 * gg + 7471 * b + 0x8000) >> 16);
     }
     __syncthreads();
-    for (int e = t; e < 40 * 40; e += FT_THREADS) {
-        const int ty = e / 40, tx = e - ty * 40;
-        const int y = y0 - 4 + ty, x = x0 - 4 + tx;
-        int gx = 0, gy = 0;
-        if (y >= 0 && y < H && x >= 0 && x < W) {
-            const int a = sy[ty][tx], b = sy[ty][tx + 1], c = sy[ty][tx + 2], d = sy[ty + 1][tx], f = sy[ty + 1][tx + 2], g = sy[ty + 2][tx], h = sy[ty + 2][tx + 1],
-                      i = sy[ty + 2][tx + 2];
-            gx = (c + 2 * f + i) - (a + 2 * d + g);
-            gy = (g + 2 * h + i) - (a + 2 * b + c);
-        }
-        sgx[ty][tx] = (int16_t)gx, sgy[ty][tx] = (int16_t)gy;
-    }
-    __syncthreads();
-    for (int e = t; e < 34 * 34; e += FT_THREADS) {
-        const int ty = e / 34, tx = e - ty * 34;
-        int a = 0, b = 0, c = 0;
-        for (int dy = 0; dy < 7; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 7; ++dx) {
-                const int gx = sgx[ty + dy][tx + dx], gy = sgy[ty + dy][tx + dx];
-                a += gx * gx, b += gy * gy, c += gx * gy;
-            }
-        const long long A = a, Bq = b, Cq = c;
-        sr[ty][tx] = 16 * (A * Bq - Cq * Cq) - (A + Bq) * (A + Bq);
-    }
-    __syncthreads();
-    long long cr[4];
-    int ci[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int p = t + FT_THREADS * j, py = p >> 5, px = p & 31, y = y0 + py, x = x0 + px;
-        cr[j] = 0, ci[j] = 0x7FFFFFFF;
-        if (y < H && x < W) {
-            int s = 0;                                       // 5x5 box sum of the luma, terms outside the image 0
-            for (int dy = -2; dy <= 2; ++dy)
-                for (int dx = -2; dx <= 2; ++dx)
-                    if (y + dy >= 0 && y + dy < H && x + dx >= 0 && x + dx < W) s += sy[py + 5 + dy][px + 5 + dx];
-            box[(size_t)z * hw + (size_t)y * W + x] = (uint16_t)s;
-            if (y >= FT_BORDER && y < H - FT_BORDER && x >= FT_BORDER && x < W - FT_BORDER) {
-                const long long r = sr[py + 1][px + 1];
-                bool ok = r > 0;
-#pragma unroll
-                for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        if (!dy && !dx) continue;
-                        const long long q = sr[py + 1 + dy][px + 1 + dx];
-                        ok = ok && ((dy < 0 || (dy == 0 && dx < 0)) ? r > q : r >= q);
-                    }
-                if (ok) cr[j] = r, ci[j] = y * W + x;
-            }
-        }
-    }
-    const int cell = blockIdx.y * CW + blockIdx.x;
-    for (int rank = 0; rank < FT_PER_CELL; ++rank) {
-        long long br = 0;
-        int bi = 0x7FFFFFFF;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (ft_better(cr[j], ci[j], br, bi)) br = cr[j], bi = ci[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const long long qr = ft_shfl_xor64(br, o);
-            const int qi = __shfl_xor(bi, o, 64);
-            if (ft_better(qr, qi, br, bi)) br = qr, bi = qi;
-        }
-        if ((t & 63) == 0) wr[t >> 6] = br, wi[t >> 6] = bi;
-        __syncthreads();
-        br = wr[0], bi = wi[0];
-#pragma unroll
-        for (int v = 1; v < 4; ++v)
-            if (ft_better(wr[v], wi[v], br, bi)) br = wr[v], bi = wi[v];
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (ci[j] == bi) cr[j] = 0, ci[j] = 0x7FFFFFFF;     // taken (no candidate has the index of "none")
-        if (t == 0) {
-            int32_t* o = kp + ((size_t)z * N + FT_PER_CELL * cell + rank) * 2;
-            o[0] = br > 0 ? bi % W : -1, o[1] = br > 0 ? bi / W : -1;
-        }
-    }
+    int win[FT_PER_CELL];                                    // (only ftms_detect_kernel goes on with the winners)
+    ft_corners<5, FT_BORDER>(sy, x0, y0, H, W, kp + ((size_t)z * N + FT_PER_CELL * cell) * 2, box + (size_t)z * hw, win);
 }
 
 // n2 = number of (item, image) planes; box uint16 [n2, H, W], kp int32 [n2, N, 2] (x, y), desc uint32 [n2, N, 8]
@@ -275,114 +194,7 @@ __global__ void __launch_bounds__(FT_THREADS) ft_refit_kernel(const int32_t* __r
                                                                const int32_t* __restrict__ count, const int32_t* __restrict__ scores, int H, int W, int N, int max_hyp,
                                                                uint32_t seed, double thr2, int min_inliers, float* __restrict__ motion, float* __restrict__ Hout,
                                                                int32_t* __restrict__ info, uint8_t* __restrict__ mask) {
-    __shared__ uint8_t sm[4 * FT_CHUNK];                     // inlier flag of every list entry (N <= 4096)
-    __shared__ double sa[72], sh[8], sp[4][44], smc[4 * FT_CHUNK];
-    __shared__ int part[4], s_have;
-    const int t = threadIdx.x, b = blockIdx.x, m = ft_count(count, b, N);
-    const double* mb = mc + (size_t)b * N * 4;
-    const double sx = 0.5 * W, sy = 0.5 * H;
-    int n1 = 0, n2 = 0, best = -1;
-    for (int i = t; i < N; i += FT_THREADS) n1 += kp1[((size_t)b * N + i) * 2] >= 0, n2 += kp2[((size_t)b * N + i) * 2] >= 0;
-    n1 = ft_block_sum(n1, part), n2 = ft_block_sum(n2, part);
-    // the winner: the highest score, ties to the lowest k
-    for (int k = t; k < max_hyp; k += FT_THREADS) {
-        const int s = scores[(size_t)b * max_hyp + k];
-        if (s >= 0) best = max(best, s * 65536 + (65535 - k));
-    }
-    best = ft_block_max(best, part);
-    const int winner = m >= FT_MIN_MATCHES && best >= 0 ? 65535 - (best & 65535) : -1;
-    if (t == 0) {
-        double h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const bool ok = winner >= 0 && ft_hypothesis<1>(mb, m, seed, winner, sa, h);
-        s_have = ok;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) sh[c] = h[c];
-    }
-    __syncthreads();
-    const bool have = s_have;
-    int inliers = 0;
-    for (int round = 0; round <= 2; ++round) {
-        if (round && have) {                                 // a refit over the current inliers
-            // 36 entries of the upper triangle of A^T A, then the 8 of A^T b.  An entry is (s0 + s1) + (s2 + s3), s_q the sum over the inliers at
-            // list positions p = q mod 4 in list order: thread 44 q + e sums s_q of entry e, the matches 1024 at a time in LDS
-            const int e = t % 44, q = t / 44;
-            int r = 0, c = e;
-            if (e >= 36) r = e - 36, c = 8;
-            else
-                while (c >= 8 - r) c -= 8 - r, ++r;
-            if (e < 36) c += r;
-            double acc = 0.0;
-            for (int c0 = 0; c0 < m; c0 += FT_CHUNK) {
-                const int n = min(FT_CHUNK, m - c0);
-                __syncthreads();
-                for (int i = t; i < 4 * n; i += FT_THREADS) smc[i] = mb[4 * (size_t)c0 + i];
-                __syncthreads();
-                if (q < 4)
-                    for (int p = q; p < n; p += 4) {
-                        if (!sm[c0 + p]) continue;
-                        const double x = smc[4 * p], y = smc[4 * p + 1], u = smc[4 * p + 2], v = smc[4 * p + 3];
-                        acc = acc + ft_row0(r, x, y, u) * ft_row0(c, x, y, u);
-                        acc = acc + ft_row1(r, x, y, v) * ft_row1(c, x, y, v);
-                    }
-            }
-            if (q < 4) sp[q][e] = acc;
-            __syncthreads();
-            if (t < 44) {
-                const double total = (sp[0][e] + sp[1][e]) + (sp[2][e] + sp[3][e]);
-                sa[r * 9 + c] = total;
-                if (c < 8) sa[c * 9 + r] = total;
-            }
-            __syncthreads();
-            if (t == 0) {
-                double h[8];
-                if (ft_solve8<1>(sa, h))                     // singular: the previous H stays
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) sh[c] = h[c];
-            }
-            __syncthreads();
-        }
-        double h[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) h[c] = sh[c];
-        int n = 0;
-        for (int p = t; p < m; p += FT_THREADS) {
-            const bool in = have && ft_inlier(h, mb[4 * p], mb[4 * p + 1], mb[4 * p + 2], mb[4 * p + 3], sx, sy, thr2);
-            sm[p] = in, n += in;
-        }
-        inliers = ft_block_sum(n, part);                     // (its barriers also order sm and sa between the rounds)
-    }
-    for (int p = t; p < N; p += FT_THREADS) mask[(size_t)b * N + p] = p < m ? sm[p] : 0;
-    if (t == 0) {                                            // (features_common.h has this tail as ft_write_model; called from here the compiler schedules this kernel differently, and its code object is pinned)
-        double h[9];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) h[c] = sh[c];
-        h[8] = 1.0;
-        // pixel units: D Hn Nm with Nm = [[1/sx, 0, -1], [0, 1/sy, -1], [0, 0, 1]], D = [[sx, 0, sx], [0, sy, sy], [0, 0, 1]]
-        double M[9], P[9];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) M[3 * r] = h[3 * r] / sx, M[3 * r + 1] = h[3 * r + 1] / sy, M[3 * r + 2] = (h[3 * r + 2] - h[3 * r]) - h[3 * r + 1];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) P[c] = sx * M[c] + sx * M[6 + c], P[3 + c] = sy * M[3 + c] + sy * M[6 + c], P[6 + c] = M[6 + c];
-        float Hf[9], mo[8];
-        bool fin = true;
-#pragma unroll
-        for (int c = 0; c < 9; ++c) Hf[c] = c == 8 ? 1.f : (float)(P[c] / P[8]), fin = fin && isfinite(Hf[c]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {                        // the corners (0,0), (W,0), (0,H), (W,H): -1 / +1 in normalised units
-            const double xn = q & 1 ? 1.0 : -1.0, yn = q & 2 ? 1.0 : -1.0, cx = q & 1 ? (double)W : 0.0, cy = q & 2 ? (double)H : 0.0;
-            const double den = (h[6] * xn + h[7] * yn) + 1.0;
-            const double ux = ((h[0] * xn + h[1] * yn) + h[2]) / den, uy = ((h[3] * xn + h[4] * yn) + h[5]) / den;
-            mo[2 * q] = (float)((ux * sx + sx) - cx), mo[2 * q + 1] = (float)((uy * sy + sy) - cy);
-            fin = fin && isfinite(mo[2 * q]) && isfinite(mo[2 * q + 1]);
-        }
-        const bool valid = have && fin && inliers >= min_inliers;
-#pragma unroll
-        for (int c = 0; c < 9; ++c) Hout[(size_t)b * 9 + c] = valid ? Hf[c] : (c % 4 == 0 ? 1.f : 0.f);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) motion[(size_t)b * 8 + c] = valid ? mo[c] : 0.f;
-        int32_t* o = info + (size_t)b * 8;
-        o[0] = valid, o[1] = n1, o[2] = n2, o[3] = m, o[4] = have ? winner : -1, o[5] = inliers, o[6] = 0, o[7] = 0;
-    }
+    ft_refit<4 * FT_CHUNK>(kp1, kp2, mc, count, scores, H, W, N, max_hyp, seed, thr2, min_inliers, motion, Hout, info, mask);      // (N <= 4096 by ft_shape_ok)
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
@@ -422,22 +234,20 @@ int ft_launch_match(const int32_t* kp1, const uint32_t* desc1, const int32_t* kp
     ST_CHECK_LAUNCH();
     return ST_OK;
 }
-int ft_launch_hyp(const double* mc, const int32_t* count, int B, int H, int W, int N, int max_hyp, uint32_t seed, double thr2, int32_t* scores, hipStream_t s) {
+int ft_launch_hyp_refit(ft_refit_fn refit, const int32_t* kp1, const int32_t* kp2, const double* mc, const int32_t* count, int B, int H, int W, int N, int max_hyp,
+                        double thr2, int min_inliers, uint32_t seed, int32_t* scores, float* motion, float* Hout, int32_t* info, uint8_t* mask, hipStream_t s) {
     ft_hyp_kernel<<<dim3((max_hyp + 63) / 64, B), 64, 0, s>>>(mc, count, H, W, N, max_hyp, seed, thr2, scores);
+    ST_CHECK_LAUNCH();
+    refit<<<B, FT_THREADS, 0, s>>>(kp1, kp2, mc, count, scores, H, W, N, max_hyp, seed, thr2, min_inliers, motion, Hout, info, mask);
     ST_CHECK_LAUNCH();
     return ST_OK;
 }
 static int ft_launch_ransac(const int32_t* kp1, const int32_t* kp2, const int32_t* matches, const int32_t* count, int B, int H, int W, int max_hyp, double thr,
                             int min_inliers, uint32_t seed, double* mc, int32_t* scores, float* motion, float* Hout, int32_t* info, uint8_t* mask, hipStream_t s) {
     const int N = ft_slots(H, W);
-    const double thr2 = thr * thr;
     ft_norm_kernel<<<dim3((N + FT_THREADS - 1) / FT_THREADS, B), FT_THREADS, 0, s>>>(kp1, kp2, matches, count, H, W, N, mc);
     ST_CHECK_LAUNCH();
-    const int rc = ft_launch_hyp(mc, count, B, H, W, N, max_hyp, seed, thr2, scores, s);
-    if (rc) return rc;
-    ft_refit_kernel<<<B, FT_THREADS, 0, s>>>(kp1, kp2, mc, count, scores, H, W, N, max_hyp, seed, thr2, min_inliers, motion, Hout, info, mask);
-    ST_CHECK_LAUNCH();
-    return ST_OK;
+    return ft_launch_hyp_refit(ft_refit_kernel, kp1, kp2, mc, count, B, H, W, N, max_hyp, thr * thr, min_inliers, seed, scores, motion, Hout, info, mask, s);
 }
 
 extern "C" int st_feature_slots(int32_t H, int32_t W) { return ft_shape_ok(1, H, W) ? ft_slots(H, W) : 0; }
@@ -480,26 +290,19 @@ extern "C" int st_feature_describe(const uint16_t* box, const int32_t* kp, int32
 extern "C" int st_feature_match(const int32_t* kp1, const uint32_t* desc1, const int32_t* kp2, const uint32_t* desc2, int32_t B, int32_t H, int32_t W, int32_t* nn_out,
                                 int32_t* matches_out, int32_t* count_out, void* stream) {
     if (!ft_shape_ok(B, H, W)) return ST_EINVAL;
-    const int64_t N = ft_slots(H, W), bn = (int64_t)B * N;
-    const ft_region r[7] = {{kp1, 8 * bn, false}, {desc1, 32 * bn, false}, {kp2, 8 * bn, false}, {desc2, 32 * bn, false},
-                            {nn_out, 24 * bn, true}, {matches_out, 8 * bn, true}, {count_out, 4 * B, true}};
-    if (!ft_regions_ok(r, 7)) return ST_EINVAL;
-    return ft_launch_match(kp1, desc1, kp2, desc2, B, (int)N, nn_out, matches_out, count_out, (hipStream_t)stream);
+    const int N = ft_slots(H, W);
+    if (!ft_match_operands_ok(kp1, desc1, kp2, desc2, nn_out, matches_out, count_out, B, N)) return ST_EINVAL;
+    return ft_launch_match(kp1, desc1, kp2, desc2, B, N, nn_out, matches_out, count_out, (hipStream_t)stream);
 }
 
-// workspace: mc fp64 [B,N,4] then scores int32 [B,max_hyp] = 32 B N + 4 B max_hyp bytes
 extern "C" int st_feature_ransac(const int32_t* kp1, const int32_t* kp2, const int32_t* matches, const int32_t* count, int32_t B, int32_t H, int32_t W, int32_t max_hyp,
                                  double thr, int32_t min_inliers, int32_t seed, float* motion_out, float* H_out, int32_t* info_out, uint8_t* mask_out, void* workspace,
                                  int64_t workspace_bytes, void* stream) {
     if (!ft_shape_ok(B, H, W) || !ft_params_ok(max_hyp, thr, min_inliers)) return ST_EINVAL;
-    const int64_t N = ft_slots(H, W), bn = (int64_t)B * N, need = 32 * bn + 4 * (int64_t)B * max_hyp;
-    if (workspace_bytes < need || ((uintptr_t)workspace & 15)) return ST_EINVAL;
-    const ft_region r[9] = {{kp1, 8 * bn, false}, {kp2, 8 * bn, false}, {matches, 8 * bn, false}, {count, 4 * B, false}, {motion_out, 32 * B, true},
-                            {H_out, 36 * B, true}, {info_out, 32 * B, true}, {mask_out, bn, true}, {workspace, need, true}};
-    if (!ft_regions_ok(r, 9)) return ST_EINVAL;
-    double* mc = (double*)workspace;
-    return ft_launch_ransac(kp1, kp2, matches, count, B, H, W, max_hyp, thr, min_inliers, (uint32_t)seed, mc, (int32_t*)((char*)workspace + 32 * bn), motion_out, H_out,
-                            info_out, mask_out, (hipStream_t)stream);
+    const int64_t N = ft_slots(H, W);
+    if (!ft_ransac_operands_ok(kp1, kp2, matches, count, motion_out, H_out, info_out, mask_out, nullptr, false, workspace, workspace_bytes, B, N, max_hyp)) return ST_EINVAL;
+    return ft_launch_ransac(kp1, kp2, matches, count, B, H, W, max_hyp, thr, min_inliers, (uint32_t)seed, (double*)workspace, (int32_t*)((char*)workspace + 32 * B * N),
+                            motion_out, H_out, info_out, mask_out, (hipStream_t)stream);
 }
 
 extern "C" int st_feature_homography(const float* img1, const float* img2, int32_t B, int32_t H, int32_t W, int32_t max_hyp, double thr, int32_t min_inliers,

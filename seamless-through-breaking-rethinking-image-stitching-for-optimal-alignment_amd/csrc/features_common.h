@@ -1,5 +1,6 @@
 // What csrc/features.hip (feature_align) and csrc/features_ms.hip (feature_align_ms) both need, written once: the contract's constants, the
-// hash and the BRIEF pattern, the fp64 four-point solve, the inlier test, the H / motion / info tail, the argument checks, and the host
+// hash and the BRIEF pattern, the corner body of the two detect kernels (ft_corners), the fp64 four-point solve, the inlier test, the body
+// of the two refit kernels (ft_refit) with its H / motion / info tail, the argument checks of the match and ransac entries, and the host
 // launchers of the kernels of features.hip that the multi-scale front end reuses as they are.  Both files are compiled with
 // -ffp-contract=off: every product and sum below rounds on its own.
 #pragma once
@@ -52,6 +53,100 @@ __device__ __forceinline__ long long ft_shfl_xor64(long long v, int o) {
 
 // (R descending, index ascending)
 __device__ __forceinline__ bool ft_better(long long ra, int ia, long long rb, int ib) { return ra > rb || (ra == rb && ia < ib); }
+
+// The corners of one 32x32 cell at (x0, y0) of an H x W luma plane, from its tile in LDS (clamped to the plane, HALO >= 5 pixels around the
+// cell): Sobel (halo 4) -> Harris response (halo 1), the 3x3 non-maximum suppression BORDER pixels inside the plane, the cell's best 4
+// corners by (R descending, index ascending) into kp (the cell's 4 slots, (x, y) or (-1, -1)) and, in every thread, into win (y W + x or
+// -1); and the 5x5 box sum of the luma into box (the plane).  All FT_THREADS threads call it, behind the barrier that follows the tile load.
+template <int HALO, int BORDER>
+__device__ __forceinline__ void ft_corners(const uint8_t (&sy)[FT_CELL + 2 * HALO][FT_CELL + 2 * HALO + 2], int x0, int y0, int H, int W, int32_t* __restrict__ kp,
+                                           uint16_t* __restrict__ box, int (&win)[FT_PER_CELL]) {
+    __shared__ int16_t sgx[40][40], sgy[40][40];
+    __shared__ long long sr[34][34];
+    __shared__ long long wr[4];
+    __shared__ int wi[4];
+    constexpr int O = HALO - 5;                              // the 42x42 tile that the response of the cell reads, inside this one
+    const int t = threadIdx.x;
+    for (int e = t; e < 40 * 40; e += FT_THREADS) {
+        const int ty = e / 40, tx = e - ty * 40;
+        const int y = y0 - 4 + ty, x = x0 - 4 + tx;
+        int gx = 0, gy = 0;
+        if (y >= 0 && y < H && x >= 0 && x < W) {
+            const int a = sy[O + ty][O + tx], b = sy[O + ty][O + tx + 1], c = sy[O + ty][O + tx + 2], d = sy[O + ty + 1][O + tx], f = sy[O + ty + 1][O + tx + 2],
+                      g = sy[O + ty + 2][O + tx], h = sy[O + ty + 2][O + tx + 1], i = sy[O + ty + 2][O + tx + 2];
+            gx = (c + 2 * f + i) - (a + 2 * d + g);
+            gy = (g + 2 * h + i) - (a + 2 * b + c);
+        }
+        sgx[ty][tx] = (int16_t)gx, sgy[ty][tx] = (int16_t)gy;
+    }
+    __syncthreads();
+    for (int e = t; e < 34 * 34; e += FT_THREADS) {
+        const int ty = e / 34, tx = e - ty * 34;
+        int a = 0, b = 0, c = 0;
+        for (int dy = 0; dy < 7; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 7; ++dx) {
+                const int gx = sgx[ty + dy][tx + dx], gy = sgy[ty + dy][tx + dx];
+                a += gx * gx, b += gy * gy, c += gx * gy;
+            }
+        const long long A = a, Bq = b, Cq = c;
+        sr[ty][tx] = 16 * (A * Bq - Cq * Cq) - (A + Bq) * (A + Bq);
+    }
+    __syncthreads();
+    long long cr[4];
+    int ci[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int p = t + FT_THREADS * j, py = p >> 5, px = p & 31, y = y0 + py, x = x0 + px;
+        cr[j] = 0, ci[j] = 0x7FFFFFFF;
+        if (y < H && x < W) {
+            int s = 0;                                       // 5x5 box sum of the luma, terms outside the plane 0
+            for (int dy = -2; dy <= 2; ++dy)
+                for (int dx = -2; dx <= 2; ++dx)
+                    if (y + dy >= 0 && y + dy < H && x + dx >= 0 && x + dx < W) s += sy[py + HALO + dy][px + HALO + dx];
+            box[(size_t)y * W + x] = (uint16_t)s;
+            if (y >= BORDER && y < H - BORDER && x >= BORDER && x < W - BORDER) {
+                const long long r = sr[py + 1][px + 1];
+                bool ok = r > 0;
+#pragma unroll
+                for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        if (!dy && !dx) continue;
+                        const long long q = sr[py + 1 + dy][px + 1 + dx];
+                        ok = ok && ((dy < 0 || (dy == 0 && dx < 0)) ? r > q : r >= q);
+                    }
+                if (ok) cr[j] = r, ci[j] = y * W + x;
+            }
+        }
+    }
+#pragma unroll                                               // (so that win[rank] is a register, not scratch)
+    for (int rank = 0; rank < FT_PER_CELL; ++rank) {
+        long long br = 0;
+        int bi = 0x7FFFFFFF;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (ft_better(cr[j], ci[j], br, bi)) br = cr[j], bi = ci[j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const long long qr = ft_shfl_xor64(br, o);
+            const int qi = __shfl_xor(bi, o, 64);
+            if (ft_better(qr, qi, br, bi)) br = qr, bi = qi;
+        }
+        if ((t & 63) == 0) wr[t >> 6] = br, wi[t >> 6] = bi;
+        __syncthreads();
+        br = wr[0], bi = wi[0];
+#pragma unroll
+        for (int v = 1; v < 4; ++v)
+            if (ft_better(wr[v], wi[v], br, bi)) br = wr[v], bi = wi[v];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (ci[j] == bi) cr[j] = 0, ci[j] = 0x7FFFFFFF;     // taken (no candidate has the index of "none")
+        win[rank] = br > 0 ? bi : -1;
+        if (t == 0) kp[2 * rank] = br > 0 ? bi % W : -1, kp[2 * rank + 1] = br > 0 ? bi / W : -1;
+    }
+}
 
 __device__ __forceinline__ int ft_count(const int32_t* __restrict__ count, int b, int N) { return min(max(count[b], 0), N); }
 
@@ -190,6 +285,99 @@ __device__ __forceinline__ void ft_write_model(const double (&sh)[8], bool have,
     o[0] = valid, o[1] = n1, o[2] = n2, o[3] = m, o[4] = have ? winner : -1, o[5] = inliers, o[6] = 0, o[7] = 0;
 }
 
+// The body of ft_refit_kernel and ftms_refit_kernel, one workgroup per item: winner, inlier mask, two least-squares refits (four interleaved
+// partial sums per entry), H / motion / info.  CAP = the list entries whose inlier flags LDS holds; the entries prove N <= CAP.
+template <int CAP>
+__device__ __forceinline__ void ft_refit(const int32_t* kp1, const int32_t* kp2, const double* mc, const int32_t* count, const int32_t* scores, int H, int W, int N,
+                                         int max_hyp, uint32_t seed, double thr2, int min_inliers, float* motion, float* Hout, int32_t* info, uint8_t* mask) {
+    __shared__ uint8_t sm[CAP];                              // inlier flag of every list entry
+    __shared__ double sa[72], sh[8], sp[4][44], smc[4 * FT_CHUNK];
+    __shared__ int part[4], s_have;
+    const int t = threadIdx.x, b = blockIdx.x, m = ft_count(count, b, min(N, CAP));
+    const double* mb = mc + (size_t)b * N * 4;
+    const double sx = 0.5 * W, sy = 0.5 * H;
+    int n1 = 0, n2 = 0, best = -1;
+    for (int i = t; i < N; i += FT_THREADS) n1 += kp1[((size_t)b * N + i) * 2] >= 0, n2 += kp2[((size_t)b * N + i) * 2] >= 0;
+    n1 = ft_block_sum(n1, part), n2 = ft_block_sum(n2, part);
+    // the winner: the highest score, ties to the lowest k
+    for (int k = t; k < max_hyp; k += FT_THREADS) {
+        const int s = scores[(size_t)b * max_hyp + k];
+        if (s >= 0) best = max(best, s * 65536 + (65535 - k));
+    }
+    best = ft_block_max(best, part);
+    const int winner = m >= FT_MIN_MATCHES && best >= 0 ? 65535 - (best & 65535) : -1;
+    if (t == 0) {
+        double h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const bool ok = winner >= 0 && ft_hypothesis<1>(mb, m, seed, winner, sa, h);
+        s_have = ok;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) sh[c] = h[c];
+    }
+    __syncthreads();
+    const bool have = s_have;
+    int inliers = 0;
+    for (int round = 0; round <= 2; ++round) {
+        if (round && have) {                                 // a refit over the current inliers
+            // 36 entries of the upper triangle of A^T A, then the 8 of A^T b.  An entry is (s0 + s1) + (s2 + s3), s_q the sum over the inliers at
+            // list positions p = q mod 4 in list order: thread 44 q + e sums s_q of entry e, the matches 1024 at a time in LDS
+            const int e = t % 44, q = t / 44;
+            int r = 0, c = e;
+            if (e >= 36) r = e - 36, c = 8;
+            else
+                while (c >= 8 - r) c -= 8 - r, ++r;
+            if (e < 36) c += r;
+            double acc = 0.0;
+            for (int c0 = 0; c0 < m; c0 += FT_CHUNK) {
+                const int n = min(FT_CHUNK, m - c0);
+                __syncthreads();
+                for (int i = t; i < 4 * n; i += FT_THREADS) smc[i] = mb[4 * (size_t)c0 + i];
+                __syncthreads();
+                // The loop below is nearly all of the kernel's time, and its switches diverge in every wave: some 400 instructions with 46 conditional
+                // branches, whose cost depends on where they fall in the 64-byte fetch lines.  Measured on the MI355X with the loop's first LDS read at
+                // byte 0 / 40 / 12 of a line: 549 / 531 / 529 us for ftms_refit_kernel at 512x512 (README.md, feature_align_ms, Measurements).  So the
+                // place is fixed here, 12 as it was before the two kernels shared this body, and no longer moves with the code in front of it.
+                // The nine belongs to the blocks the present compiler lays between this point and the loop's header: after a compiler update, or a change
+                // to the loop, disassemble the kernel, take the offset of the loop's first ds_read_u8 from the kernel's start modulo 64, and choose the
+                // count that makes it 12 again.  (A branch-free loop would not need any of this; that is tuning and a change of its own.)
+                asm volatile(".p2align 6\n .rept 9\n s_nop 0\n .endr");
+                if (q < 4)
+                    for (int p = q; p < n; p += 4) {
+                        if (!sm[c0 + p]) continue;
+                        const double x = smc[4 * p], y = smc[4 * p + 1], u = smc[4 * p + 2], v = smc[4 * p + 3];
+                        acc = acc + ft_row0(r, x, y, u) * ft_row0(c, x, y, u);
+                        acc = acc + ft_row1(r, x, y, v) * ft_row1(c, x, y, v);
+                    }
+            }
+            if (q < 4) sp[q][e] = acc;
+            __syncthreads();
+            if (t < 44) {
+                const double total = (sp[0][e] + sp[1][e]) + (sp[2][e] + sp[3][e]);
+                sa[r * 9 + c] = total;
+                if (c < 8) sa[c * 9 + r] = total;
+            }
+            __syncthreads();
+            if (t == 0) {
+                double h[8];
+                if (ft_solve8<1>(sa, h))                     // singular: the previous H stays
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) sh[c] = h[c];
+            }
+            __syncthreads();
+        }
+        double h[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) h[c] = sh[c];
+        int n = 0;
+        for (int p = t; p < m; p += FT_THREADS) {
+            const bool in = have && ft_inlier(h, mb[4 * p], mb[4 * p + 1], mb[4 * p + 2], mb[4 * p + 3], sx, sy, thr2);
+            sm[p] = in, n += in;
+        }
+        inliers = ft_block_sum(n, part);                     // (its barriers also order sm and sa between the rounds)
+    }
+    for (int p = t; p < N; p += FT_THREADS) mask[(size_t)b * N + p] = p < m ? sm[p] : 0;
+    if (t == 0) ft_write_model(sh, have, winner, inliers, min_inliers, n1, n2, m, H, W, sx, sy, b, motion, Hout, info);
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 struct ft_region {
     const void* p;
@@ -220,8 +408,31 @@ static inline bool ft_params_ok(int max_hyp, double thr, int min_inliers) {
     return max_hyp >= 1 && max_hyp <= FT_MAX_HYP && thr > 0.0 && thr <= 1.7e308 && min_inliers >= 0;       // (a NaN thr fails both comparisons)
 }
 
-// launchers of features.hip's kernels that take the number of slots N as an argument (defined there): ft_match_kernel + ft_compact_kernel,
-// and ft_hyp_kernel on normalised match coordinates
+// the operands of the match entries of both paths, N slots per image
+static inline bool ft_match_operands_ok(const void* kp1, const void* desc1, const void* kp2, const void* desc2, const void* nn, const void* matches, const void* count, int B,
+                                        int64_t N) {
+    const int64_t bn = B * N;
+    const ft_region r[7] = {{kp1, 8 * bn, false}, {desc1, 32 * bn, false}, {kp2, 8 * bn, false}, {desc2, 32 * bn, false},
+                            {nn, 24 * bn, true}, {matches, 8 * bn, true}, {count, 4 * B, true}};
+    return ft_regions_ok(r, 7);
+}
+
+// those of the ransac entries, xy fp64 [2,B,N,2] where the entry has it; workspace: mc fp64 [B,N,4] then scores int32 [B,max_hyp] = 32 B N +
+// 4 B max_hyp bytes
+static inline bool ft_ransac_operands_ok(const void* kp1, const void* kp2, const void* matches, const void* count, const void* motion, const void* Hout, const void* info,
+                                         const void* mask, const void* xy, bool has_xy, const void* workspace, int64_t workspace_bytes, int B, int64_t N, int max_hyp) {
+    const int64_t bn = B * N, need = 32 * bn + 4 * (int64_t)B * max_hyp;
+    if (workspace_bytes < need || ((uintptr_t)workspace & 15)) return false;
+    const ft_region r[10] = {{kp1, 8 * bn, false}, {kp2, 8 * bn, false}, {matches, 8 * bn, false}, {count, 4 * B, false}, {motion, 32 * B, true},
+                             {Hout, 36 * B, true}, {info, 32 * B, true}, {mask, bn, true}, {workspace, need, true}, {xy, 32 * bn, true}};
+    return ft_regions_ok(r, has_xy ? 10 : 9);
+}
+
+// launchers of features.hip's kernels that take the number of slots N as an argument (defined there): ft_match_kernel + ft_compact_kernel;
+// and, behind the path's own norm kernel, ft_hyp_kernel on the normalised match coordinates mc, then the path's refit kernel
+typedef void (*ft_refit_fn)(const int32_t* kp1, const int32_t* kp2, const double* mc, const int32_t* count, const int32_t* scores, int H, int W, int N, int max_hyp,
+                            uint32_t seed, double thr2, int min_inliers, float* motion, float* Hout, int32_t* info, uint8_t* mask);
 int ft_launch_match(const int32_t* kp1, const uint32_t* desc1, const int32_t* kp2, const uint32_t* desc2, int B, int N, int32_t* nn, int32_t* matches, int32_t* count,
                     hipStream_t s);
-int ft_launch_hyp(const double* mc, const int32_t* count, int B, int H, int W, int N, int max_hyp, uint32_t seed, double thr2, int32_t* scores, hipStream_t s);
+int ft_launch_hyp_refit(ft_refit_fn refit, const int32_t* kp1, const int32_t* kp2, const double* mc, const int32_t* count, int B, int H, int W, int N, int max_hyp,
+                        double thr2, int min_inliers, uint32_t seed, int32_t* scores, float* motion, float* Hout, int32_t* info, uint8_t* mask, hipStream_t s);

@@ -8,11 +8,11 @@
 //
 //   ftms_luma_kernel      one thread per pixel: level 0 of the pyramid, the luma as uint8
 //   ftms_down_kernel      one thread per coarser pixel: level l+1 from level l, centre-aligned x 5/4, bilinear in 1/256 px
-//   ftms_detect_kernel    one workgroup per 32x32 cell, all levels in one launch: ft_detect_kernel on a luma tile with a halo of 15, border 20, then one
-//                         wave per winner: the two first moments over the disc of radius 15 from the tile, the best of 32 bins
+//   ftms_detect_kernel    one workgroup per 32x32 cell, all levels in one launch: ft_detect_kernel's corner body (ft_corners) on a luma tile with a halo of
+//                         15, border 20, then one wave per winner: the two first moments over the disc of radius 15 from the tile, the best of 32 bins
 //   ftms_describe_kernel  one thread per descriptor word: 32 comparisons of box sums of the slot's level at offsets steered by its bin
 //   ftms_norm_kernel      level-0 coordinates of every slot and the normalised fp64 coordinates of the matches
-//   ftms_refit_kernel     ft_refit_kernel with the inlier flags of up to FTMS_MAX_SLOTS list entries in LDS
+//   ftms_refit_kernel     ft_refit_kernel's body (ft_refit) with the inlier flags of FTMS_MAX_SLOTS list entries in LDS
 #include "features_common.h"
 
 #define FTMS_MAX_LEVELS 8
@@ -89,107 +89,26 @@ __device__ __forceinline__ int ftms_level_of(const ftms_levels& V, int slot, int
 __global__ void __launch_bounds__(FT_THREADS) ftms_detect_kernel(const uint8_t* __restrict__ pyr, ftms_levels V, int n2, int oriented, int32_t* __restrict__ kp,
                                                                   uint8_t* __restrict__ bins, uint16_t* __restrict__ box_all) {
     __shared__ uint8_t sy[FTMS_TILE][FTMS_TILE + 2];
-    __shared__ int16_t sgx[40][40], sgy[40][40];
-    __shared__ long long sr[34][34];
-    __shared__ long long wr[4];
-    __shared__ int wi[4], swin[FT_PER_CELL];
+    __shared__ int swin[FT_PER_CELL];
     const int t = threadIdx.x, z = blockIdx.y, N = V.N;
     int H, W, slot0;
     long long pix0;
     ftms_level_of(V, FT_PER_CELL * blockIdx.x, H, W, slot0, pix0);
     const int CW = (W + FT_CELL - 1) / FT_CELL, cell = blockIdx.x - slot0 / FT_PER_CELL, cy = cell / CW;
     const int x0 = (cell - cy * CW) * FT_CELL, y0 = cy * FT_CELL;
-    const size_t hw = (size_t)H * W;
+    const size_t hw = (size_t)H * W, slot = (size_t)z * N + FT_PER_CELL * blockIdx.x;
     const uint8_t* img = pyr + (size_t)pix0 * n2 + (size_t)z * hw;
-    uint16_t* box = box_all + (size_t)pix0 * n2;
     for (int e = t; e < FTMS_TILE * FTMS_TILE; e += FT_THREADS) {
         const int ty = e / FTMS_TILE, tx = e - ty * FTMS_TILE;
         const int y = min(max(y0 - FTMS_RADIUS + ty, 0), H - 1), x = min(max(x0 - FTMS_RADIUS + tx, 0), W - 1);
         sy[ty][tx] = img[(size_t)y * W + x];
     }
     __syncthreads();
-    constexpr int O = FTMS_RADIUS - 5;                       // ft_detect_kernel's tile (halo 5) inside this one
-    for (int e = t; e < 40 * 40; e += FT_THREADS) {
-        const int ty = e / 40, tx = e - ty * 40;
-        const int y = y0 - 4 + ty, x = x0 - 4 + tx;
-        int gx = 0, gy = 0;
-        if (y >= 0 && y < H && x >= 0 && x < W) {
-            const int a = sy[O + ty][O + tx], b = sy[O + ty][O + tx + 1], c = sy[O + ty][O + tx + 2], d = sy[O + ty + 1][O + tx], f = sy[O + ty + 1][O + tx + 2],
-                      g = sy[O + ty + 2][O + tx], h = sy[O + ty + 2][O + tx + 1], i = sy[O + ty + 2][O + tx + 2];
-            gx = (c + 2 * f + i) - (a + 2 * d + g);
-            gy = (g + 2 * h + i) - (a + 2 * b + c);
-        }
-        sgx[ty][tx] = (int16_t)gx, sgy[ty][tx] = (int16_t)gy;
-    }
-    __syncthreads();
-    for (int e = t; e < 34 * 34; e += FT_THREADS) {
-        const int ty = e / 34, tx = e - ty * 34;
-        int a = 0, b = 0, c = 0;
-        for (int dy = 0; dy < 7; ++dy)
+    int won[FT_PER_CELL];
+    ft_corners<FTMS_RADIUS, FTMS_BORDER>(sy, x0, y0, H, W, kp + slot * 2, box_all + (size_t)pix0 * n2 + (size_t)z * hw, won);
+    if (t == 0)                                              // (every thread holds won[]; a wave picks its own through LDS as it always did, which keeps the 19680 bytes)
 #pragma unroll
-            for (int dx = 0; dx < 7; ++dx) {
-                const int gx = sgx[ty + dy][tx + dx], gy = sgy[ty + dy][tx + dx];
-                a += gx * gx, b += gy * gy, c += gx * gy;
-            }
-        const long long A = a, Bq = b, Cq = c;
-        sr[ty][tx] = 16 * (A * Bq - Cq * Cq) - (A + Bq) * (A + Bq);
-    }
-    __syncthreads();
-    long long cr[4];
-    int ci[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int p = t + FT_THREADS * j, py = p >> 5, px = p & 31, y = y0 + py, x = x0 + px;
-        cr[j] = 0, ci[j] = 0x7FFFFFFF;
-        if (y < H && x < W) {
-            int s = 0;                                       // 5x5 box sum of the level, terms outside it 0
-            for (int dy = -2; dy <= 2; ++dy)
-                for (int dx = -2; dx <= 2; ++dx)
-                    if (y + dy >= 0 && y + dy < H && x + dx >= 0 && x + dx < W) s += sy[py + FTMS_RADIUS + dy][px + FTMS_RADIUS + dx];
-            box[(size_t)z * hw + (size_t)y * W + x] = (uint16_t)s;
-            if (y >= FTMS_BORDER && y < H - FTMS_BORDER && x >= FTMS_BORDER && x < W - FTMS_BORDER) {
-                const long long r = sr[py + 1][px + 1];
-                bool ok = r > 0;
-#pragma unroll
-                for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        if (!dy && !dx) continue;
-                        const long long q = sr[py + 1 + dy][px + 1 + dx];
-                        ok = ok && ((dy < 0 || (dy == 0 && dx < 0)) ? r > q : r >= q);
-                    }
-                if (ok) cr[j] = r, ci[j] = y * W + x;
-            }
-        }
-    }
-    for (int rank = 0; rank < FT_PER_CELL; ++rank) {
-        long long br = 0;
-        int bi = 0x7FFFFFFF;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (ft_better(cr[j], ci[j], br, bi)) br = cr[j], bi = ci[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const long long qr = ft_shfl_xor64(br, o);
-            const int qi = __shfl_xor(bi, o, 64);
-            if (ft_better(qr, qi, br, bi)) br = qr, bi = qi;
-        }
-        if ((t & 63) == 0) wr[t >> 6] = br, wi[t >> 6] = bi;
-        __syncthreads();
-        br = wr[0], bi = wi[0];
-#pragma unroll
-        for (int v = 1; v < 4; ++v)
-            if (ft_better(wr[v], wi[v], br, bi)) br = wr[v], bi = wi[v];
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (ci[j] == bi) cr[j] = 0, ci[j] = 0x7FFFFFFF;     // taken (no candidate has the index of "none")
-        if (t == 0) {
-            int32_t* o = kp + ((size_t)z * N + slot0 + FT_PER_CELL * cell + rank) * 2;
-            o[0] = br > 0 ? bi % W : -1, o[1] = br > 0 ? bi / W : -1;
-            swin[rank] = br > 0 ? bi : -1;
-        }
-    }
+        for (int r = 0; r < FT_PER_CELL; ++r) swin[r] = won[r];
     __syncthreads();
     // wave `rank` takes winner `rank`: m10 = sum dx Y, m01 = sum dy Y over the disc (a winner is 20 px inside the level: the disc lies in the
     // tile and in the image), then the bin that maximises m10 c + m01 s, ties to the lowest
@@ -217,7 +136,7 @@ __global__ void __launch_bounds__(FT_THREADS) ftms_detect_kernel(const uint8_t* 
             if (ft_better(qv, qb, best, bin)) best = qv, bin = qb;
         }
     }
-    if (lane == 0) bins[(size_t)z * N + slot0 + FT_PER_CELL * cell + rank] = (uint8_t)bin;
+    if (lane == 0) bins[slot + rank] = (uint8_t)bin;
 }
 
 // box uint16: level l's [n2, H_l, W_l] planes at pix0[l] n2; kp int32 [n2, N, 2]; bins uint8 [n2, N]; desc uint32 [n2, N, 8]
@@ -279,87 +198,11 @@ __global__ void __launch_bounds__(FT_THREADS) ftms_norm_kernel(const int32_t* __
     o[2] = (X - sx) / sx, o[3] = (Y - sy) / sy;
 }
 
-// ft_refit_kernel for N <= FTMS_MAX_SLOTS list entries
 __global__ void __launch_bounds__(FT_THREADS) ftms_refit_kernel(const int32_t* __restrict__ kp1, const int32_t* __restrict__ kp2, const double* __restrict__ mc,
                                                                  const int32_t* __restrict__ count, const int32_t* __restrict__ scores, int H, int W, int N, int max_hyp,
                                                                  uint32_t seed, double thr2, int min_inliers, float* __restrict__ motion, float* __restrict__ Hout,
                                                                  int32_t* __restrict__ info, uint8_t* __restrict__ mask) {
-    __shared__ uint8_t sm[FTMS_MAX_SLOTS];                   // inlier flag of every list entry
-    __shared__ double sa[72], sh[8], sp[4][44], smc[4 * FT_CHUNK];
-    __shared__ int part[4], s_have;
-    const int t = threadIdx.x, b = blockIdx.x, m = ft_count(count, b, min(N, FTMS_MAX_SLOTS));
-    const double* mb = mc + (size_t)b * N * 4;
-    const double sx = 0.5 * W, sy = 0.5 * H;
-    int n1 = 0, n2 = 0, best = -1;
-    for (int i = t; i < N; i += FT_THREADS) n1 += kp1[((size_t)b * N + i) * 2] >= 0, n2 += kp2[((size_t)b * N + i) * 2] >= 0;
-    n1 = ft_block_sum(n1, part), n2 = ft_block_sum(n2, part);
-    // the winner: the highest score, ties to the lowest k
-    for (int k = t; k < max_hyp; k += FT_THREADS) {
-        const int s = scores[(size_t)b * max_hyp + k];
-        if (s >= 0) best = max(best, s * 65536 + (65535 - k));
-    }
-    best = ft_block_max(best, part);
-    const int winner = m >= FT_MIN_MATCHES && best >= 0 ? 65535 - (best & 65535) : -1;
-    if (t == 0) {
-        double h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const bool ok = winner >= 0 && ft_hypothesis<1>(mb, m, seed, winner, sa, h);
-        s_have = ok;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) sh[c] = h[c];
-    }
-    __syncthreads();
-    const bool have = s_have;
-    int inliers = 0;
-    for (int round = 0; round <= 2; ++round) {
-        if (round && have) {                                 // a refit over the current inliers, summed as in ft_refit_kernel
-            const int e = t % 44, q = t / 44;
-            int r = 0, c = e;
-            if (e >= 36) r = e - 36, c = 8;
-            else
-                while (c >= 8 - r) c -= 8 - r, ++r;
-            if (e < 36) c += r;
-            double acc = 0.0;
-            for (int c0 = 0; c0 < m; c0 += FT_CHUNK) {
-                const int n = min(FT_CHUNK, m - c0);
-                __syncthreads();
-                for (int i = t; i < 4 * n; i += FT_THREADS) smc[i] = mb[4 * (size_t)c0 + i];
-                __syncthreads();
-                if (q < 4)
-                    for (int p = q; p < n; p += 4) {
-                        if (!sm[c0 + p]) continue;
-                        const double x = smc[4 * p], y = smc[4 * p + 1], u = smc[4 * p + 2], v = smc[4 * p + 3];
-                        acc = acc + ft_row0(r, x, y, u) * ft_row0(c, x, y, u);
-                        acc = acc + ft_row1(r, x, y, v) * ft_row1(c, x, y, v);
-                    }
-            }
-            if (q < 4) sp[q][e] = acc;
-            __syncthreads();
-            if (t < 44) {
-                const double total = (sp[0][e] + sp[1][e]) + (sp[2][e] + sp[3][e]);
-                sa[r * 9 + c] = total;
-                if (c < 8) sa[c * 9 + r] = total;
-            }
-            __syncthreads();
-            if (t == 0) {
-                double h[8];
-                if (ft_solve8<1>(sa, h))                     // singular: the previous H stays
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) sh[c] = h[c];
-            }
-            __syncthreads();
-        }
-        double h[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) h[c] = sh[c];
-        int n = 0;
-        for (int p = t; p < m; p += FT_THREADS) {
-            const bool in = have && ft_inlier(h, mb[4 * p], mb[4 * p + 1], mb[4 * p + 2], mb[4 * p + 3], sx, sy, thr2);
-            sm[p] = in, n += in;
-        }
-        inliers = ft_block_sum(n, part);                     // (its barriers also order sm and sa between the rounds)
-    }
-    for (int p = t; p < N; p += FT_THREADS) mask[(size_t)b * N + p] = p < m ? sm[p] : 0;
-    if (t == 0) ft_write_model(sh, have, winner, inliers, min_inliers, n1, n2, m, H, W, sx, sy, b, motion, Hout, info);
+    ft_refit<FTMS_MAX_SLOTS>(kp1, kp2, mc, count, scores, H, W, N, max_hyp, seed, thr2, min_inliers, motion, Hout, info, mask);    // (N <= FTMS_MAX_SLOTS by ftms_levels_plan)
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
@@ -423,14 +266,9 @@ static int ftms_launch_ransac(const int32_t* kp1, const int32_t* kp2, const int3
                               double thr, int min_inliers, uint32_t seed, double* xy, double* mc, int32_t* scores, float* motion, float* Hout, int32_t* info,
                               uint8_t* mask, hipStream_t s) {
     const int N = V.N;
-    const double thr2 = thr * thr;
     ftms_norm_kernel<<<dim3((N + FT_THREADS - 1) / FT_THREADS, B), FT_THREADS, 0, s>>>(kp1, kp2, matches, count, V, B, H, W, xy, mc);
     ST_CHECK_LAUNCH();
-    const int rc = ft_launch_hyp(mc, count, B, H, W, N, max_hyp, seed, thr2, scores, s);
-    if (rc) return rc;
-    ftms_refit_kernel<<<B, FT_THREADS, 0, s>>>(kp1, kp2, mc, count, scores, H, W, N, max_hyp, seed, thr2, min_inliers, motion, Hout, info, mask);
-    ST_CHECK_LAUNCH();
-    return ST_OK;
+    return ft_launch_hyp_refit(ftms_refit_kernel, kp1, kp2, mc, count, B, H, W, N, max_hyp, thr * thr, min_inliers, seed, scores, motion, Hout, info, mask, s);
 }
 
 extern "C" int st_feature_ms_level_sizes(int32_t H, int32_t W, int32_t levels, int32_t* sizes_host) {
@@ -492,26 +330,18 @@ extern "C" int st_feature_ms_match(const int32_t* kp1, const uint32_t* desc1, co
                                    int32_t* nn_out, int32_t* matches_out, int32_t* count_out, void* stream) {
     ftms_levels V;
     if (!ft_shape_ok(B, H, W) || !ftms_levels_plan(H, W, levels, V)) return ST_EINVAL;
-    const int64_t bn = (int64_t)B * V.N;
-    const ft_region r[7] = {{kp1, 8 * bn, false}, {desc1, 32 * bn, false}, {kp2, 8 * bn, false}, {desc2, 32 * bn, false},
-                            {nn_out, 24 * bn, true}, {matches_out, 8 * bn, true}, {count_out, 4 * B, true}};
-    if (!ft_regions_ok(r, 7)) return ST_EINVAL;
+    if (!ft_match_operands_ok(kp1, desc1, kp2, desc2, nn_out, matches_out, count_out, B, V.N)) return ST_EINVAL;
     return ft_launch_match(kp1, desc1, kp2, desc2, B, V.N, nn_out, matches_out, count_out, (hipStream_t)stream);
 }
 
-// workspace: mc fp64 [B,N,4] then scores int32 [B,max_hyp] = 32 B N + 4 B max_hyp bytes
 extern "C" int st_feature_ms_ransac(const int32_t* kp1, const int32_t* kp2, const int32_t* matches, const int32_t* count, int32_t B, int32_t H, int32_t W, int32_t levels,
                                     int32_t max_hyp, double thr, int32_t min_inliers, int32_t seed, float* motion_out, float* H_out, int32_t* info_out, uint8_t* mask_out,
                                     double* xy_out, void* workspace, int64_t workspace_bytes, void* stream) {
     ftms_levels V;
     if (!ft_shape_ok(B, H, W) || !ftms_levels_plan(H, W, levels, V) || !ft_params_ok(max_hyp, thr, min_inliers)) return ST_EINVAL;
-    const int64_t bn = (int64_t)B * V.N, need = 32 * bn + 4 * (int64_t)B * max_hyp;
-    if (workspace_bytes < need || ((uintptr_t)workspace & 15)) return ST_EINVAL;
-    const ft_region r[10] = {{kp1, 8 * bn, false}, {kp2, 8 * bn, false}, {matches, 8 * bn, false}, {count, 4 * B, false}, {motion_out, 32 * B, true},
-                             {H_out, 36 * B, true}, {info_out, 32 * B, true}, {mask_out, bn, true}, {xy_out, 32 * bn, true}, {workspace, need, true}};
-    if (!ft_regions_ok(r, 10)) return ST_EINVAL;
+    if (!ft_ransac_operands_ok(kp1, kp2, matches, count, motion_out, H_out, info_out, mask_out, xy_out, true, workspace, workspace_bytes, B, V.N, max_hyp)) return ST_EINVAL;
     return ftms_launch_ransac(kp1, kp2, matches, count, B, H, W, V, max_hyp, thr, min_inliers, (uint32_t)seed, xy_out, (double*)workspace,
-                              (int32_t*)((char*)workspace + 32 * bn), motion_out, H_out, info_out, mask_out, (hipStream_t)stream);
+                              (int32_t*)((char*)workspace + 32 * (int64_t)B * V.N), motion_out, H_out, info_out, mask_out, (hipStream_t)stream);
 }
 
 extern "C" int st_feature_ms_homography(const float* img1, const float* img2, int32_t B, int32_t H, int32_t W, int32_t levels, int32_t oriented, int32_t max_hyp, double thr,

@@ -1760,6 +1760,32 @@ def _feature_operand(t, name, dtype, shape):
     return t
 
 
+def _feature_lists(B, N, **operands):
+    """the per-slot operands of the match and ransac stages of both paths, by name: kp* int32 [B,N,2], desc* int32 [B,N,8], matches int32 [B,N,2], count int32 [B]"""
+    for name, t in operands.items():
+        _feature_operand(t, name, torch.int32, (B,) if name == "count" else (B, N, 8) if name.startswith("desc") else (B, N, 2))
+
+
+def _feature_model(B, dev):
+    """the uninitialised (motion fp32 [B,4,2], H fp32 [B,3,3], info int32 [B,8]) that the ransac and homography entries of both paths fill"""
+    return (torch.empty((B, 4, 2), dtype=torch.float32, device=dev), torch.empty((B, 3, 3), dtype=torch.float32, device=dev),
+            torch.empty((B, 8), dtype=torch.int32, device=dev))
+
+
+def _feature_fields(workspace, L, B, N, more=()):
+    """copies of the regions of a workspace with the byte offsets L: the fields that both paths return, and under its own name every (name, bytes,
+    dtype, shape) of `more`"""
+    raw = workspace.view(torch.uint8).reshape(-1)
+
+    def region(name, nbytes, dtype, shape):
+        return raw[L[name]:L[name] + nbytes].view(dtype).reshape(shape).clone()
+    kp = region("kp", 16 * B * N, torch.int32, (2, B, N, 2))
+    desc = region("desc", 64 * B * N, torch.int32, (2, B, N, 8))
+    return dict(kp1=kp[0], kp2=kp[1], desc1=desc[0], desc2=desc[1], nn=region("nn", 24 * B * N, torch.int32, (2, B, N, 3)),
+                matches=region("matches", 8 * B * N, torch.int32, (B, N, 2)), count=region("count", 4 * B, torch.int32, (B,)),
+                mask=region("mask", B * N, torch.uint8, (B, N)), **{r[0]: region(*r) for r in more})
+
+
 def _feature_seed(seed):
     seed = int(seed) & 0xFFFFFFFF
     return seed - (1 << 32) if seed >= 1 << 31 else seed
@@ -1829,9 +1855,7 @@ def feature_match(kp1, desc1, kp2, desc2, H, W):
     B = kp1.shape[0]
     _feature_shape(B, H, W)
     N = feature_slots(H, W)
-    for k, d, n in ((kp1, desc1, "1"), (kp2, desc2, "2")):
-        _feature_operand(k, "kp" + n, torch.int32, (B, N, 2))
-        _feature_operand(d, "desc" + n, torch.int32, (B, N, 8))
+    _feature_lists(B, N, kp1=kp1, desc1=desc1, kp2=kp2, desc2=desc2)
     dev = kp1.device
     nn = torch.empty((2, B, N, 3), dtype=torch.int32, device=dev)
     matches = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
@@ -1846,14 +1870,9 @@ def feature_ransac(kp1, kp2, matches, count, H, W, *, max_hyp=2048, thr=3.0, min
     _feature_shape(B, H, W)
     max_hyp, thr, min_inliers = _feature_params(max_hyp, thr, min_inliers)
     N = feature_slots(H, W)
-    _feature_operand(kp1, "kp1", torch.int32, (B, N, 2))
-    _feature_operand(kp2, "kp2", torch.int32, (B, N, 2))
-    _feature_operand(matches, "matches", torch.int32, (B, N, 2))
-    _feature_operand(count, "count", torch.int32, (B,))
+    _feature_lists(B, N, kp1=kp1, kp2=kp2, matches=matches, count=count)
     dev = kp1.device
-    motion = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
-    Hm = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
-    info = torch.empty((B, 8), dtype=torch.int32, device=dev)
+    motion, Hm, info = _feature_model(B, dev)
     mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
     ws = torch.empty(32 * B * N + 4 * B * max_hyp, dtype=torch.uint8, device=dev)
     check(lib.st_feature_ransac(_pc(kp1), _pc(kp2), _pc(matches), _pc(count), B, H, W, max_hyp, thr, min_inliers, _feature_seed(seed), _p(motion), _p(Hm), _p(info),
@@ -1878,23 +1897,12 @@ def feature_homography(img1, img2, *, max_hyp=2048, thr=3.0, min_inliers=12, see
     dev = img1.device
     if workspace is None:
         workspace = torch.empty(feature_workspace_bytes(B, H, W, max_hyp), dtype=torch.uint8, device=dev)
-    motion = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
-    Hm = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
-    info = torch.empty((B, 8), dtype=torch.int32, device=dev)
+    motion, Hm, info = _feature_model(B, dev)
     check(lib.st_feature_homography(_pc(img1), _pc(img2), B, H, W, max_hyp, thr, min_inliers, _feature_seed(seed), _p(motion), _p(Hm), _p(info), _p(workspace),
                                     workspace.numel() * workspace.element_size(), _stream()), "st_feature_homography")
     if not return_fields:
         return motion, Hm, info
-    N, L, raw = feature_slots(H, W), feature_workspace_layout(B, H, W, max_hyp), workspace.view(torch.uint8).reshape(-1)
-
-    def region(name, nbytes, dtype, shape):
-        return raw[L[name]:L[name] + nbytes].view(dtype).reshape(shape).clone()
-    kp = region("kp", 16 * B * N, torch.int32, (2, B, N, 2))
-    desc = region("desc", 64 * B * N, torch.int32, (2, B, N, 8))
-    fields = dict(kp1=kp[0], kp2=kp[1], desc1=desc[0], desc2=desc[1], nn=region("nn", 24 * B * N, torch.int32, (2, B, N, 3)),
-                  matches=region("matches", 8 * B * N, torch.int32, (B, N, 2)), count=region("count", 4 * B, torch.int32, (B,)),
-                  mask=region("mask", B * N, torch.uint8, (B, N)))
-    return motion, Hm, info, fields
+    return motion, Hm, info, _feature_fields(workspace, feature_workspace_layout(B, H, W, max_hyp), B, feature_slots(H, W))
 
 
 # ---- feature_align_ms: oriented, multi-scale keypoints in front of the same matching and RANSAC (csrc/features_ms.hip; README.md, feature_align_ms) ----
@@ -1992,9 +2000,7 @@ def feature_ms_match(kp1, desc1, kp2, desc2, H, W, levels=6):
     B = kp1.shape[0]
     _feature_shape(B, H, W)
     N = feature_ms_slots(H, W, _feature_ms_levels(levels))
-    for k, d, n in ((kp1, desc1, "1"), (kp2, desc2, "2")):
-        _feature_operand(k, "kp" + n, torch.int32, (B, N, 2))
-        _feature_operand(d, "desc" + n, torch.int32, (B, N, 8))
+    _feature_lists(B, N, kp1=kp1, desc1=desc1, kp2=kp2, desc2=desc2)
     dev = kp1.device
     nn = torch.empty((2, B, N, 3), dtype=torch.int32, device=dev)
     matches = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
@@ -2010,14 +2016,9 @@ def feature_ms_ransac(kp1, kp2, matches, count, H, W, levels=6, *, max_hyp=2048,
     _feature_shape(B, H, W)
     max_hyp, thr, min_inliers = _feature_params(max_hyp, thr, min_inliers)
     N = feature_ms_slots(H, W, _feature_ms_levels(levels))
-    _feature_operand(kp1, "kp1", torch.int32, (B, N, 2))
-    _feature_operand(kp2, "kp2", torch.int32, (B, N, 2))
-    _feature_operand(matches, "matches", torch.int32, (B, N, 2))
-    _feature_operand(count, "count", torch.int32, (B,))
+    _feature_lists(B, N, kp1=kp1, kp2=kp2, matches=matches, count=count)
     dev = kp1.device
-    motion = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
-    Hm = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
-    info = torch.empty((B, 8), dtype=torch.int32, device=dev)
+    motion, Hm, info = _feature_model(B, dev)
     mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
     xy = torch.empty((2, B, N, 2), dtype=torch.float64, device=dev)
     ws = torch.empty(32 * B * N + 4 * B * max_hyp, dtype=torch.uint8, device=dev)
@@ -2042,26 +2043,17 @@ def feature_homography_ms(img1, img2, *, levels=6, oriented=True, max_hyp=2048, 
     dev = img1.device
     if workspace is None:
         workspace = torch.empty(feature_ms_workspace_bytes(B, H, W, levels, max_hyp), dtype=torch.uint8, device=dev)
-    motion = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
-    Hm = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
-    info = torch.empty((B, 8), dtype=torch.int32, device=dev)
+    motion, Hm, info = _feature_model(B, dev)
     check(lib.st_feature_ms_homography(_pc(img1), _pc(img2), B, H, W, levels, int(bool(oriented)), max_hyp, thr, min_inliers, _feature_seed(seed), _p(motion), _p(Hm),
                                        _p(info), _p(workspace), workspace.numel() * workspace.element_size(), _stream()), "st_feature_ms_homography")
     if not return_fields:
         return motion, Hm, info
-    N, L, raw = feature_ms_slots(H, W, levels), feature_ms_workspace_layout(B, H, W, levels, max_hyp), workspace.view(torch.uint8).reshape(-1)
-    sizes = feature_ms_level_sizes(H, W, levels)
-
-    def region(name, nbytes, dtype, shape):
-        return raw[L[name]:L[name] + nbytes].view(dtype).reshape(shape).clone()
-    kp = region("kp", 16 * B * N, torch.int32, (2, B, N, 2))
-    desc = region("desc", 64 * B * N, torch.int32, (2, B, N, 8))
-    bins = region("bins", 2 * B * N, torch.uint8, (2, B, N))
-    pyr = _feature_ms_split(region("pyr", 2 * B * sum(h * w for h, w in sizes), torch.uint8, (-1,)), 2 * B, sizes)
-    fields = dict(kp1=kp[0], kp2=kp[1], desc1=desc[0], desc2=desc[1], bins1=bins[0], bins2=bins[1], pyr1=[p[:B] for p in pyr], pyr2=[p[B:] for p in pyr],
-                  nn=region("nn", 24 * B * N, torch.int32, (2, B, N, 3)), matches=region("matches", 8 * B * N, torch.int32, (B, N, 2)),
-                  count=region("count", 4 * B, torch.int32, (B,)), mask=region("mask", B * N, torch.uint8, (B, N)),
-                  xy=region("xy", 32 * B * N, torch.float64, (2, B, N, 2)))
+    N, sizes = feature_ms_slots(H, W, levels), feature_ms_level_sizes(H, W, levels)
+    fields = _feature_fields(workspace, feature_ms_workspace_layout(B, H, W, levels, max_hyp), B, N,
+                             (("bins", 2 * B * N, torch.uint8, (2, B, N)), ("pyr", 2 * B * sum(h * w for h, w in sizes), torch.uint8, (-1,)),
+                              ("xy", 32 * B * N, torch.float64, (2, B, N, 2))))
+    bins, pyr = fields.pop("bins"), _feature_ms_split(fields.pop("pyr"), 2 * B, sizes)
+    fields.update(bins1=bins[0], bins2=bins[1], pyr1=[p[:B] for p in pyr], pyr2=[p[B:] for p in pyr])
     return motion, Hm, info, fields
 
 

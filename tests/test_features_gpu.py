@@ -135,6 +135,45 @@ def test_ransac_on_planted_matches(name):
     assert want[2][0] == (name in ("m8", "outliers"))
 
 
+@functools.lru_cache(maxsize=None)
+def _full_list():
+    """synthetic keypoints in all N = 4096 slots of 1024x1024 and a list over every slot, the last slot first (built like _long_list of
+    test_features_ms_gpu.py): a slot's partner is its image under a homography, rounded to the pixel, every fifth one displaced by 12 px or more.
+    List position 4095, the last inlier flag the refit kernel holds, is slot 0: an inlier."""
+    H = W = 1024
+    rng = np.random.default_rng(4096)
+    N = ref.slots(H, W)
+    assert N == 4096
+    kp1 = np.stack([rng.integers(16, W - 16, N), rng.integers(16, H - 16, N)], 1).astype(np.int32)
+    q = np.c_[kp1, np.ones(N)] @ ref.homography_matrix(H, W, 7, -5, 3.0, 2e-5, -1e-5).T
+    q = np.rint(q[:, :2] / q[:, 2:]).astype(np.int64)
+    out = np.arange(N) % 5 == 2
+    q[out] += rng.integers(12, 40, (int(out.sum()), 2))
+    partner = rng.permutation(N)
+    kp2 = np.full((N, 2), -1, np.int32)
+    kp2[partner] = np.clip(q, 0, [W - 1, H - 1])
+    return kp1, kp2, np.stack([np.arange(N)[::-1], partner[::-1]], 1).astype(np.int32)
+
+
+@pytest.mark.parametrize("m", (4096, 4095))
+def test_ransac_on_a_list_that_fills_every_slot(m):
+    """N = 4096, the most a single-scale call has: the inlier flags fill the refit kernel's array to its last byte, and to one before it"""
+    from stitch_amd import ops
+    H = W = 1024
+    kp1, kp2, matches = _full_list()
+    matches = matches.copy()
+    matches[m:] = -1
+    kw = dict(max_hyp=2048, thr=3.0, min_inliers=12, seed=1)
+    want = ref.ransac(kp1, kp2, matches, m, H, W, **kw)
+    got = ops.feature_ransac(*_dev([kp1[None], kp2[None], matches[None], np.array([m], np.int32)]), H, W, **kw)
+    for g, x, name in zip(got, want, ("motion", "H", "info", "mask")):
+        g = g[0].cpu().numpy()
+        assert g.dtype == x.dtype and g.shape == x.shape and np.array_equal(g.view(np.uint8), x.view(np.uint8)), (name, g, x)
+    info, mask = want[2], want[3]
+    assert info[0] == 1 and info[1] == info[2] == 4096 and info[3] == m and info[5] == mask[:m].sum() > 0.7 * m
+    assert mask[4094] == 1 and mask[4095] == (m == 4096)
+
+
 @pytest.fixture(scope="module")
 def two_cases():
     return _pair(160, 129), _want(160, 129), _pair(96, 128), _want(96, 128)
